@@ -8,7 +8,14 @@ GPUs additionally ONE flat RCCL all-reduce of the gradients (weak scaling: 256 g
 Inputs (synthetic D0 start positions, or D1 random playouts with --data D1) are resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config L256|S256|MIX] [--data D0|D1]
+A plain run sets up, preheats, warms up, times the K steps and prints the headline line.  Everything else it can
+measure or check -- the sustained window, the per-kernel roofline passes, the split-precision timing, the other
+BASELINE configurations, the CPU baseline, the collective probe, the replica check of N > 1 -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (loss, per-graph TD error, Q-values, every parameter
+gradient) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config L256|S256|MIX] [--data D0|D1] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -233,7 +240,7 @@ def main():
                          "--batch-graph batch per step, split over the GPUs by edge count (gnn_hex_amd.dist.balance_by_edges); "
                          "value = --batch graphs per step time")
     ap.add_argument("--sustain-s", type=float, default=2.0,
-                    help="after the K timed steps, repeat the step for at least this many seconds and report that window as "
+                    help="--full: after the K timed steps, repeat the step for at least this many seconds and report that window as "
                          "`sustained` (never `value`); 0 disables it")
     ap.add_argument("--no-overlap", action="store_true",
                     help="N > 1: one all-reduce after the backward instead of the staged backward whose first gradient "
@@ -255,7 +262,18 @@ def main():
                     help="skip the extra lines for the other single-GPU BASELINE configurations (D1 boards, GNN-S, MIX) that "
                          "the default N=1 run appends as `other_configs`")
     ap.add_argument("--no-split", action="store_true", help="skip the informational split-precision timing (clean profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the sustained window, the per-kernel "
+                         "roofline passes, the split-precision timing, the other configurations, the CPU baseline, the "
+                         "collective probe and (N > 1) the replica check; the --no-* / --sustain-s options above act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, td, q, grad.<parameter>) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded sample of larger arrays)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "train":
+        raise SystemExit("--dump-outputs writes the training step's outputs: --mode train only")
     if args.graph is None:
         args.graph = args.mode == "train"
     if args.no_pack:
@@ -328,6 +346,8 @@ def main():
     if args.plain_autograd and args.graph:
         raise SystemExit("--plain-autograd is an --eager measurement (the step an unmodified train.py issues)")
 
+    # every form of the step returns what its caller receives, (loss, td, q) -- td None where the form does not
+    # compute it -- beside the parameter gradients (--dump-outputs writes those of the last timed step)
     def step(i):
         bt = batches[i & 1]
         for p in plist:              # optimizer.zero_grad(set_to_none=True) over a cached parameter list
@@ -338,15 +358,19 @@ def main():
             d = q[bt["sel"]]
             loss = torch.nn.functional.mse_loss(d, bt["tgt"]) if bt["w"] is None else (bt["w"] * (d - bt["tgt"]) ** 2).mean()
             loss.backward()
+            res = (loss, None, q)
         elif td_fused:
             # the same three calls in their fused form (ops.td_step: the loss is formed in the forward kernel's tail)
-            hexops.td_step(hip, bt["x"], bt["ei"], bt["bv"], bt["ptr"], sel=bt["sel"], target=bt["tgt"], weights=bt["w"])
+            res = hexops.td_step(hip, bt["x"], bt["ei"], bt["bv"], bt["ptr"], sel=bt["sel"], target=bt["tgt"],
+                                 weights=bt["w"])
         else:
             q = hip(bt["x"], bt["ei"], bt["bv"], bt["ptr"])
-            loss, _ = hexops.td_loss(q, bt["sel"], bt["tgt"], bt["w"])
+            loss, td = hexops.td_loss(q, bt["sel"], bt["tgt"], bt["w"])
             hexops.backward(loss)   # == loss.backward(), minus autograd's ones-fill and the TD scatter launch (ops.backward)
+            res = (loss, td, q)
         if world > 1:
             sync.all_reduce()
+        return res
 
     if args.graph:
         from gnn_hex_amd.graphs import GraphedStep
@@ -357,11 +381,11 @@ def main():
                     p.grad = None
                 if td_fused:
                     return hexops.td_step(hip, bt["x"], bt["ei"], bt["bv"], bt["ptr"], sel=bt["sel"], target=bt["tgt"],
-                                          weights=bt["w"])[0]
+                                          weights=bt["w"])
                 q = hip(bt["x"], bt["ei"], bt["bv"], bt["ptr"])
-                loss, _ = hexops.td_loss(q, bt["sel"], bt["tgt"], bt["w"])
+                loss, td = hexops.td_loss(q, bt["sel"], bt["tgt"], bt["w"])
                 hexops.backward(loss)
-                return loss
+                return loss, td, q
             return fn
 
         split = args.split_graph
@@ -379,9 +403,9 @@ def main():
                 def fn():
                     for p in plist:
                         p.grad = None
-                    loss, _, _, call = hexops.td_step(hip, bt["x"], bt["ei"], bt["bv"], bt["ptr"], sel=bt["sel"],
-                                                      target=bt["tgt"], weights=bt["w"], defer_lower=True)
-                    return loss, call
+                    loss, td, q, call = hexops.td_step(hip, bt["x"], bt["ei"], bt["bv"], bt["ptr"], sel=bt["sel"],
+                                                       target=bt["tgt"], weights=bt["w"], defer_lower=True)
+                    return (loss, td, q), call
                 return fn
 
             g0 = GraphedSplitStep(first_of(batches[0]), hexops.finish_backward, plist)
@@ -391,7 +415,7 @@ def main():
 
             def step(i):
                 gr = graphs[i & 1]
-                gr.replay_first()
+                res = gr.replay_first()
                 if gr.flat is not None and world > 1:
                     sync.reduce_segment(gr.flat, gr.cut, gr.total)
                 gr.replay_second()
@@ -399,15 +423,17 @@ def main():
                     if gr.flat is not None:
                         sync.reduce_segment(gr.flat, 0, gr.cut)
                     sync.all_reduce()
+                return res
         else:
             g0 = GraphedStep(local_step(batches[0]), plist)
             g1 = GraphedStep(local_step(batches[1]), plist, pool=g0.pool())
             graphs = (g0, g1)
 
             def step(i):
-                graphs[i & 1].replay()
+                res = graphs[i & 1].replay()
                 if world > 1:
                     sync.all_reduce()
+                return res
 
     with _stdout_to_stderr():
         init_group()
@@ -450,8 +476,9 @@ def main():
         step(i)
     barrier()
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(i)
+    last = step(args.steps - 1)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -460,11 +487,15 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = B * gfactor * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # before anything else steps again: a captured step's outputs live in its graph's pool
+        dump_outputs(args.dump_outputs, last, hip.named_parameters())
+    del last
 
     # what holds under load: the same step for >= `--sustain-s` seconds (same count on every rank), reported beside the
     # K-step line (`value` stays the driver's protocol).  The short window can sit inside a boost period of the box.
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         ks = max(args.steps, int(args.sustain_s / (dt / args.steps)) + 1)
         barrier()
         t1 = time.perf_counter()
@@ -481,7 +512,7 @@ def main():
     # N > 1: the replicas must stay identical -- one more step, a plain SGD update from the all-reduced gradients on every
     # rank, then the parameter checksums of all ranks are compared (a rank that reduced a different bucket would diverge)
     replicas_identical = None
-    if world > 1:
+    if world > 1 and args.full:
         step(0)
         with torch.no_grad():
             for p in plist:
@@ -498,8 +529,12 @@ def main():
             raise SystemExit("rank %d: parameter replicas diverged after the gradient all-reduce: %s" % (rank, gathered))
         sync.enable_overlap(False)       # the rank-0-only passes below must not start collectives
 
-    out = None
-    if rank == 0:
+    # --full: the per-kernel roofline, the split-precision timing, the other configurations, the CPU baseline and the
+    # collective probe (rank 0)
+    roof = split = others = cpu = probe = None
+    if rank == 0 and not args.full:
+        note("timed region done: %.4f ms/step" % ms_per_step)
+    if rank == 0 and args.full:
         note("timed region done: %.4f ms/step; per-kernel HIP-event passes" % ms_per_step)
         # ---- live per-kernel timing (HIP events on the launch stream) over the same steps ---------------
         L = _lib.lib()
@@ -603,6 +638,8 @@ def main():
         if world == 1 and not args.no_collective_probe:
             probe = collective_probe_child(4 * sum(p.numel() for p in plist if p.grad is not None))
 
+    out = None
+    if rank == 0:
         out = {
             "metric": "board-graphs/sec fwd+bwd", "value": value, "unit": "graphs/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "preheat_steps": preheat_steps, "ms_per_step": ms_per_step,
@@ -751,6 +788,29 @@ def collective_probe(dev, nbytes, reps=50):
                 "note": "1-rank RCCL group on this GPU: launch + kernel latency of the per-step gradient all-reduce, no wire time"}
     except Exception as exc:  # noqa: BLE001
         return {"backend": "rccl", "world": 1, "error": "%s: %s" % (type(exc).__name__, exc)}
+
+
+def dump_outputs(path, res, named_params, cap_bytes=60 << 20):
+    """What the last timed step handed its caller -- `loss`, `td` (per-graph TD error, where the step form computes it),
+    `q` (Q-values of every node) and `grad.<parameter name>` -- as <path>/<name>.npy in float32, within 64 MB.  Above
+    `cap_bytes` of data in all, every array is cut to the same share of its elements, a fixed seeded (seed 0) sample in flat index order."""
+    import numpy as np
+    arrays = {}
+    for name, t in zip(("loss", "td", "q"), res):
+        if torch.is_tensor(t):
+            arrays[name] = t.detach().float().cpu().numpy()
+    for name, p in named_params:
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if total > cap_bytes:
+            k = max(1, a.size * cap_bytes // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("[bench] wrote %d output arrays to %s" % (len(arrays), path), file=sys.stderr, flush=True)
 
 
 def step_local(hip, batches, i):

@@ -31,12 +31,12 @@ for c in S256 MIX; do
   echo "stats $c done"
 done
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-python3 bench.py --steps 20 --warmup 5 --eager --no-cpu-baseline --no-other-configs --no-split > $O/bench_eager.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --config S256 --eager --no-cpu-baseline --no-split > $O/bench_S256_eager.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --config S256 --no-cpu-baseline --no-split > $O/bench_S256.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --config MIX --no-cpu-baseline --no-split > $O/bench_MIX.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --data D1 --no-cpu-baseline --no-split --no-other-configs > $O/bench_D1.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 --eager --no-cpu-baseline --no-other-configs --no-split > $O/bench_eager.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --config S256 --eager --no-cpu-baseline --no-split > $O/bench_S256_eager.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --config S256 --no-cpu-baseline --no-split > $O/bench_S256.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --config MIX --no-cpu-baseline --no-split > $O/bench_MIX.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --data D1 --no-cpu-baseline --no-split --no-other-configs > $O/bench_D1.json 2>/dev/null
 echo "bench lines done"
 # only summaries travel back (gpurun merges at most 64 MiB): kernel-stats CSVs, the PMC figures as JSON, the bench lines
 S=$R/gpurun_out/r03_summary

@@ -24,13 +24,13 @@ for c in ${PROFILE_CONFIGS:-L256 S256 MIX}; do
 done
 cd $R
 [ -z "$PROFILE_SKIP_PMC" ] && python3 profiles/pmc_to_json.py --by-tag $O ${PROFILE_CONFIGS:-L256 S256 MIX} > $S/traffic_pmc.json
-python3 bench.py --steps 20 --warmup 5 > $S/bench_default.json 2> $S/bench_default.err
-python3 bench.py --steps 20 --warmup 5 --config S256 --no-cpu-baseline --no-split > $S/bench_S256.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --config MIX --no-cpu-baseline --no-split > $S/bench_MIX.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --data D1 --no-cpu-baseline --no-split --no-other-configs > $S/bench_D1.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --eager --no-cpu-baseline --no-other-configs --no-split > $S/bench_eager.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --config S256 --eager --no-cpu-baseline --no-split > $S/bench_S256_eager.json 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --config S256 --eager --plain-autograd --no-cpu-baseline --no-split > $S/bench_S256_eager_plain.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 > $S/bench_default.json 2> $S/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 --config S256 --no-cpu-baseline --no-split > $S/bench_S256.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --config MIX --no-cpu-baseline --no-split > $S/bench_MIX.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --data D1 --no-cpu-baseline --no-split --no-other-configs > $S/bench_D1.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --eager --no-cpu-baseline --no-other-configs --no-split > $S/bench_eager.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --config S256 --eager --no-cpu-baseline --no-split > $S/bench_S256_eager.json 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --config S256 --eager --plain-autograd --no-cpu-baseline --no-split > $S/bench_S256_eager_plain.json 2>/dev/null
 echo "bench lines done"
 rm -rf $O/*/*.db 2>/dev/null
 ls -la $S

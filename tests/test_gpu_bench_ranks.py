@@ -24,7 +24,8 @@ def test_bench_two_ranks_gloo_rehearsal(config, data, issue):
     (empty) graph, and the one-launch stack kernels leave 64 CUs to the collective's kernels (hexgnn_stack_reserve_cus)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", config,
-           "--data", data, "--steps", "6", "--warmup", "2", "--preheat-ms", "20", "--no-cpu-baseline", "--no-split", issue]
+           "--data", data, "--steps", "6", "--warmup", "2", "--preheat-ms", "20", "--no-cpu-baseline", "--no-split", "--full",
+           issue]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -45,7 +46,7 @@ def test_bench_four_ranks_gloo_rehearsal():
     bookkeeping (global batch 1024, value = 1024 graphs / step time) and identical replicas after the averaged update."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--config", "S256",
-           "--data", "D1", "--steps", "4", "--warmup", "1", "--preheat-ms", "10", "--no-cpu-baseline", "--no-split"]
+           "--data", "D1", "--steps", "4", "--warmup", "1", "--preheat-ms", "10", "--no-cpu-baseline", "--no-split", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -65,7 +66,7 @@ def test_bench_two_ranks_strong_scaling(config):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", config,
            "--data", "D1", "--steps", "4", "--warmup", "1", "--preheat-ms", "10", "--sustain-s", "0", "--no-cpu-baseline",
-           "--no-split", "--scaling", "strong"]
+           "--no-split", "--full", "--scaling", "strong"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -37,39 +37,61 @@ def test_start_graph_closed_form_and_golden_csr(hexref, n):
     assert np.array_equal(s, gold["s%d" % n]) and np.array_equal(t, gold["t%d" % n]) and np.array_equal(es, gold["es%d" % n])
 
 
+def _container_answers(g, ops):
+    """Run the ops (a, b, kind) through a Graph container: add_edge / delete_edge answers (-1 after clear_vertex),
+    edge_exists(a, b) after every op, and the final CSR."""
+    ret, exists = [], []
+    for a, b, op in ops.tolist():
+        if op < 6:
+            ret.append(int(g.add_edge(a, b)))
+        elif op < 9:
+            ret.append(int(g.delete_edge(a, b)))
+        else:
+            g.clear_vertex(a)
+            ret.append(-1)
+        exists.append(int(g.edge_exists(a, b)))
+    s, t, es = g.dump()
+    return dict(ret=np.array(ret, np.int8), exists=np.array(exists, np.int8), s=s, t=t, es=es)
+
+
 def test_reference_graph_container_live(hexref):
-    """When oracle/_ref is present: the reference's own Graph (graph.cpp) against the oracle's bit matrix under a
-    random add/delete/clear sequence, and the start graph rebuilt live."""
+    """The reference's own Graph (graph.cpp) against the oracle's bit matrix under a random add/delete/clear sequence:
+    its answers as recorded in tests/golden/graph_container_ops.npz (oracle/make_golden.py), and, when oracle/_ref is
+    built, the same answers and the start graph rebuilt live."""
     from oracle import ref_graph
-    if not ref_graph.available():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    s, t, es = ref_graph.start_graph_via_reference_container(11)
-    gs, gt, ges = _csr_of(hexref.RefGame(11))
-    assert np.array_equal(s, gs) and np.array_equal(t, gt) and np.array_equal(es, ges)
+    gold = np.load(os.path.join(GOLD, "graph_container_ops.npz"))
     rng = np.random.default_rng(0)
     nv = 40
-    g = ref_graph.RefGraph(nv)
-    adj = np.zeros((nv, nv), dtype=bool)
+    ops = []
     for _ in range(3000):
         a, b = rng.integers(0, nv, 2)
         op = rng.integers(0, 10)
-        if a == b:
-            continue
+        if a != b:
+            ops.append((int(a), int(b), int(op)))
+    ops = np.array(ops, np.int32)
+    assert np.array_equal(ops, gold["ops"])
+    if ref_graph.available():
+        s, t, es = ref_graph.start_graph_via_reference_container(11)
+        gs, gt, ges = _csr_of(hexref.RefGame(11))
+        assert np.array_equal(s, gs) and np.array_equal(t, gt) and np.array_equal(es, ges)
+        live = _container_answers(ref_graph.RefGraph(nv), ops)
+        for k, v in live.items():
+            assert np.array_equal(v, gold[k]), k
+    adj = np.zeros((nv, nv), dtype=bool)
+    for k, (a, b, op) in enumerate(ops.tolist()):
         if op < 6:
-            assert g.add_edge(int(a), int(b)) == (not adj[a, b])
+            assert gold["ret"][k] == (not adj[a, b])
             adj[a, b] = adj[b, a] = True
         elif op < 9:
-            assert g.delete_edge(int(a), int(b)) == bool(adj[a, b])
+            assert gold["ret"][k] == bool(adj[a, b])
             adj[a, b] = adj[b, a] = False
         else:
-            g.clear_vertex(int(a))
             adj[a, :] = False
             adj[:, a] = False
-        assert g.edge_exists(int(a), int(b)) == bool(adj[a, b])
-    s, t, es = g.dump()
+        assert gold["exists"][k] == bool(adj[a, b])
     rs, rt = np.nonzero(adj)                  # row-major => sorted adjacency rows, as the reference keeps them
-    assert np.array_equal(s, rs) and np.array_equal(t, rt)
-    assert np.array_equal(es, np.concatenate([[0], np.cumsum(adj.sum(1))]))
+    assert np.array_equal(gold["s"], rs) and np.array_equal(gold["t"], rt)
+    assert np.array_equal(gold["es"], np.concatenate([[0], np.cumsum(adj.sum(1))]))
 
 
 @pytest.mark.parametrize("size,games", [(5, 150), (7, 150), (11, 200)])

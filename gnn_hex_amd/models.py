@@ -613,54 +613,52 @@ class DuellingTwoHeaded(torch.nn.Module):
         # graphs above 128 nodes / hidden 113..128: the same network on the layer-major kernels, as ONE stack + head tail
         layered = (not fused) and fusable and not noisy and ops._DIRECT_GRADS and c_in <= 8 and c_in != h \
             and x2.shape[1] == c_in and n_body >= 1
+        grad_on = torch.is_grad_enabled()
+        direct = False
         if fused or layered:
-            grad_on = torch.is_grad_enabled()
-            if ops._DIRECT_GRADS and not noisy:
-                # direct-gradient form (ops.QNetDirectFn): cached pointer arrays, one autograd input, gradients assigned to
-                # p.grad by the backward itself -- the eager step of an unmodified train.py
-                cache = ent[2]
-                if not cache.valid():
-                    cache.refresh()
-                if cache.direct_ok or not grad_on:
-                    # (a deferred grouped CSR build goes in as the tuple: built WITH the weight pack, in one launch)
-                    fargs = (cache, x2, gs if gs is not None else deferred, gptr, b, c_in, h, n_body, n_head, mode, grad_on,
-                             layered)
-                    if grad_on:
-                        anchor = self.__dict__.get("_hex_anchor")
-                        if anchor is None or anchor.device != x.device:
-                            anchor = torch.zeros(1, device=x.device, requires_grad=True)
-                            self.__dict__["_hex_anchor"] = anchor
-                        holder = []
-                        outs = ops.QNetDirectFn.apply(anchor, holder, fargs)
-                        call = holder[0]
-                        call.sink = self.activations_hook
-                        q, out_v = outs if mode == 1 else (outs, None)
-                        if mode == 0:
-                            q._hex_call = call          # lets ops.td_loss / ops.backward run this backward directly
-                            # (the loss expression of an unmodified training loop -- q[actions], F.mse_loss, loss.backward()
-                            # -- recognised on the tensor itself: gnn_hex_amd/qvalues.py)
-                            q = qvalues.wrap_q(q)
-                    else:
-                        q, out_v, call = ops.qnet_direct_forward(*fargs)
-                    self.__dict__["_fca"] = call
-                    if mode == 2:
-                        return q.view(-1, 1)
-                    if mode == 1:
-                        return out_v, q
-                    return q
-            if layered:
-                fused = False       # (frozen / hooked parameters: the per-module composition below)
+            cache = ent[2]                     # (None for noisy heads: their weights are formed per forward)
+            if cache is not None and not cache.valid():
+                cache.refresh()
+            # direct-gradient form (ops.QNetDirectFn): cached pointer arrays, one autograd input, gradients assigned to p.grad
+            # by the backward itself -- the eager step of an unmodified train.py.  Else the autograd form (ops.QNetFusedFn) on
+            # the fused kernels, the per-module composition below on the layer-major ones.
+            direct = cache is not None and ops._DIRECT_GRADS and (cache.direct_ok or not grad_on)
+        if direct:
+            # (a deferred grouped CSR build goes in as the tuple: built WITH the weight pack, in one launch)
+            fargs = (cache, x2, gs if gs is not None else deferred, gptr, b, c_in, h, n_body, n_head, mode, grad_on, layered)
+            if grad_on:
+                anchor = self.__dict__.get("_hex_anchor")
+                if anchor is None or anchor.device != x.device:
+                    anchor = torch.zeros(1, device=x.device, requires_grad=True)
+                    self.__dict__["_hex_anchor"] = anchor
+                holder = []
+                outs = ops.QNetDirectFn.apply(anchor, holder, fargs)
+                call = holder[0]
+                call.sink = self.activations_hook
+                q, out_v = outs if mode == 1 else (outs, None)
+                if mode == 0:
+                    q._hex_call = call          # lets ops.td_loss / ops.backward run this backward directly
+                    # (the loss expression of an unmodified training loop -- q[actions], F.mse_loss, loss.backward()
+                    # -- recognised on the tensor itself: gnn_hex_amd/qvalues.py)
+                    q = qvalues.wrap_q(q)
+            else:
+                q, out_v, call = ops.qnet_forward(*fargs)
+            self.__dict__["_fca"] = call
+            if mode == 2:
+                return q.view(-1, 1)
+            if mode == 1:
+                return out_v, q
+            return q
         if gs is None:              # every other path: the structure now
             gs = ops.GraphStructure.grouped(*deferred)
         if fused:
-            grad_on = torch.is_grad_enabled()
             params = ent[1]
             if noisy:      # effective weights are formed per forward
                 params = params[:-6] + list(head._lin_params()) + params[-4:]
             sink = self.activations_hook if grad_on else None
             if gptr is None:
                 gptr = gs.gptr
-            outs = ops.QNetFusedFn.apply(x2, gs, gptr, b, c_in, h, n_body, n_head, mode, sink, *params)
+            outs = ops.QNetFusedFn.apply(cache, x2, gs, gptr, b, c_in, h, n_body, n_head, mode, sink, *params)
             self.final_conv_acts = outs[-1]
             if mode == 2:
                 return outs[0].view(-1, 1)
@@ -723,9 +721,6 @@ class DuellingTwoHeaded(torch.nn.Module):
             ent = (sig, params, qcache, (self.gnn.in_channels, h, n_body, n_head, fusable, noisy))
             cache[key] = ent
         return ent
-
-    def _fused_params(self, head):
-        return self._fused_entry(head)[1]
 
     def _apply(self, fn, *args, **kwargs):
         self.__dict__.pop("_fused_cache", None)

@@ -898,136 +898,19 @@ def qnet_fused_supported(c_in: int, hidden: int, max_nodes: int) -> bool:
     return ok
 
 
-class QNetFusedFn(torch.autograd.Function):
-    """DuellingTwoHeaded.forward (GN0/models.py:537-584) as ONE kernel launch; backward = one data-chain launch +
-    the batched weight-gradient GEMM.  Outputs: mode 0 -> (Q, embeds); 1 -> (V, A-mean(A), embeds);
-    2 -> (2tanh(adv), embeds).  ``embeds`` (final_conv_acts) is returned non-differentiable; its gradient is handed
-    to ``grad_sink(d_embeds)`` during backward (final_conv_grads / Grad-CAM)."""
-
-    @staticmethod
-    def forward(ctx, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
-                head_layers: int, mode: int, grad_sink, *params):
-        L = _lib.lib()
-        ctx.set_materialize_grads(False)      # unused outputs (embeds, V) arrive as None instead of freshly zeroed tensors
-        dev = x.device
-        n = int(x.shape[0])
-        hp = padded_width(hidden)
-        tot = body_layers + head_layers
-        if x.dtype != torch.float32 or x.stride(1) != 1:
-            x = x.float().contiguous()
-        x_stride = x.stride(0) if n > 0 else c_in
-        # a parameter that is computed per forward (FactorizedNoisyLinear's mu + sigma * eps) is no leaf: its gradient is
-        # an intermediate that autograd still has to carry to mu / sigma, so it must not be all-reduced in place
-        ctx.nonleaf_params = any(p.grad_fn is not None for p in params)
-        params = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous() for p in params]
-        convs, tail = params[:3 * tot], params[3 * tot:]
-        wl, bl, wr = convs[0::3], convs[1::3], convs[2::3]
-        need_bwd = any(ctx.needs_input_grad)
-        acts = torch.empty((tot, n, hp), dtype=torch.float32, device=dev)
-        wpack = _bytes(L.hexgnn_sage_stack_pack_bytes(c_in, hidden, tot), dev)
-        saved = _bytes(L.hexgnn_qnet_saved_bytes(n, b, c_in, hidden, tot), dev)
-        q = torch.empty(n, dtype=torch.float32, device=dev)
-        out_v = torch.empty(b, dtype=torch.float32, device=dev) if mode == 1 else None
-        status = gs.status      # shared status word (OR-ed into by the kernels)
-        _lib.check(L.hexgnn_qnet_forward(
-            n, b, c_in, hidden, tot, mode, gptr.data_ptr(), gs.rowptr.data_ptr(), gs.col.data_ptr(),
-            gs.invdeg.data_ptr(), x.data_ptr(), x_stride, _ptr_array(wl), _ptr_array(bl), _ptr_array(wr),
-            tail[0].data_ptr(), tail[1].data_ptr(), tail[2].data_ptr(), tail[3].data_ptr(), tail[4].data_ptr(),
-            tail[5].data_ptr(), wpack.data_ptr(), acts.data_ptr(), saved.data_ptr(), int(need_bwd), body_layers - 1, _MATH,
-            q.data_ptr(),
-            out_v.data_ptr() if out_v is not None else None, status.data_ptr(), _stream()), "hexgnn_qnet_forward")
-        embeds = acts[body_layers - 1][:, :hidden]
-        ctx.mark_non_differentiable(embeds)
-        if need_bwd:
-            ctx.gs, ctx.gptr = gs, gptr
-            ctx.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride)
-            ctx.math = _MATH
-            ctx.bufs = (x, acts, saved, wpack, tail, status)
-            ctx.params = params
-            # flat gradient layout follows model.parameters() order (convs..., value_head.layers.*, linear.*) so that
-            # GradSync can all-reduce the buffer in place; the call's tail order is (lin_w, lin_b, v0_w, v0_b, v1_w, v1_b)
-            nconv = 3 * tot
-            flat_order = list(range(nconv)) + [nconv + 2, nconv + 3, nconv + 4, nconv + 5, nconv + 0, nconv + 1]
-            offs, o = [0] * len(params), 0
-            for i in flat_order:
-                offs[i] = o
-                o += params[i].numel()
-            ctx.param_offsets = (offs, o, flat_order)
-            ctx.grad_sink = grad_sink
-        if mode == 1:
-            return out_v, q, embeds
-        return q, embeds
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        L = _lib.lib()
-        n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride = ctx.dims
-        x, acts, saved, wpack, tail, status = ctx.bufs
-        gs, gptr = ctx.gs, ctx.gptr
-        dev = acts.device
-        if mode == 1:
-            d_v, dq = gouts[0], gouts[1]
-            d_v = torch.zeros(b, dtype=torch.float32, device=dev) if d_v is None else d_v.float().contiguous()
-        else:
-            dq, d_v = gouts[0], None
-        dq = torch.zeros(n, dtype=torch.float32, device=dev) if dq is None else dq.float().contiguous()
-        # ONE flat gradient buffer for all parameters (views are handed to autograd): one allocation instead of
-        # 66, and the layout a single RCCL all-reduce wants (gnn_hex_amd.dist.GradSync adopts it without copies).
-        params = ctx.params
-        offs, total, flat_order = ctx.param_offsets
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        ordered = torch._C._nn.unflatten_dense_tensors(flat, [params[i] for i in flat_order])
-        grads = [None] * len(params)
-        for i, gview in zip(flat_order, ordered):
-            grads[i] = gview
-        base = flat.data_ptr()
-        ptrs = [base + 4 * o for o in offs]
-        cp, tp = ptrs[:3 * tot], ptrs[3 * tot:]
-        vp_arr = C.c_void_p * tot
-        d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if ctx.grad_sink is not None else None
-        ws_bytes = L.hexgnn_qnet_backward_workspace_bytes(n, b, c_in, hidden, tot)
-        ws = _bytes(ws_bytes, dev)
-        common = (n, b, c_in, hidden, tot, body_layers, mode, ctx.math, gptr.data_ptr(), gs.rowptr_t.data_ptr(),
-                  gs.col_t.data_ptr(), gs.invdeg.data_ptr(), x.data_ptr(), x_stride, acts.data_ptr(), saved.data_ptr(),
-                  wpack.data_ptr(), tail[0].data_ptr(), tail[2].data_ptr(), tail[4].data_ptr(), dq.data_ptr(),
-                  d_v.data_ptr() if d_v is not None else None, d_emb.data_ptr() if d_emb is not None else None,
-                  vp_arr(*cp[0::3]), vp_arr(*cp[1::3]), vp_arr(*cp[2::3]), tp[0], tp[1], tp[2], tp[3], tp[4], tp[5],
-                  ws.data_ptr(), ws_bytes, status.data_ptr())
-        hook = _GRAD_STAGE_HOOK
-        if hook is None or tot < 3 or mode == 2 or ctx.nonleaf_params:
-            # (non-leaf parameters, --noisy_dqn=True: d_sigma = d_w * eps with per-rank noise is not the average of the ranks'
-            # d_sigma if d_w is averaged first, and the mu / sigma gradients live outside the flat buffer: no staging, GradSync
-            # reduces the finished .grad tensors through its bucket)
-            _lib.check(L.hexgnn_qnet_backward(*common, _stream()), "hexgnn_qnet_backward")
-        else:
-            # two stages: the upper half of the hidden layers + everything small first -- with the head tail they are the
-            # TAIL of the flat buffer, handed to the hook (all-reduce on the collective's own stream) while the lower
-            # half's weight-gradient GEMM is enqueued behind them; then the head of the buffer
-            mid = 1 + tot // 2
-            _lib.check(L.hexgnn_qnet_backward_staged(*common, 1 | 2 | 4, mid, tot, _stream()), "hexgnn_qnet_backward_staged")
-            hook(flat, offs[3 * mid], total)
-            _lib.check(L.hexgnn_qnet_backward_staged(*common, 4, 1, mid, _stream()), "hexgnn_qnet_backward_staged")
-            hook(flat, 0, offs[3 * mid])
-        cg, tg = grads[:3 * tot], grads[3 * tot:]
-        if ctx.grad_sink is not None:
-            ctx.grad_sink(d_emb[:, :hidden])
-        if mode == 2:
-            tg[2] = tg[3] = tg[4] = tg[5] = None
-        return (None,) * 10 + tuple(cg) + tuple(tg)
-
-
 # ------------------------------------------------------------------------------------------------
-# direct-gradient form of the fused path: the eager step an unmodified train.py issues
+# the fused Q-network call: one forward (qnet_forward), one backward (qnet_backward), two autograd forms
 # ------------------------------------------------------------------------------------------------
-# QNetFusedFn hands 57 parameter tensors to autograd and receives 57 gradients back: ~0.45 ms of Python + autograd per step
-# (pointer arrays rebuilt, 66 AccumulateGrad nodes, six allocations), which left GNN-S host-bound at 0.8 M graphs/s against
-# 2 M replayed.  Here the parameters are NOT autograd inputs: the function has ONE differentiable input (a per-model
-# anchor), the forward call uses pointer arrays cached per (model, head) -- re-validated by data_ptr every call, 57 C-level
-# calls -- and the backward writes every gradient into ONE flat buffer (``hexgnn_qnet_backward_flat``: base pointer + cached
-# offset table) and assigns the views to ``p.grad`` itself (accumulating when a gradient is already there, like
-# AccumulateGrad).  Same kernels, same bits.  Not usable with ``torch.autograd.grad(loss, parameters)`` or tensor hooks on
-# parameters (the model falls back to QNetFusedFn when it finds hooks, frozen or non-leaf parameters);
-# ``set_direct_grads(False)`` switches it off.
+# The direct-gradient form (QNetDirectFn, the eager step an unmodified train.py issues): the parameters are NOT autograd
+# inputs -- handing 57 parameter tensors to autograd and receiving 57 gradients back cost ~0.45 ms of Python + autograd per
+# step (66 AccumulateGrad nodes), which left GNN-S host-bound at 0.8 M graphs/s against 2 M replayed.  The function has ONE
+# differentiable input (a per-model anchor), the forward call uses pointer arrays cached per (model, head) -- re-validated by
+# data_ptr every call, 57 C-level calls -- and the backward writes every gradient into ONE flat buffer
+# (``hexgnn_qnet_backward_flat``: base pointer + cached offset table) and assigns the views to ``p.grad`` itself
+# (accumulating when a gradient is already there, like AccumulateGrad).  Not usable with ``torch.autograd.grad(loss,
+# parameters)`` or hooks on parameters: the model takes the autograd form (QNetFusedFn: parameters are inputs, the same flat
+# buffer's views are returned) when it finds hooks, frozen or non-leaf parameters, or after ``set_direct_grads(False)``.
+# Same kernels, same bits.
 _DIRECT_GRADS = True
 
 
@@ -1059,8 +942,8 @@ class QNetParamCache:
         self.params = params
         self.tot = tot
         self.ptrs = None
-        self.sizes = {}          # (n, b) -> buffer sizes of the fused calls (three C queries per new batch shape)
-        self.grad_ring = []      # [(flat gradient buffer, its per-parameter views, stream)]: see grad_buffer()
+        self.sizes = {}          # (layered, n, b) -> buffer sizes of the fused calls (qnet_forward)
+        self.grad_ring = []      # [(flat gradient buffer, its per-parameter views, stream, storage use count)]: grad_buffer()
         self.refresh()
 
     def grad_buffer(self, dev):
@@ -1070,13 +953,16 @@ class QNetParamCache:
         earlier backward is handed out again when NOBODY references any of its views any more (Python reference counts: the
         ring's own tuple only), which is exactly when autograd's freshly allocated gradients would be indistinguishable
         from it; a view still held anywhere (``p.grad`` not cleared, a list of gradients kept for logging) leaves that buffer
-        alone (``Tensor._use_count()`` sees the holders Python reference counts do not: ``.grad`` itself).  Not inside a HIP-graph capture (those gradients must come from the graph's pool)."""
+        alone (``Tensor._use_count()`` sees the holders Python reference counts do not: ``.grad`` itself), and so does any
+        other tensor on the buffer's storage (``p.grad.detach()``, ``.data``, ``.view(-1)``, a slice of the buffer: the
+        storage's use count is then above the one recorded when the buffer was made).  Not inside a HIP-graph capture (those
+        gradients must come from the graph's pool)."""
         if torch.cuda.is_current_stream_capturing():
             return torch.empty(self.total, dtype=torch.float32, device=dev), None
         rc = sys.getrefcount
         free_rc = _free_refcount()
         st = _stream()
-        for flat, views, owner in self.grad_ring:
+        for flat, views, owner, uses in self.grad_ring:
             if owner == st and flat.device == dev:      # (same stream only: the caching allocator's rule for a freed block)
                 for v in views:
                     # Python side: the tuple, the loop variable, the argument (measured once, _free_refcount); C++ side (a .grad, a
@@ -1084,12 +970,13 @@ class QNetParamCache:
                     if rc(v) != free_rc or v._use_count() != 1:
                         break
                 else:
-                    return flat, views
+                    if torch._C._storage_Use_Count(flat.untyped_storage()._cdata) == uses:
+                        return flat, views
         flat = torch.empty(self.total, dtype=torch.float32, device=dev)
         views = tuple(torch._C._nn.unflatten_dense_tensors(flat, self.flat_params))
         if len(self.grad_ring) >= 3:
             self.grad_ring.pop(0)
-        self.grad_ring.append((flat, views, st))
+        self.grad_ring.append((flat, views, st, torch._C._storage_Use_Count(flat.untyped_storage()._cdata)))
         return flat, views
 
     def refresh(self):
@@ -1125,21 +1012,26 @@ class QNetParamCache:
 
 
 class _QNetCall:
-    """Everything one fused forward leaves behind for its backward (plain attributes: cheaper than ctx.save_for_backward)."""
-    __slots__ = ("cache", "gs", "gptr", "dims", "x", "bufs", "math", "sink", "gp", "done", "layered", "td", "pending", "versions")
+    """Everything one fused forward leaves behind for its backward (plain attributes: cheaper than ctx.save_for_backward).
+    ``assign``: the direct form (the backward assigns ``p.grad``) rather than the autograd form (it returns the gradients);
+    ``nonleaf``: a parameter of the call is computed per forward (no staging, see qnet_backward)."""
+    __slots__ = ("cache", "gs", "gptr", "dims", "x", "bufs", "math", "sink", "gp", "done", "layered", "td", "pending", "versions",
+                 "assign", "nonleaf")
 
 
-_HP_CACHE = {}
+def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
+                 head_layers: int, mode: int, need_bwd: bool, layered: bool = False, assign: bool = True):
+    """Launch the fused forward with the cache's pointer arrays; returns (q, out_v, call) -- ``call`` feeds qnet_backward.
+    ``gptr`` may be None when ``gs`` comes from ``GraphStructure.grouped`` (it carries the pointer), and ``gs`` may be the
+    deferred grouped build's arguments (models.py): the build then runs here, with the weight pack in the same launch.
 
+    ``layered``: the same network on the layer-major kernels (graphs above 128 nodes, hidden 113..128): body + head SAGE layers
+    as ONE stack of body_layers + head_layers layers (``hexgnn_sage_stack_forward_blocks``; the head's gnn is just more SAGE
+    layers with ReLU), then the head tail (``hexgnn_head_forward``).  Against the per-module composition (body stack, head
+    stack, head tail as three autograd functions) the backward has ONE batched weight-gradient GEMM + ONE slab reduce over all
+    hidden layers instead of two of each, no stack-boundary combine, and ~1 ms less Python per step.
 
-def qnet_direct_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
-                        head_layers: int, mode: int, need_bwd: bool, layered: bool = False):
-    """Launch the fused forward with cached pointer arrays; returns (q, out_v, call) -- ``call`` feeds QNetDirectFn.
-    ``gptr`` may be None when ``gs`` comes from ``GraphStructure.grouped`` (it carries the pointer).  ``layered``: the same
-    network on the layer-major kernels (graphs above 128 nodes, hidden 113..128): body and head SAGE layers as ONE stack +
-    the head-tail kernels, see ``qnet_layered_forward``."""
-    if layered:
-        return qnet_layered_forward(cache, x, gs, gptr, b, c_in, hidden, body_layers, head_layers, mode, need_bwd)
+    ``assign``: see _QNetCall; td_step()'s loss in the forward kernel's tail is taken by the direct form only."""
     L = _lib.lib()
     dev = x.device
     n = x.shape[0]
@@ -1147,26 +1039,37 @@ def qnet_direct_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: i
     if x.dtype != torch.float32 or x.stride(1) != 1:
         x = x.float().contiguous()
     x_stride = x.stride(0) if n > 0 else c_in
-    sizes = cache.sizes.get((n, b))
+    key = (layered, n, b)
+    sizes = cache.sizes.get(key)
     if sizes is None:
+        # (hp, activations, weight pack, saved state, backward workspace): C queries once per batch shape
         hp = padded_width(hidden)
-        a_bytes = (4 * tot * n * hp + 255) & ~255
-        w_bytes = (L.hexgnn_sage_stack_pack_bytes(c_in, hidden, tot) + 255) & ~255
-        s_bytes = L.hexgnn_qnet_saved_bytes(n, b, c_in, hidden, tot)
-        ws_bytes = L.hexgnn_qnet_backward_workspace_bytes(n, b, c_in, hidden, tot)
+        if layered:
+            al = lambda v: (max(int(v), 16) + 255) & ~255
+            s_bytes = al(L.hexgnn_sage_stack_saved_bytes(n, c_in, hidden, tot))
+            sizes = (hp, al(4 * tot * n * hp), al(L.hexgnn_sage_stack_pack_bytes(c_in, hidden, tot)),
+                     s_bytes + al(L.hexgnn_head_saved_bytes(n, b, hidden)),
+                     (s_bytes, al(L.hexgnn_sage_stack_backward_workspace_bytes(n, c_in, hidden, tot)),
+                      al(L.hexgnn_head_backward_workspace_bytes(n, b, hidden))))
+        else:
+            sizes = (hp, (4 * tot * n * hp + 255) & ~255, (L.hexgnn_sage_stack_pack_bytes(c_in, hidden, tot) + 255) & ~255,
+                     max(L.hexgnn_qnet_saved_bytes(n, b, c_in, hidden, tot), 16),
+                     max(L.hexgnn_qnet_backward_workspace_bytes(n, b, c_in, hidden, tot), 16))
         if len(cache.sizes) > 64:
             cache.sizes.clear()
-        sizes = cache.sizes[(n, b)] = (hp, a_bytes, w_bytes, max(s_bytes, 16), max(ws_bytes, 16))
-    hp, a_bytes, w_bytes, s_bytes, ws_bytes = sizes
+        cache.sizes[key] = sizes
+    hp, a_bytes, w_bytes, s_bytes, bwd_bytes = sizes
     # [acts | wpack | saved] in ONE allocation (256-byte aligned parts)
     buf = torch.empty(a_bytes + w_bytes + s_bytes, dtype=torch.uint8, device=dev)
     base = buf.data_ptr()
+    wpack, saved = base + a_bytes, base + a_bytes + w_bytes
     q = torch.empty(n, dtype=torch.float32, device=dev)
     out_v = torch.empty(b, dtype=torch.float32, device=dev) if mode == 1 else None
     wl, bl, wr = cache.wl, cache.bl, cache.wr
-    if type(gs) is tuple:       # deferred grouped build (models.py): CSR + weight pack in one launch, now that wpack exists
-        if _MATH == 0:
-            gs = GraphStructure.grouped(gs[0], gs[1], gs[2], gs[3], pack=(c_in, hidden, tot, wl, bl, wr, base + a_bytes))
+    if type(gs) is tuple:       # deferred grouped build: CSR + weight pack in one launch, now that wpack exists
+        if (hidden <= 128) if layered else (_MATH == 0):        # (layered: the packed layout exists up to 128)
+            gs = GraphStructure.grouped(gs[0], gs[1], gs[2], gs[3], pack=(c_in, hidden, tot, wl, bl, wr, wpack),
+                                        device_blocks=layered)
             wl = bl = wr = None
         else:
             gs = GraphStructure.grouped(*gs)
@@ -1177,98 +1080,43 @@ def qnet_direct_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: i
     t = cache.tail
     stream = _stream()
     td = None
-    tda = getattr(_TD_STEP, "args", None)
-    if tda is not None and mode == 0 and need_bwd and b > 0 and n > 0:
-        # td_step(): the update's loss is formed in the forward kernel's tail (one selected node per graph)
-        sel, tgt, w, lfn = tda
-        if sel.numel() == b:
+    if layered:
+        blk = gs.blocks
+        _lib.check(L.hexgnn_sage_stack_forward_blocks(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl,
+                                                      bl, wr, wpack, base, saved, int(need_bwd), 0,
+                                                      blk[0].data_ptr() if blk else None, blk[1] if blk else 0, stream),
+                   "hexgnn_sage_stack_forward_blocks")
+        _lib.check(L.hexgnn_head_forward(n, b, hidden, mode, gp[5], base + 4 * (tot - 1) * n * hp, t[0], t[1], t[2], t[3],
+                                         t[4], t[5], q.data_ptr(), out_v.data_ptr() if out_v is not None else None,
+                                         saved + bwd_bytes[0], stream), "hexgnn_head_forward")
+    else:
+        tda = getattr(_TD_STEP, "args", None) if assign else None
+        if tda is not None and mode == 0 and need_bwd and b > 0 and n > 0 and tda[0].numel() == b:
+            # td_step(): the update's loss is formed in the forward kernel's tail (one selected node per graph)
+            sel, tgt, w, lfn = tda
             # one buffer: dq [n] | td [b] | loss terms [b] | loss [1]
             tb = torch.empty(n + 2 * b + 1, dtype=torch.float32, device=dev)
             tp = tb.data_ptr()
             _lib.check(L.hexgnn_qnet_forward_td(
                 n, b, c_in, hidden, tot, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
-                t[0], t[1], t[2], t[3], t[4], t[5], base + a_bytes, base, base + a_bytes + w_bytes, _MATH, q.data_ptr(), gp[6],
+                t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, _MATH, q.data_ptr(), gp[6],
                 sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
                 tp + 4 * (n + b), stream), "hexgnn_qnet_forward_td")
             td = (tb, n, b)
-    if td is None:
-        _lib.check(L.hexgnn_qnet_forward(
-            n, b, c_in, hidden, tot, mode, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
-            t[0], t[1], t[2], t[3], t[4], t[5], base + a_bytes, base, base + a_bytes + w_bytes, int(need_bwd), body_layers - 1,
-            _MATH, q.data_ptr(), out_v.data_ptr() if out_v is not None else None, gp[6], stream), "hexgnn_qnet_forward")
+        else:
+            _lib.check(L.hexgnn_qnet_forward(
+                n, b, c_in, hidden, tot, mode, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
+                t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, int(need_bwd), body_layers - 1,
+                _MATH, q.data_ptr(), out_v.data_ptr() if out_v is not None else None, gp[6], stream), "hexgnn_qnet_forward")
     call = _QNetCall()
     call.cache, call.gs, call.gptr, call.x = cache, gs, gptr, x
-    call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, ws_bytes)
-    call.bufs, call.math, call.gp = buf, _MATH, gp
-    call.sink = None
-    call.done = False
-    call.layered = False
-    call.td = td
+    # (bwd_bytes: the fused backward's workspace bytes; layered: (stack saved, stack workspace, head workspace) bytes)
+    call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, bwd_bytes)
+    call.bufs, call.math, call.gp = buf, 0 if layered else _MATH, gp
+    call.sink, call.done, call.layered, call.td, call.pending = None, False, layered, td, None
+    call.assign, call.nonleaf = assign, False
     # the backward reads the head tail's weights LIVE (the SAGE layers' from the pack made by this forward): an in-place update
     # between the two would mix old and new weights without autograd's saved-tensor version check to notice it
-    call.versions = tuple(p._version for p in cache.params[-6:]) if need_bwd else None
-    return q, out_v, call
-
-
-def qnet_layered_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
-                         head_layers: int, mode: int, need_bwd: bool):
-    """DuellingTwoHeaded.forward on the layer-major kernels with the direct-gradient bookkeeping: body + head SAGE layers run
-    as ONE stack of body_layers + head_layers layers (``hexgnn_sage_stack_forward``; the head's gnn is just more SAGE layers
-    with ReLU), then the head tail (``hexgnn_head_forward``).  Against the per-module composition (body stack, head stack,
-    head tail as three autograd functions) the backward has ONE batched weight-gradient GEMM + ONE slab reduce over all 16
-    hidden layers instead of two of each, no stack-boundary combine, and ~1 ms less Python per step."""
-    L = _lib.lib()
-    dev = x.device
-    n = x.shape[0]
-    tot = body_layers + head_layers
-    if x.dtype != torch.float32 or x.stride(1) != 1:
-        x = x.float().contiguous()
-    x_stride = x.stride(0) if n > 0 else c_in
-    sizes = cache.sizes.get(("L", n, b))
-    if sizes is None:
-        hp = padded_width(hidden)
-        al = lambda v: (max(int(v), 16) + 255) & ~255
-        sizes = cache.sizes[("L", n, b)] = (
-            hp, al(4 * tot * n * hp), al(L.hexgnn_sage_stack_pack_bytes(c_in, hidden, tot)),
-            al(L.hexgnn_sage_stack_saved_bytes(n, c_in, hidden, tot)), al(L.hexgnn_head_saved_bytes(n, b, hidden)),
-            al(L.hexgnn_sage_stack_backward_workspace_bytes(n, c_in, hidden, tot)),
-            al(L.hexgnn_head_backward_workspace_bytes(n, b, hidden)))
-    hp, a_bytes, w_bytes, s_bytes, hs_bytes, ws_bytes, hws_bytes = sizes
-    buf = torch.empty(a_bytes + w_bytes + s_bytes + hs_bytes, dtype=torch.uint8, device=dev)
-    base = buf.data_ptr()
-    q = torch.empty(n, dtype=torch.float32, device=dev)
-    out_v = torch.empty(b, dtype=torch.float32, device=dev) if mode == 1 else None
-    wl, bl, wr = cache.wl, cache.bl, cache.wr
-    if type(gs) is tuple:       # deferred grouped build: CSR + weight pack in one launch (hidden <= 128: the packed layout)
-        if hidden <= 128:
-            gs = GraphStructure.grouped(gs[0], gs[1], gs[2], gs[3], pack=(c_in, hidden, tot, wl, bl, wr, base + a_bytes),
-                                        device_blocks=True)
-            wl = bl = wr = None
-        else:
-            gs = GraphStructure.grouped(*gs)
-    gp = gs._ptrs
-    if gp is None:
-        gp = (gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.rowptr_t.data_ptr(), gs.col_t.data_ptr(), gs.invdeg.data_ptr(),
-              gptr.data_ptr(), gs.status.data_ptr())
-    t = cache.tail
-    stream = _stream()
-    blk = gs.blocks
-    _lib.check(L.hexgnn_sage_stack_forward_blocks(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl,
-                                                  wr, base + a_bytes, base, base + a_bytes + w_bytes, int(need_bwd), 0,
-                                                  blk[0].data_ptr() if blk else None, blk[1] if blk else 0, stream),
-               "hexgnn_sage_stack_forward_blocks")
-    h_top = base + 4 * (tot - 1) * n * hp
-    _lib.check(L.hexgnn_head_forward(n, b, hidden, mode, gp[5], h_top, t[0], t[1], t[2], t[3], t[4], t[5], q.data_ptr(),
-                                     out_v.data_ptr() if out_v is not None else None, base + a_bytes + w_bytes + s_bytes,
-                                     stream), "hexgnn_head_forward")
-    call = _QNetCall()
-    call.cache, call.gs, call.gptr, call.x = cache, gs, gptr, x
-    call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, (s_bytes, ws_bytes, hws_bytes))
-    call.bufs, call.math, call.gp = buf, 0, gp
-    call.sink = None
-    call.done = False
-    call.layered = True
-    call.td = None
     call.versions = tuple(p._version for p in cache.params[-6:]) if need_bwd else None
     return q, out_v, call
 
@@ -1287,10 +1135,38 @@ def _assign_flat_grads(cache: QNetParamCache, flat: torch.Tensor, mode: int, vie
         p.grad = v if g is None else g + v
 
 
-def qnet_layered_backward(call: "_QNetCall", dq, d_v=None) -> None:
+def qnet_embeds(call: _QNetCall) -> torch.Tensor:
+    """final_conv_acts of a fused forward: the body output as a [n, hidden] view of the activation slab."""
+    n, b, c_in, hidden, tot, body_layers, mode, hp = call.dims[:8]
+    acts = call.bufs[:4 * tot * n * hp].view(torch.float32).view(tot, n, hp)
+    return acts[body_layers - 1][:, :hidden]
+
+
+def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
+    """The fused backward of a fused forward: every parameter gradient into ONE flat buffer (the layout of
+    ``model.parameters()``, so that GradSync can all-reduce it in place).  The direct form (``call.assign``) assigns the views
+    to ``p.grad`` (accumulated when a gradient is already there) and returns None; called by autograd (QNetDirectFn.backward,
+    on the engine's device thread) or straight from ``ops.backward(loss)`` on the caller's thread.  The autograd form returns
+    the views in the call's parameter order (None for the value head in mode 2), from a fresh buffer every time.
+
+    Staging (fused kernels only): with a stage hook installed (``set_grad_stage_hook``) or ``defer_lower``, the first stage
+    runs the data chain, the small reduces and the weight gradients of the upper half of the hidden layers -- the TAIL of the
+    flat buffer is then final.  The hook gets that segment (all-reduce on the collective's own stream) while the lower half's
+    weight-gradient GEMM is enqueued behind it, then the head of the buffer; ``defer_lower`` leaves the lower half to
+    ``finish_backward(call)`` instead (a step captured as two HIP graphs split there lets the tail's all-reduce travel while
+    the second graph computes: graphs.GraphedSplitStep).  Not for non-leaf parameters (``--noisy_dqn=True``: d_sigma = d_w *
+    eps with per-rank noise is not the average of the ranks' d_sigma if d_w is averaged first, and the mu / sigma gradients
+    live outside the flat buffer; GradSync reduces the finished .grad tensors through its bucket)."""
+    call.pending = None
+    if call.versions is not None and call.versions != tuple(p._version for p in call.cache.params[-6:]):
+        raise RuntimeError("a head parameter of the model was modified in place between this forward and its backward (the "
+                           "fused backward reads the head tail's weights live); run the backward before optimizer.step()")
+    if call.done:
+        raise RuntimeError("this forward's backward already ran through ops.backward(loss) (its graph is spent, as after "
+                           "loss.backward() without retain_graph)")
     L = _lib.lib()
     cache = call.cache
-    n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, (s_bytes, ws_bytes, hws_bytes) = call.dims
+    n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, bwd_bytes = call.dims
     dev = call.x.device
     if mode == 1:
         d_v = torch.zeros(b, dtype=torch.float32, device=dev) if d_v is None else d_v.float().contiguous()
@@ -1298,56 +1174,90 @@ def qnet_layered_backward(call: "_QNetCall", dq, d_v=None) -> None:
         d_v = None
     dq = torch.zeros(n, dtype=torch.float32, device=dev) if dq is None else \
         (dq if (dq.dtype == torch.float32 and dq.is_contiguous()) else dq.float().contiguous())
-    flat, gviews = cache.grad_buffer(dev)
-    ws = torch.empty(ws_bytes + hws_bytes, dtype=torch.uint8, device=dev)
-    # the head tail writes dh * [h > 0] = G of the top layer straight into its slab of the stack's workspace
-    # (HEXGNN_HEAD_MASK_DH / HEXGNN_SAGE_DY_IN_PLACE: no masked copy in between)
-    dh_ptr = ws.data_ptr() + 4 * (tot - 1) * n * hp
-    d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if (call.sink is not None and body_layers < tot) else None
-    base, gp, t = call.bufs.data_ptr(), call.gp, cache.tail
-    fb = flat.data_ptr()
-    offs = cache.offsets
-    tp = [fb + 4 * offs[3 * tot + k] for k in range(6)]          # d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b
-    vh = mode != 2
-    stream = _stream()
-    h_top = base + 4 * (tot - 1) * n * hp
-    _lib.check(L.hexgnn_head_backward(n, b, hidden, mode | 8, gp[5], h_top, t[0], t[2], t[4], base + a_bytes + w_bytes + s_bytes,
-                                      dq.data_ptr(), d_v.data_ptr() if d_v is not None else None, dh_ptr, tp[0], tp[1],
-                                      tp[2] if vh else None, tp[3] if vh else None, tp[4] if vh else None,
-                                      tp[5] if vh else None, ws.data_ptr() + ws_bytes, hws_bytes, stream),
-               "hexgnn_head_backward")
-    vp = C.c_void_p * tot
-    d_wl = vp(*[fb + 4 * offs[3 * l] for l in range(tot)])
-    d_bl = vp(*[fb + 4 * offs[3 * l + 1] for l in range(tot)])
-    d_wr = vp(*[fb + 4 * offs[3 * l + 2] for l in range(tot)])
-    blk = call.gs.blocks
-    _lib.check(L.hexgnn_sage_stack_backward_blocks(
-        n, c_in, hidden, tot, gp[0], gp[1], gp[2], gp[3], gp[4], call.x.data_ptr(), x_stride, base, base + a_bytes + w_bytes,
-        base + a_bytes, dh_ptr, None, d_wl, d_bl, d_wr, ws.data_ptr(), ws_bytes, 2,
-        body_layers - 1 if d_emb is not None else -1, d_emb.data_ptr() if d_emb is not None else None,
-        blk[0].data_ptr() if blk else None, blk[1] if blk else 0, stream), "hexgnn_sage_stack_backward_blocks")
-    _assign_flat_grads(cache, flat, mode, gviews)
-    del gviews
-    if call.sink is not None and d_emb is not None:
+    if call.assign:
+        flat, gviews = cache.grad_buffer(dev)
+    else:
+        flat, gviews = torch.empty(cache.total, dtype=torch.float32, device=dev), None
+    base, gp, t, fb = call.bufs.data_ptr(), call.gp, cache.tail, flat.data_ptr()
+    if call.layered:
+        s_bytes, ws_bytes, hws_bytes = bwd_bytes
+        ws = torch.empty(ws_bytes + hws_bytes, dtype=torch.uint8, device=dev)
+        # the head tail writes dh * [h > 0] = G of the top layer straight into its slab of the stack's workspace
+        # (HEXGNN_HEAD_MASK_DH / HEXGNN_SAGE_DY_IN_PLACE: no masked copy in between)
+        dh_ptr = ws.data_ptr() + 4 * (tot - 1) * n * hp
+        d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if (call.sink is not None and body_layers < tot) else None
+        offs = cache.offsets
+        tp = [fb + 4 * offs[3 * tot + k] for k in range(6)]          # d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b
+        vh = mode != 2
+        stream = _stream()
+        h_top = base + 4 * (tot - 1) * n * hp
+        _lib.check(L.hexgnn_head_backward(n, b, hidden, mode | 8, gp[5], h_top, t[0], t[2], t[4],
+                                          base + a_bytes + w_bytes + s_bytes, dq.data_ptr(),
+                                          d_v.data_ptr() if d_v is not None else None, dh_ptr, tp[0], tp[1],
+                                          tp[2] if vh else None, tp[3] if vh else None, tp[4] if vh else None,
+                                          tp[5] if vh else None, ws.data_ptr() + ws_bytes, hws_bytes, stream),
+                   "hexgnn_head_backward")
+        vp = C.c_void_p * tot
+        d_wl = vp(*[fb + 4 * offs[3 * l] for l in range(tot)])
+        d_bl = vp(*[fb + 4 * offs[3 * l + 1] for l in range(tot)])
+        d_wr = vp(*[fb + 4 * offs[3 * l + 2] for l in range(tot)])
+        blk = call.gs.blocks
+        _lib.check(L.hexgnn_sage_stack_backward_blocks(
+            n, c_in, hidden, tot, gp[0], gp[1], gp[2], gp[3], gp[4], call.x.data_ptr(), x_stride, base,
+            base + a_bytes + w_bytes, base + a_bytes, dh_ptr, None, d_wl, d_bl, d_wr, ws.data_ptr(), ws_bytes, 2,
+            body_layers - 1 if d_emb is not None else -1, d_emb.data_ptr() if d_emb is not None else None,
+            blk[0].data_ptr() if blk else None, blk[1] if blk else 0, stream), "hexgnn_sage_stack_backward_blocks")
+    else:
+        ws_bytes = bwd_bytes
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if call.sink is not None else None
+        common = (n, b, c_in, hidden, tot, body_layers, mode, call.math, gp[5], gp[2], gp[3], gp[4], call.x.data_ptr(),
+                  x_stride, base, base + a_bytes + w_bytes, base + a_bytes, t[0], t[2], t[4], dq.data_ptr(),
+                  d_v.data_ptr() if d_v is not None else None, d_emb.data_ptr() if d_emb is not None else None,
+                  fb, cache.offsets, ws.data_ptr(), ws_bytes, gp[6])
+        hook = _GRAD_STAGE_HOOK
+        split = tot >= 3 and mode != 2 and not call.nonleaf and (defer_lower or hook is not None)
+        mid = 1 + tot // 2 if split else 1
+        td = call.td
+        if td is not None and dq.data_ptr() == td[0].data_ptr():
+            # td_step(): d loss / d Q came from the forward launch; the reduce launch also writes the loss (mean of the graphs' terms)
+            tb, tn, tbb = td
+            tp = tb.data_ptr()
+            ctd = common[:6] + common[7:21] + common[22:]          # (no mode, no d_out_v: mode 0)
+            _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
+                                                      _stream()), "hexgnn_qnet_backward_flat_td")
+        else:
+            _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, mid, tot, _stream()), "hexgnn_qnet_backward_flat")
+        if split and defer_lower:
+            call.pending = (common, mid, flat, cache.cut, ws, d_emb)
+        elif split:
+            hook(flat, cache.cut, cache.total)
+            _lib.check(L.hexgnn_qnet_backward_flat(*common, 4, 1, mid, _stream()), "hexgnn_qnet_backward_flat")
+            hook(flat, 0, cache.cut)
+    grads = None
+    if call.assign:
+        _assign_flat_grads(cache, flat, mode, gviews)
+        del gviews
+    else:
+        # flat order -> the call's order: the head tail's (lin_w, lin_b, v0_w, v0_b, v1_w, v1_b) sit in the flat buffer as
+        # (v0_w, v0_b, v1_w, v1_b, lin_w, lin_b)
+        g = torch._C._nn.unflatten_dense_tensors(flat, cache.flat_params)
+        nconv = 3 * tot
+        grads = tuple(g[:nconv]) + tuple(g[-2:]) + ((None,) * 4 if mode == 2 else tuple(g[nconv:nconv + 4]))
+    if d_emb is not None:
         call.sink(d_emb[:, :hidden])
-
-
-def qnet_embeds(call: _QNetCall) -> torch.Tensor:
-    """final_conv_acts of a direct forward: the body output as a [n, hidden] view of the activation slab."""
-    n, b, c_in, hidden, tot, body_layers, mode, hp = call.dims[:8]
-    acts = call.bufs[:4 * tot * n * hp].view(torch.float32).view(tot, n, hp)
-    return acts[body_layers - 1][:, :hidden]
+    return grads
 
 
 class QNetDirectFn(torch.autograd.Function):
-    """Autograd node of a direct forward: ONE differentiable input (the per-model anchor, whose gradient is never produced);
-    ``fargs`` = the arguments of ``qnet_direct_forward``, ``holder`` = a list that receives the call record.  The backward
-    runs the fused backward kernels and assigns the parameter gradients (see the section comment)."""
+    """Autograd node of the direct form: ONE differentiable input (the per-model anchor, whose gradient is never produced);
+    ``fargs`` = the arguments of ``qnet_forward``, ``holder`` = a list that receives the call record.  The backward runs the
+    fused backward kernels and assigns the parameter gradients (see the section comment)."""
 
     @staticmethod
     def forward(ctx, anchor, holder, fargs):
         ctx.set_materialize_grads(False)
-        q, out_v, call = qnet_direct_forward(*fargs)
+        q, out_v, call = qnet_forward(*fargs)
         ctx.call = call
         holder.append(call)
         if out_v is None:
@@ -1356,84 +1266,42 @@ class QNetDirectFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dq, d_v=None):
-        qnet_direct_backward(ctx.call, dq, d_v)
+        qnet_backward(ctx.call, dq, d_v)
         return None, None, None
 
 
-def qnet_direct_backward(call: "_QNetCall", dq, d_v=None, defer_lower: bool = False) -> None:
-    """The fused backward of a direct forward: every parameter gradient into ONE flat buffer, views assigned to ``p.grad``
-    (accumulated when a gradient is already there).  Called by autograd (QNetDirectFn.backward, on the engine's device
-    thread) or straight from ``ops.backward(loss)`` on the caller's thread.
+class QNetFusedFn(torch.autograd.Function):
+    """The autograd form: DuellingTwoHeaded.forward (GN0/models.py:537-584) on the fused kernels with the parameters as
+    autograd inputs (frozen or hooked parameters, post-accumulate hooks, ``--noisy_dqn`` weights formed per forward,
+    ``torch.autograd.grad``, ``set_direct_grads(False)``).  ``cache`` = the head's QNetParamCache, or None when the weights
+    are formed per forward (a cache is then built for the call).  Outputs: mode 0 -> (Q, embeds); 1 -> (V, A-mean(A),
+    embeds); 2 -> (2tanh(adv), embeds).  ``embeds`` (final_conv_acts) is returned non-differentiable; its gradient is handed
+    to ``grad_sink(d_embeds)`` during backward (final_conv_grads / Grad-CAM)."""
 
-    ``defer_lower``: only the first stage of the staged backward runs (data chain, small reduces, weight gradients of the upper
-    half of the hidden layers: the TAIL of the flat buffer is final); ``finish_backward(call)`` runs the rest.  A step captured
-    as two HIP graphs split there lets the tail's all-reduce travel while the second graph computes (graphs.GraphedSplitStep)."""
-    call.pending = None
-    if call.versions is not None and call.versions != tuple(p._version for p in call.cache.params[-6:]):
-        raise RuntimeError("a head parameter of the model was modified in place between this forward and its backward (the "
-                           "fused backward reads the head tail's weights live); run the backward before optimizer.step()")
-    if call.done:
-        raise RuntimeError("this forward's backward already ran through ops.backward(loss) (its graph is spent, as after "
-                           "loss.backward() without retain_graph)")
-    if call.layered:
-        return qnet_layered_backward(call, dq, d_v)
-    L = _lib.lib()
-    cache = call.cache
-    n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, ws_bytes = call.dims
-    dev = call.x.device
-    if mode == 1:
-        d_v = torch.zeros(b, dtype=torch.float32, device=dev) if d_v is None else d_v.float().contiguous()
-    else:
-        d_v = None
-    dq = torch.zeros(n, dtype=torch.float32, device=dev) if dq is None else \
-        (dq if (dq.dtype == torch.float32 and dq.is_contiguous()) else dq.float().contiguous())
-    flat, gviews = cache.grad_buffer(dev)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if call.sink is not None else None
-    base = call.bufs.data_ptr()
-    gp, t = call.gp, cache.tail
-    common = (n, b, c_in, hidden, tot, body_layers, mode, call.math, gp[5], gp[2], gp[3], gp[4], call.x.data_ptr(),
-              x_stride, base, base + a_bytes + w_bytes, base + a_bytes, t[0], t[2], t[4], dq.data_ptr(),
-              d_v.data_ptr() if d_v is not None else None, d_emb.data_ptr() if d_emb is not None else None,
-              flat.data_ptr(), cache.offsets, ws.data_ptr(), ws_bytes, gp[6])
-    hook = _GRAD_STAGE_HOOK
-    td = call.td
-    if td is not None and dq.data_ptr() == td[0].data_ptr():
-        # td_step(): d loss / d Q came from the forward launch; the reduce launch also writes the loss (mean of the graphs' terms)
-        tb, tn, tbb = td
-        tp = tb.data_ptr()
-        ctd = common[:6] + common[7:21] + common[22:]          # (no mode, no d_out_v: mode 0)
-        if defer_lower and tot >= 3:
-            mid = 1 + tot // 2
-            _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb), _stream()),
-                       "hexgnn_qnet_backward_flat_td")
-            call.pending = (common, mid, flat, cache.cut, ws, d_emb)
-        elif hook is None or tot < 3:
-            _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, 1, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb), _stream()),
-                       "hexgnn_qnet_backward_flat_td")
-        else:
-            mid, cut = 1 + tot // 2, cache.cut
-            _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb), _stream()),
-                       "hexgnn_qnet_backward_flat_td")
-            hook(flat, cut, cache.total)
-            _lib.check(L.hexgnn_qnet_backward_flat(*common, 4, 1, mid, _stream()), "hexgnn_qnet_backward_flat")
-            hook(flat, 0, cut)
-    elif defer_lower and tot >= 3 and mode != 2:
-        mid = 1 + tot // 2
-        _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, mid, tot, _stream()), "hexgnn_qnet_backward_flat")
-        call.pending = (common, mid, flat, cache.cut, ws, d_emb)
-    elif hook is None or tot < 3 or mode == 2:
-        _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, 1, tot, _stream()), "hexgnn_qnet_backward_flat")
-    else:
-        mid, cut = 1 + tot // 2, cache.cut
-        _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, mid, tot, _stream()), "hexgnn_qnet_backward_flat")
-        hook(flat, cut, cache.total)
-        _lib.check(L.hexgnn_qnet_backward_flat(*common, 4, 1, mid, _stream()), "hexgnn_qnet_backward_flat")
-        hook(flat, 0, cut)
-    _assign_flat_grads(cache, flat, mode, gviews)
-    del gviews
-    if call.sink is not None:
-        call.sink(d_emb[:, :hidden])
+    @staticmethod
+    def forward(ctx, cache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int, head_layers: int,
+                mode: int, grad_sink, *params):
+        ctx.set_materialize_grads(False)      # unused outputs (embeds, V) arrive as None instead of freshly zeroed tensors
+        # a parameter that is computed per forward (FactorizedNoisyLinear's mu + sigma * eps) is no leaf: its gradient is
+        # an intermediate that autograd still has to carry to mu / sigma, so it must not be all-reduced in place
+        nonleaf = any(p.grad_fn is not None for p in params)
+        conv = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous() for p in params]
+        if cache is None or any(p is not c for p, c in zip(conv, cache.params)):
+            cache = QNetParamCache(conv, body_layers + head_layers)
+        q, out_v, call = qnet_forward(cache, x, gs, gptr, b, c_in, hidden, body_layers, head_layers, mode,
+                                      any(ctx.needs_input_grad), assign=False)
+        call.nonleaf, call.sink = nonleaf, grad_sink
+        ctx.call = call
+        embeds = qnet_embeds(call)
+        ctx.mark_non_differentiable(embeds)
+        if mode == 1:
+            return out_v, q, embeds
+        return q, embeds
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        dq, d_v = (gouts[1], gouts[0]) if ctx.call.dims[6] == 1 else (gouts[0], None)
+        return (None,) * 11 + qnet_backward(ctx.call, dq, d_v)
 
 
 def finish_backward(call: "_QNetCall"):
@@ -1455,6 +1323,20 @@ _TD_TLS = threading.local()
 _ONES = {}
 
 
+def _td_args(sel, target, weights, dev):
+    """sel / target / weights of a TD loss as contiguous tensors on ``dev`` (int64, fp32, fp32) of one length.  (.to() costs
+    ~2 us even when nothing changes: the usual case -- device tensors of the right type -- skips it.)"""
+    if sel.dtype != torch.long or sel.device != dev or not sel.is_contiguous():
+        sel = sel.to(device=dev, dtype=torch.long).contiguous()
+    if target.dtype != torch.float32 or target.device != dev or not target.is_contiguous():
+        target = target.to(device=dev, dtype=torch.float32).contiguous()
+    if weights is not None and (weights.dtype != torch.float32 or weights.device != dev or not weights.is_contiguous()):
+        weights = weights.to(device=dev, dtype=torch.float32).contiguous()
+    if target.numel() != sel.numel() or (weights is not None and weights.numel() != sel.numel()):
+        raise ValueError("sel / target / weights must have the same length")
+    return sel, target, weights
+
+
 class TdLossFn(torch.autograd.Function):
     """``loss_fn(Q[sel], target)`` of the DQN update: mean of importance-weighted squared ("mse") or Huber errors over the
     selected nodes.  When Q needs a gradient the forward is ONE launch that also produces ``d loss / d Q``
@@ -1470,18 +1352,8 @@ class TdLossFn(torch.autograd.Function):
         qf = q if q.dim() == 1 else q.reshape(-1)
         if qf.dtype != torch.float32 or not qf.is_contiguous():
             qf = qf.float().contiguous()
-        # (.to() costs ~2 us even when nothing changes: the usual case -- device tensors of the right type -- skips it)
-        if sel.dtype != torch.long or sel.device != dev or not sel.is_contiguous():
-            sel = sel.to(device=dev, dtype=torch.long).contiguous()
-        tgt = target
-        if tgt.dtype != torch.float32 or tgt.device != dev or not tgt.is_contiguous():
-            tgt = tgt.to(device=dev, dtype=torch.float32).contiguous()
-        w = weights
-        if w is not None and (w.dtype != torch.float32 or w.device != dev or not w.is_contiguous()):
-            w = w.to(device=dev, dtype=torch.float32).contiguous()
+        sel, tgt, w = _td_args(sel, target, weights, dev)
         k, n = sel.numel(), qf.numel()
-        if tgt.numel() != k or (w is not None and w.numel() != k):
-            raise ValueError("sel / target / weights must have the same length")
         loss = torch.empty((), dtype=torch.float32, device=dev)
         td = torch.empty(k, dtype=torch.float32, device=dev)
         dq = None
@@ -1555,7 +1427,7 @@ def backward(loss: torch.Tensor) -> None:
     direct = loss.__dict__.pop("_hex_direct", None) if _GRAD_STAGE_HOOK is None else None
     if direct is not None and not direct[0].done:
         call, dq = direct
-        qnet_direct_backward(call, dq, None)
+        qnet_backward(call, dq, None)
         call.done = True            # like autograd without retain_graph: a second backward through this forward is an error
         return
     key = (loss.device.type, loss.device.index)
@@ -1590,19 +1462,11 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
     selections per graph, graphs above 128 nodes, frozen parameters, ``--noisy_dqn``) runs the three calls.
 
     ``defer_lower=True`` returns ``(loss, td, q, call)`` with only the first stage of the staged backward issued (see
-    ``qnet_direct_backward``); ``finish_backward(call)`` issues the rest (a no-op returning (None, 0) where the step did not
+    ``qnet_backward``); ``finish_backward(call)`` issues the rest (a no-op returning (None, 0) where the step did not
     take the fused path and ran whole)."""
     if not x.is_cuda:
         raise _lib.HexGnnError("td_step runs only on the MI355X HIP path (no CPU fallback)")
-    dev = x.device
-    if sel.dtype != torch.long or sel.device != dev or not sel.is_contiguous():
-        sel = sel.to(device=dev, dtype=torch.long).contiguous()
-    if target.dtype != torch.float32 or target.device != dev or not target.is_contiguous():
-        target = target.to(device=dev, dtype=torch.float32).contiguous()
-    if weights is not None and (weights.dtype != torch.float32 or weights.device != dev or not weights.is_contiguous()):
-        weights = weights.to(device=dev, dtype=torch.float32).contiguous()
-    if target.numel() != sel.numel() or (weights is not None and weights.numel() != sel.numel()):
-        raise ValueError("sel / target / weights must have the same length")
+    sel, target, weights = _td_args(sel, target, weights, x.device)
     lfn = {"mse": 0, "huber": 1}[loss_fn]
     _TD_STEP.args = (sel, target, weights, lfn)
     try:
@@ -1615,9 +1479,9 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
     if td is None:
         loss, tde = td_loss(q, sel, target, weights, loss_fn)
         direct = getattr(loss, "_hex_direct", None)
-        if defer_lower and direct is not None and _GRAD_STAGE_HOOK is None and not direct[0].layered:
+        if defer_lower and direct is not None and _GRAD_STAGE_HOOK is None:
             loss.__dict__.pop("_hex_direct", None)
-            qnet_direct_backward(direct[0], direct[1], None, defer_lower=True)
+            qnet_backward(direct[0], direct[1], None, defer_lower=True)
             direct[0].done = True
             return loss, tde, q, direct[0]
         backward(loss)
@@ -1628,7 +1492,7 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
             return loss, tde, q, call
         return loss, tde, q
     tb, n, b = td
-    qnet_direct_backward(call, tb[:n], None, defer_lower=defer_lower and _GRAD_STAGE_HOOK is None)
+    qnet_backward(call, tb[:n], None, defer_lower=defer_lower and _GRAD_STAGE_HOOK is None)
     call.done = True
     if defer_lower:
         return tb[n + 2 * b], tb[n:n + b], q, call

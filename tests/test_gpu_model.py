@@ -577,7 +577,8 @@ def test_direct_gradient_form_matches_the_autograd_form():
     """The eager fast path (ops.QNetDirectFn: parameters are not autograd inputs, the backward assigns p.grad itself) against
     the autograd form (ops.QNetFusedFn: 57 inputs / 57 returned gradients): Q and every gradient bit-identical, for all three
     output modes; gradients ACCUMULATE when the caller did not clear them (a second backward, retain_graph); a frozen
-    parameter or a tensor hook on a parameter sends the model back to the autograd form."""
+    parameter or a tensor hook on a parameter sends the model back to the autograd form; a head-tail weight changed in place
+    before the backward is an error on both forms."""
     from gnn_hex_amd import ops
     if not ops._FUSED_ENABLED:
         pytest.skip("a test of the fused path")
@@ -661,6 +662,19 @@ def test_direct_gradient_form_matches_the_autograd_form():
     with torch.no_grad():
         qn = hip(xd, eid, bv, pt)
     assert torch.equal(qn, q.detach()) and not qn.requires_grad
+    # a head-tail weight edited in place between forward and backward (as optimizer.step() does) raises on the autograd form
+    # as well: its backward reads the head tail's weights live, like the direct form's
+    ops.set_direct_grads(False)
+    try:
+        q = hip(xd, eid, bv, pt)
+        assert not isinstance(hip.__dict__.get("_fca"), ops._QNetCall)
+        loss = torch.nn.functional.mse_loss(q[sd], td)
+        with torch.no_grad():
+            hip.maker_head.linear.weight.add_(1e-3)
+        with pytest.raises(RuntimeError, match="modified in place"):
+            loss.backward()
+    finally:
+        ops.set_direct_grads(True)
 
 
 def test_randomised_configurations():

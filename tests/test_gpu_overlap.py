@@ -39,35 +39,50 @@ def test_staged_backward_matches_single_call(math, layers, hidden, sizes):
             calls.append((flat.data_ptr(), flat.numel(), lo, hi, ev))
 
         ops.set_grad_stage_hook(hook)
-        q1, g1 = _step(hip, data)
-        torch.cuda.synchronize()
-        # two segments, tail first, tiling the flat buffer of this step's gradients
-        assert len(calls) == 2
-        (p0, n0, lo0, hi0, _), (p1, n1, lo1, hi1, _) = calls
-        assert p0 == p1 and n0 == n1 and hi0 == n0 and lo1 == 0 and hi1 == lo0 and 0 < lo0 < n0
-        active = [p for p in hip.parameters() if p.grad is not None]
-        flat = GradSync._adopt_flat(active)
-        assert flat is not None and flat.numel() == n0 and flat.data_ptr() == p0
-        # the boundary is a layer boundary: the head segment holds the first 1 + tot // 2 conv layers
-        tot = layers + 2
-        mid = 1 + tot // 2
-        convs = list(hip.gnn.convs) + list(hip.breaker_head.gnn.convs)
-        head_elems = sum(c.lin_l.weight.numel() + c.lin_l.bias.numel() + c.lin_r.weight.numel() for c in convs[:mid])
-        assert lo0 == head_elems
-        assert torch.equal(q0, q1)
-        for k in g0:
-            assert (g0[k] is None) == (g1[k] is None), k
-            if g0[k] is not None:
-                scale = max(1.0, g0[k].abs().max().item())
-                assert (g0[k] - g1[k]).abs().max().item() < 2e-6 * scale, k
-        # and against the oracle at the usual bar
         ref.zero_grad(set_to_none=True)
         q_ref = ref(x, ei, batch, ptr)
         torch.nn.functional.mse_loss(q_ref[sel], tgt).backward()
-        for k, p in ref.named_parameters():
-            if p.grad is not None:
-                assert (g1[k].cpu() - p.grad).abs().max().item() < 1e-4 * max(1.0, p.grad.abs().max().item()), k
+        staged = {}
+        # the direct form, then the autograd form (parameters as autograd inputs, gradients returned): the same staging
+        for direct in (True, False):
+            ops.set_direct_grads(direct)
+            calls.clear()
+            q1, g1 = _step(hip, data)
+            torch.cuda.synchronize()
+            assert isinstance(hip.__dict__.get("_fca"), ops._QNetCall) == direct
+            # two segments, tail first, tiling the flat buffer of this step's gradients
+            assert len(calls) == 2
+            (p0, n0, lo0, hi0, _), (p1, n1, lo1, hi1, _) = calls
+            assert p0 == p1 and n0 == n1 and hi0 == n0 and lo1 == 0 and hi1 == lo0 and 0 < lo0 < n0
+            active = [p for p in hip.parameters() if p.grad is not None]
+            flat = GradSync._adopt_flat(active)
+            assert flat is not None and flat.numel() == n0 and flat.data_ptr() == p0
+            # the boundary is a layer boundary: the head segment holds the first 1 + tot // 2 conv layers
+            tot = layers + 2
+            mid = 1 + tot // 2
+            convs = list(hip.gnn.convs) + list(hip.breaker_head.gnn.convs)
+            head_elems = sum(c.lin_l.weight.numel() + c.lin_l.bias.numel() + c.lin_r.weight.numel() for c in convs[:mid])
+            assert lo0 == head_elems
+            assert torch.equal(q0, q1)
+            for k in g0:
+                assert (g0[k] is None) == (g1[k] is None), k
+                if g0[k] is not None:
+                    scale = max(1.0, g0[k].abs().max().item())
+                    assert (g0[k] - g1[k]).abs().max().item() < 2e-6 * scale, k
+            # and against the oracle at the usual bar
+            for k, p in ref.named_parameters():
+                if p.grad is not None:
+                    assert (g1[k].cpu() - p.grad).abs().max().item() < 1e-4 * max(1.0, p.grad.abs().max().item()), k
+            staged[direct] = ([(lo, hi) for _, _, lo, hi, _ in calls], q1, g1)
+        # the autograd form: the direct form's two segments, its Q and its gradients, bit for bit
+        (seg_d, q_d, g_d), (seg_a, q_a, g_a) = staged[True], staged[False]
+        assert seg_a == seg_d and torch.equal(q_a, q_d)
+        for k in g_d:
+            assert (g_d[k] is None) == (g_a[k] is None), k
+            if g_d[k] is not None:
+                assert torch.equal(g_d[k], g_a[k]), k
     finally:
+        ops.set_direct_grads(True)
         ops.set_grad_stage_hook(None)
         ops.set_math("fp32")
 

@@ -183,3 +183,33 @@ def test_gradient_buffers_are_reused_only_when_nobody_holds_them():
     torch.cuda.synchronize()
     got = [p.grad for p in plist if p.grad is not None]
     assert all(torch.allclose(g, a + b, rtol=0, atol=1e-6) for g, a, b in zip(got, want1, g2))
+
+
+def test_gradient_buffer_is_not_reused_under_a_kept_alias():
+    """A tensor on the gradient buffer's storage that is not one of the backward's own views (``p.grad.detach()``, ``.data``,
+    ``.view(-1)``) keeps that buffer from being handed out again: after ``zero_grad(set_to_none=True)`` and a backward on
+    other targets the alias still holds the first step's values."""
+    from helpers import batch_tensors, make_pair, sel_and_targets
+    from gnn_hex_amd import ops
+    hip, _ = make_pair(3, 35, seed=2)
+    x, ei, bv, ptr = batch_tensors("D0", [7] * 16)
+    sel, tgt = sel_and_targets(ptr)
+    xd = ops.attach_hints(x.cuda(), True, int((ptr[1:] - ptr[:-1]).max()))
+    eid = ei.cuda()
+    eid._hex_grouped = True
+    bvd, ptrd, seld = bv.cuda(), ptr.cuda(), sel.cuda()
+    p = next(hip.parameters())
+
+    def step(t):
+        hip.zero_grad(set_to_none=True)
+        q = hip(xd, eid, bvd, ptrd)
+        F.mse_loss(q[seld], t).backward()
+        assert isinstance(hip.__dict__["_fca"], ops._QNetCall)             # the direct form ran
+
+    step(tgt.cuda())
+    a = p.grad.detach().clone()
+    alias = p.grad.detach()
+    step((tgt * -0.5 + 0.1).cuda())
+    torch.cuda.synchronize()
+    assert not torch.equal(p.grad, a)                  # the gradients did change
+    assert torch.equal(alias, a)

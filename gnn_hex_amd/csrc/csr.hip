@@ -341,7 +341,7 @@ struct CsrArgs {
 // 128 rows while they fit, a graph above 128 rows gets a 64-row head block and the rest in equal pieces of at most 128.  The host
 // never sees the graph sizes (raw tensors of another collation: torch_geometric's Batch), so the table always has max_blocks
 // entries: unused ones are empty blocks at the end (start == n), and a batch that needs more than max_blocks aligned blocks gets
-// the plain 128-row partition (the caller made sure that one fits).  Sizes pass through LDS in chunks of 1024 graphs; the packing
+// the plain 128-row partition (the caller made sure that one fits).  Sizes pass through LDS in chunks of 512 graphs; the packing
 // itself is sequential (one lane).
 __device__ void block_table_body(int n, int b, const int* __restrict__ gptr, const int64_t* __restrict__ ptr64,
                                  int* __restrict__ out, int max_blocks) {

@@ -1,5 +1,5 @@
 // Cross-translation-unit internals of libhexgnn.so (plans + launch helpers shared by the layer-major
-// path in sage.hip / head.hip and the fused per-graph path in qnet_fused.hip).
+// path in sage*.hip / head.hip and the fused per-graph path in qnet_fused.hip).
 #pragma once
 #include "hexgnn_common.h"
 

@@ -1,4 +1,4 @@
-// Weight packing of a SAGE stack (one launch per forward call: sage_pack_kernel in sage.hip, or the extra workgroups of
+// Weight packing of a SAGE stack (one launch per forward call: sage_pack_kernel in sage_pack.hip, or the extra workgroups of
 // csr_grouped_pack_kernel in csr.hip -- the CSR build and the pack do not depend on each other).
 #pragma once
 #include "hexgnn_internal.h"
@@ -70,7 +70,7 @@ __device__ __forceinline__ void sage_pack_body(const PackArgs& a, char* __restri
 
 
 
-// host side: fill PackArgs from a plan (sage.hip)
+// host side: fill PackArgs from a plan (sage_pack.hip)
 int fill_pack_args(const StackPlan& p, int c_in, int hidden, const float* const* wl, const float* const* bl,
                    const float* const* wr, PackArgs* pa);
 

@@ -1,4 +1,4 @@
-// Batched weight-gradient GEMM of the hidden SAGE layers in exact fp32 (included by sage.hip and by the stand-alone
+// Batched weight-gradient GEMM of the hidden SAGE layers in exact fp32 (included by sage_dw.hip and by the stand-alone
 // timing harness tools/microbench/dw_coexec.hip).
 //
 // Reference: the autograd backward of SAGEConv's two linears (GN0/torch_script_models.py:52-73; call site GN0/models.py:276):

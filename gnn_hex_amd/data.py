@@ -14,7 +14,7 @@ from typing import List, Optional
 import torch
 
 
-BLOCK_ROWS = 128         # rows of one workgroup of the layer-major kernels (gnn_hex_amd/csrc/sage.hip)
+BLOCK_ROWS = 128         # rows of one workgroup of the layer-major kernels (gnn_hex_amd/csrc/sage_layer.hip, sage_stack.hip)
 
 
 def blocks_for_order(sizes: List[int], block: int = BLOCK_ROWS, head: int = 64) -> List[int]:

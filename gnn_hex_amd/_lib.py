@@ -38,6 +38,7 @@ _SIGS = {
     "hexgnn_sage_stack_saved_bytes": (sz, [ci, ci, ci, ci]),
     "hexgnn_sage_stack_forward": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
     "hexgnn_sage_stack_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "hexgnn_dw_slice_plan": (ci, [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]),
     "hexgnn_sage_stack_backward": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, sz, ci, vp]),
     "hexgnn_sage_stack_backward_tap": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,

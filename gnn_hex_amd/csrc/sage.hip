@@ -22,7 +22,9 @@ using namespace hexgnn;
 // CONTENT is device data: checked by the kernel, block by block)
 static bool block_table_ok(int n, const int* block_starts, int num_blocks) {
     if (!block_starts) return num_blocks == 0;
-    return num_blocks >= (n + 127) / 128 && num_blocks >= 1 && num_blocks <= kStackFlagWords && num_blocks <= n;
+    // (more blocks than rows is fine: a table built on the device has the block budget's entries whatever n is, the unused ones
+    // == n -- empty blocks, which leave at once)
+    return num_blocks >= (n + 127) / 128 && num_blocks >= 1 && num_blocks <= kStackFlagWords;
 }
 
 // the backward workspace of a plan: G (per-layer masked output gradients), the weight-gradient slabs, the raw first layer's partials

@@ -90,7 +90,6 @@ __global__ __launch_bounds__(64 * NT) void sage_dw16_kernel(Dw16Args a, float* _
 #pragma unroll
     for (int t = 0; t < NT; ++t) { acc[t][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[t][1] = acc[t][0]; }
     f32x4 gsum = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (r_beg >= r_end) return;         // block-uniform (cannot happen with the host's slicing)
 
     const int q = tid % Q, rp = tid / Q;            // this thread's column group and row pair
     // two register sets of prefetched rows: the loads of chunk i+2 are issued while chunk i is multiplied (86 KB in flight
@@ -147,8 +146,13 @@ __global__ __launch_bounds__(64 * NT) void sage_dw16_kernel(Dw16Args a, float* _
             acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[1], acc[t][1], 0, 0, 0);
         }
     };
-    issue(pA, r_beg);
-    issue(pB, r_beg + R);          // rows past the slice are clamped + flagged, so an over-issue is harmless
+    // An EMPTY slice (r_beg >= n: rows_per_slice is rounded up to 32 after the slice count is chosen, so the last slices of
+    // a launch can start at or beyond n) loads nothing, skips the loop and stores its slab like any other: zeros, which the
+    // slice reduce then sums.  block-uniform
+    if (r_beg < r_end) {
+        issue(pA, r_beg);
+        issue(pB, r_beg + R);      // rows past the slice are clamped + flagged, so an over-issue is harmless
+    }
     for (int rc = r_beg; rc < r_end; rc += 2 * R) {
         stage(pA);
         __syncthreads();
@@ -435,3 +439,12 @@ int launch_weight_grads(int n, int c_in, int hidden, const StackPlan& p, const B
 }
 
 }  // namespace hexgnn
+
+extern "C" int hexgnn_dw_slice_plan(int n, int hidden_layers, int math, int stack_hidden_layers, int* slices,
+                                    int* rows_per_slice) {
+    if (n < 0 || hidden_layers < 1 || stack_hidden_layers < hidden_layers || math < 0 || math > 1 || !slices || !rows_per_slice)
+        return HEXGNN_EINVAL;
+    *slices = hexgnn::dw_slices_for(n, hidden_layers, math, stack_hidden_layers);
+    *rows_per_slice = hexgnn::dw_rows_per_slice(n, *slices);
+    return HEXGNN_OK;
+}

@@ -133,6 +133,13 @@ int hexgnn_sage_stack_forward(int n, int c_in, int hidden, int num_layers,
                               hexgnn_stream_t stream);
 
 size_t hexgnn_sage_stack_backward_workspace_bytes(int n, int c_in, int hidden, int num_layers);
+/* Row-slice plan of ONE launch of the batched weight-gradient GEMM (pure host arithmetic, like the *_bytes() queries): the
+ * launch covers `hidden_layers` hidden-input layers of a stack that has `stack_hidden_layers` of them (the staged backward
+ * launches a part of the stack; otherwise the two are equal), in math 0 (exact fp32) or 1 (f16x3).  *slices workgroups per
+ * layer take *rows_per_slice rows each; slice s covers rows [s * rows_per_slice, min(n, (s + 1) * rows_per_slice)), which is
+ * EMPTY when s * rows_per_slice >= n (rows_per_slice is rounded up to 32 after the slice count is chosen), and an empty
+ * slice contributes a zero slab.  HEXGNN_EINVAL for n < 0, layer counts < 1, stack_hidden_layers < hidden_layers or a NULL. */
+int hexgnn_dw_slice_plan(int n, int hidden_layers, int math, int stack_hidden_layers, int* slices, int* rows_per_slice);
 /* dy: gradient w.r.t. the stack output, padded layout [n][HP].
  * dx: gradient w.r.t. the stack input, padded layout [n][HP]; NULL to skip (always skipped when
  *     c_in != hidden).  d_wl/d_bl/d_wr: HOST arrays of device pointers, written (not accumulated),

@@ -332,3 +332,80 @@ def test_rollout_stitcher_on_host():
                               [round(v, 9) for v in blk.reward.tolist()],
                               [-1 if v < 0 else v for v in blk.next_step.tolist()], blk.done.tolist()))
             assert sorted(got[side]) == want and len(want) > 0, (n_steps, side)
+
+
+def test_dw_slice_plan_edges():
+    """The row-slice plan of the batched weight-gradient GEMM (hexgnn_dw_slice_plan = the launch's own dw_slices_for /
+    dw_rows_per_slice), every n in 1..70 000, both math modes, the hidden-layer counts of the networks in use (16 = GNN-L,
+    11 = GNN-S, 14 / 2 = the two stacks of --norm=True, 8 = a stage of GNN-L's staged backward, ...).  rows_per_slice is rounded
+    up to 32 AFTER the slice count is chosen, so trailing slices can start at or beyond n (about half of all n in math 0):
+    the plan must still cover every row, stay inside the slab count the workspaces are sized for (kDwMaxSlices = 64 per layer,
+    128 for stacks of at most two hidden layers), and use no more slices in f16x3 than in fp32 (the workspace follows the
+    fp32 count).  The kernels' side of the bargain -- an empty slice writes a zero slab -- is tests/test_gpu_dw_slices.py,
+    whose batches are asserted to exist here."""
+    import ctypes
+    from gnn_hex_amd import _lib
+    from helpers import DW_MODELS, dw_case_list, dw_empty_slices, dw_has_empty, dw_launches, dw_plan, start_board_nodes
+    L = _lib.lib()
+    s, r = ctypes.c_int(), ctypes.c_int()
+    bs, br = ctypes.byref(s), ctypes.byref(r)
+    assert L.hexgnn_dw_slice_plan(-1, 1, 0, 1, bs, br) == -1 and L.hexgnn_dw_slice_plan(5, 0, 0, 1, bs, br) == -1
+    assert L.hexgnn_dw_slice_plan(5, 2, 0, 1, bs, br) == -1 and L.hexgnn_dw_slice_plan(5, 1, 2, 1, bs, br) == -1
+    assert L.hexgnn_dw_slice_plan(5, 1, 0, 1, None, br) == -1 and L.hexgnn_dw_slice_plan(5, 1, 0, 1, bs, None) == -1
+    plan = L.hexgnn_dw_slice_plan
+    counts = [(h, h) for h in (1, 2, 3, 7, 8, 9, 11, 13, 14, 16)] + [(7, 14), (8, 16)]      # (launch, whole stack)
+    with_empty = {c: [0, 0] for c in counts}
+    N = 70000
+    for h, sh in counts:
+        cap = 128 if (h <= 2 and sh <= 2) else 64
+        for n in range(1, N + 1):
+            got = []
+            for m in (0, 1):
+                assert plan(n, h, m, sh, bs, br) == 0
+                S, rps = s.value, r.value
+                if not (S >= 1 and rps % 32 == 0 and S * rps >= n and S <= cap):
+                    raise AssertionError("n %d, %d of %d layers, math %d: %d slices of %d rows" % (n, h, sh, m, S, rps))
+                if (S - 1) * rps >= n:
+                    with_empty[(h, sh)][m] += 1
+                got.append(S)
+            assert got[1] <= got[0], (n, h, sh, got)
+    # empty slices are ordinary, not a corner: GNN-L's plan has one for about half of all n in math 0
+    assert with_empty[(16, 16)][0] > N // 4 and with_empty[(16, 16)][1] > 0 and with_empty[(11, 11)][1] > 0, with_empty
+    assert dw_plan(3936, 16, 1) == (15, 288) and dw_empty_slices(3936, 15, 288) == 1        # 32 Hex-11 start boards, f16x3
+
+    # the batches tests/test_gpu_dw_slices.py runs exist, and are what their ids say
+    for size in (7, 11):
+        ptr = batch_tensors("D0", [size] * 3)[3].tolist()
+        assert ptr == [0, start_board_nodes(size), 2 * start_board_nodes(size), 3 * start_board_nodes(size)]
+    cases = dw_case_list()
+    ids = [c[0] for c in cases]
+    assert len(set(ids)) == len(ids)
+    for key in ("L", "S"):
+        for role in ("m0-first", "m0-last", "m0-before", "m0-after", "m1-first", "m1-last", "m1-before", "m1-after",
+                     "tiny", "over1024"):
+            assert any(c[1] == key and not c[3] and not c[4] and role in c[0] for c in cases), (key, role)
+    for name, key, b, staged, norm in cases:
+        assert 1 <= b <= 256, name
+        layers, _, size = DW_MODELS[key]
+        n = b * start_board_nodes(size)
+        launches = dw_launches(layers, staged=staged, norm=norm)
+        for m in (0, 1):
+            for role in ("first", "last"):
+                if "m%d-%s" % (m, role) in name:
+                    assert dw_has_empty(n, launches, m), name
+            for role in ("before", "after"):
+                if "m%d-%s" % (m, role) in name:
+                    assert not dw_has_empty(n, launches, m), name
+        if "tiny" in name:
+            assert n < 256 and dw_plan(n, launches[0][0], 0)[0] == 1, name
+        if "over1024" in name:
+            assert n > 1024 and 0 < n % 1024 <= 8, name
+        if "empty" in name:
+            assert dw_has_empty(n, launches, 0), name
+            if staged:      # BOTH stages, both math modes
+                assert all(dw_has_empty(n, [l], m) for l in launches for m in (0, 1)), name
+            if key == "h64":
+                assert dw_has_empty(n, launches, 1), name
+            if norm:        # the head stack's launch takes more slices than a longer stack may
+                S, rps = dw_plan(n, 2, 0, 2)
+                assert S > 64 and dw_empty_slices(n, S, rps) > 0, name

@@ -153,3 +153,127 @@ def sel_and_targets(ptr, seed=1):
     gen = torch.Generator().manual_seed(seed)
     tgt = torch.rand(len(sel), generator=gen) * 2 - 1
     return torch.tensor(sel, dtype=torch.long), tgt
+
+
+# ---- raw feature counts 1..8 on every path (tests/test_gpu_feature_counts.py) ---------------------------------------------
+
+def feature_batch(sizes, c_in, seed, p_edge=0.08):
+    """Symmetric random graphs with ``c_in`` raw features per node: ``(x [n, c_in], edge_index, batch, ptr)``, edges grouped by
+    graph in graph order (what a collation produces).  Column 0 holds integers 0..8 (a degree-like count), odd columns 0/1
+    flags, the other even columns U(-1, 1); no column is constant over the batch.  Every graph of two or more nodes has the
+    edge 0 <-> 1, so that the neighbour mean is exercised in the 2- and 3-node graphs too; graphs above 3 nodes keep their
+    last node isolated."""
+    rng = np.random.default_rng(seed)
+    xs, eis, bv, ptr, off = [], [], [], [0], 0
+    for g, n in enumerate(sizes):
+        x = np.zeros((n, c_in), np.float32)
+        for k in range(c_in):
+            if k == 0:
+                x[:, k] = rng.integers(0, 9, n)
+            elif k % 2 == 1:
+                x[:, k] = rng.random(n) < 0.4
+            else:
+                x[:, k] = rng.random(n) * 2 - 1
+        m = np.triu(rng.random((n, n)) < p_edge, 1)
+        if n >= 2:
+            m[0, 1] = True
+        if n > 3:
+            m[:, n - 1] = False
+        src, dst = np.nonzero(m)
+        src, dst = np.concatenate([src, dst]), np.concatenate([dst, src])
+        perm = rng.permutation(len(src))
+        xs.append(x)
+        eis.append(np.stack([src[perm], dst[perm]]).astype(np.int64) + off)
+        bv.append(np.full(n, g, np.int64))
+        off += n
+        ptr.append(off)
+    x = np.concatenate(xs)
+    assert all(np.ptp(x[:, k]) > 0 for k in range(c_in)), "a feature column is constant over the batch"
+    return (torch.from_numpy(x), torch.from_numpy(np.concatenate(eis, 1)), torch.from_numpy(np.concatenate(bv)),
+            torch.tensor(ptr, dtype=torch.long))
+
+
+def qnet_ref(c_in, hidden, body, head, seed):
+    """The oracle's Q-network with ``c_in`` raw features: DuellingTwoHeadedRef built directly (get_pre_defined_ref fixes
+    in_channels = 2) with the ``modern_two_headed`` head, in the sharpened state."""
+    from oracle.model_ref import DuellingTwoHeadedRef
+    torch.manual_seed(seed)
+    ref = DuellingTwoHeadedRef(
+        gnn_kwargs=dict(in_channels=c_in, num_layers=body, hidden_channels=hidden, cached_norm=False, norm=None, act="relu"),
+        head_kwargs=dict(value_head_type="mlp", value_aggr_types=("sum", "max", "min", "mean"), num_layers=head,
+                         noisy_dqn=False, noise_sigma=0.5, norm=None))
+    return sharpen_(ref)
+
+
+def qnet_params(model):
+    """[(name, parameter)] of a ``qnet_ref`` model in the order of the fused call: (wl, bl, wr) per SAGE layer, body then
+    maker head, then lin_w, lin_b, v0_w, v0_b, v1_w, v1_b."""
+    out = []
+    for tag, convs in (("gnn", model.gnn.convs), ("maker_head.gnn", model.maker_head.gnn.convs)):
+        for l, conv in enumerate(convs):
+            out += [("%s.convs.%d.lin_l.weight" % (tag, l), conv.lin_l.weight), ("%s.convs.%d.lin_l.bias" % (tag, l), conv.lin_l.bias),
+                    ("%s.convs.%d.lin_r.weight" % (tag, l), conv.lin_r.weight)]
+    h = model.maker_head
+    out += [("maker_head.linear.weight", h.linear.weight), ("maker_head.linear.bias", h.linear.bias)]
+    for l in (0, 1):
+        out += [("maker_head.value_head.layers.%d.weight" % l, h.value_head.layers[l].weight),
+                ("maker_head.value_head.layers.%d.bias" % l, h.value_head.layers[l].bias)]
+    return out
+
+
+def qnet_ref_forward(model, x, ei, batch, mode):
+    """DuellingTwoHeadedRef.forward (oracle/model_ref.py) without the ``x[:, :2]`` slice and the side flag (the maker head
+    is evaluated): gnn -> maker_head -> 2 tanh(a), tanh(v), dueling combine.  Returns ``(q [n], out_v)``: mode 0 -> (Q, None),
+    1 (``seperate``) -> (A - mean A, tanh(v) [b]), 2 (``advantages_only``) -> (2 tanh(a), None)."""
+    from oracle.model_ref import scatter_ref
+    embeds = model.gnn(x, ei)
+    if mode == 2:
+        return (2 * torch.tanh(model.maker_head(embeds, ei, batch, advantages_only=True))).reshape(-1), None
+    adv, value = model.maker_head(embeds, ei, batch)
+    adv, value = 2 * torch.tanh(adv), torch.tanh(value)
+    b = int(batch.max()) + 1
+    centred = adv - scatter_ref(adv, batch, dim_size=b, reduce="mean").index_select(0, batch)
+    if mode == 1:
+        return centred.reshape(-1), value.reshape(-1)
+    return (value.index_select(0, batch) + centred).reshape(-1), None
+
+
+def one_row_per_graph(ptr, seed=1):
+    """(sel, tgt): row ptr[g] + (7919 g mod n_g) of every graph (1-node graphs included) and targets ~ U(-1, 1)."""
+    p = ptr.tolist()
+    sel = [p[g] + (g * 7919) % (p[g + 1] - p[g]) for g in range(len(p) - 1)]
+    gen = torch.Generator().manual_seed(seed)
+    return torch.tensor(sel, dtype=torch.long), torch.rand(len(sel), generator=gen) * 2 - 1
+
+
+def feature_loss(q, out_v, sel, tgt, mode):
+    """64 * mse(Q[sel], tgt), one selected row per graph; in mode 1 Q[sel] is put together from the two outputs
+    (tanh(v) of the row's graph + the centred advantage), so that both receive a gradient."""
+    pred = q[sel] + out_v if mode == 1 else q[sel]
+    return 64.0 * torch.nn.functional.mse_loss(pred, tgt)
+
+
+def qnet_hip_call(ref, x, ei, ptr, c_in, hidden, body, head, mode, layered, deferred, sel, tgt, gs=None, out=None):
+    """One forward + backward of the oracle's network through ``ops.qnet_forward`` / ``ops.qnet_backward`` (fused kernels, or
+    the layer-major ones when ``layered``; the math mode is the caller's ``ops.set_math``).  ``x`` [n, c_in] (any row stride),
+    ``ei`` and the int64 ``ptr`` are device tensors.  The structure is ``gs`` when given, the deferred grouped build
+    (CSR build and weight pack in one launch) when ``deferred``, else a prebuilt ``GraphStructure.grouped``; ``out``
+    (a dict) receives the structure the call ran on.  Returns ``(q, out_v, grads)``, the gradients of
+    ``feature_loss`` in call order (``qnet_params``; None for the value head in mode 2)."""
+    from gnn_hex_amd import ops
+    dev = x.device
+    params = [p.detach().to(device=dev, dtype=torch.float32).clone().requires_grad_(True) for _, p in qnet_params(ref)]
+    cache = ops.QNetParamCache(params, body + head)
+    n, b = int(x.shape[0]), int(ptr.numel()) - 1
+    if gs is None:
+        gs = (ei, n, b, ptr) if deferred else ops.GraphStructure.grouped(ei, n, b, ptr)
+    q, out_v, call = ops.qnet_forward(cache, x, gs, None, b, c_in, hidden, body, head, mode, True, layered=layered,
+                                      assign=False)
+    if out is not None:
+        out["gs"] = call.gs
+    ql = q.detach().clone().requires_grad_(True)
+    vl = out_v.detach().clone().requires_grad_(True) if mode == 1 else None
+    feature_loss(ql, vl, sel, tgt, mode).backward()
+    grads = ops.qnet_backward(call, ql.grad, vl.grad if mode == 1 else None)
+    torch.cuda.synchronize()
+    return q, out_v, grads

@@ -409,3 +409,33 @@ def test_dw_slice_plan_edges():
             if norm:        # the head stack's launch takes more slices than a longer stack may
                 S, rps = dw_plan(n, 2, 0, 2)
                 assert S > 64 and dw_empty_slices(n, S, rps) > 0, name
+
+
+def test_raw_feature_count_bounds_are_refused_on_the_host():
+    """The raw first layer takes 1..8 features (include/hexgnn.h): 0 and 9 are refused by the host queries, c_in == hidden means
+    the padded layout (no fused kernel), and a row stride below c_in is a bad argument.  Nothing here launches anything."""
+    from gnn_hex_amd import _lib
+    L = _lib.lib()
+    for c_in in (0, 9):
+        assert L.hexgnn_qnet_supported(c_in, 35, 64) == 0
+        assert L.hexgnn_sage_stack_pack_bytes(c_in, 35, 3) == 0
+        assert L.hexgnn_qnet_saved_bytes(196, 7, c_in, 35, 4) == 0 and L.hexgnn_qnet_backward_workspace_bytes(196, 7, c_in, 35, 4) == 0
+    for c_in in range(1, 9):
+        assert L.hexgnn_qnet_supported(c_in, 35, 128) == 1 and L.hexgnn_qnet_supported(c_in, 35, 129) == 0
+        assert L.hexgnn_sage_stack_pack_bytes(c_in, 35, 3) > 0
+    for k in (4, 8):
+        assert L.hexgnn_qnet_supported(k, k, 64) == 0           # c_in == hidden: padded layout, layer-major kernels only
+        assert L.hexgnn_sage_stack_pack_bytes(k, k, 3) > 0
+    for hidden in (2, 3, 5):                                    # the narrowest widths the fused kernels take
+        assert L.hexgnn_qnet_supported(4, hidden, 128) == 1
+    assert L.hexgnn_qnet_supported(4, 1, 128) == 0
+    # x_stride < c_in: every buffer the argument check wants is given (host memory, never dereferenced), n = b = 0, the weights
+    # "packed already", mode 2 (no value head) -- so the stride is the only thing wrong, and the check answers before any launch
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.addressof(buf)
+
+    def forward(c_in, x_stride):
+        return L.hexgnn_qnet_forward(0, 0, c_in, 35, 4, 2, p, None, None, None, None, x_stride, None, None, None, p, p, None,
+                                     None, None, None, p, None, p, 0, -1, 0, None, None, p, None)
+    assert forward(3, 2) == -1 and forward(8, 7) == -1 and forward(1, 0) == -1        # HEXGNN_EINVAL
+    assert forward(9, 9) == -2 and forward(0, 3) == -2                                 # HEXGNN_EUNSUPPORTED comes first

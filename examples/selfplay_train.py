@@ -83,11 +83,9 @@ def main():
             for side in sides:
                 buf = bufs[side]
                 idx, w, s, s2, act, r, d = buf.sample_end(pending[side])
-                with torch.no_grad():
-                    q_on = q_net(s2.x, s2.edge_index, s2.batch, s2.ptr)
-                    q_tg = target_net(s2.x, s2.edge_index, s2.batch, s2.ptr)
-                    # double DQN: argmax of the online net over each next state's non-terminal nodes, target net's value
-                    y = r + (gamma ** n_step) * q_tg[ops.greedy_nodes(q_on, s2.ptr)] * (~d).float()
+                # double DQN: argmax of the online net over each next state's non-terminal nodes, target net's value there --
+                # both networks in one forward launch, y = r + gamma^n * q_tg[argmax] * (~d).float() formed by one more
+                y, _ = ops.double_dqn_targets(q_net, target_net, s2.x, s2.edge_index, s2.batch, s2.ptr, r, d, gamma ** n_step)
                 q = q_net(s.x, s.edge_index, s.batch, s.ptr)
                 loss, td = ops.td_loss(q, s.ptr[:-1] + act.long(), y, w, "mse")
                 opt.zero_grad(set_to_none=True)

@@ -94,6 +94,11 @@ _SIGS = {
                                     vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
     "hexgnn_qnet_backward_flat_td": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp, sz, vp, ci, ci, ci, vp, vp, vp]),
+    "hexgnn_qnet_jobs_bytes": (sz, [ci, ci]),
+    "hexgnn_qnet_multi_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
+    "hexgnn_qnet_forward_jobs": (ci, [ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "hexgnn_qnet_forward_multi": (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+    "hexgnn_dqn_targets": (ci, [ci, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp]),
     "hexgnn_env_create": (ci, [ci, ci, vp]),
     "hexgnn_env_destroy": (None, [vp]),
     "hexgnn_env_num_vertices": (ci, [vp]),

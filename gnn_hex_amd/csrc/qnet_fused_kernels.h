@@ -52,6 +52,19 @@ struct QFwdArgs {
     float* td_dq; float* td_out; float* td_loss_part;
 };
 
+// The job-table form of the forward (qnet_fwd_kernel<NT, 0, true>): up to kMaxSets weight sets over the same batch in one launch.
+constexpr int kMaxSets = HEXGNN_MAX_SETS;
+static_assert((kMaxSets & (kMaxSets - 1)) == 0 && kMaxSets == 4, "a job word keeps the set in its two low bits");
+struct QSet {     // what belongs to one weight set
+    const char* wpack;
+    const float* lin_w; const float* lin_b; const float* v0_w; const float* v0_b; const float* v1_w; const float* v1_b;
+    float* q; int* status;
+};
+struct QFwdJobArgs : QFwdArgs {     // the batch and the plan (the base's per-set fields, acts / saved / head scalars / TD fields are not read)
+    const int* jobs;       // [b * sets]: graph << 2 | set, largest graph first (qnet_jobs_pack_kernel)
+    QSet set[kMaxSets];
+};
+
 struct QBwdArgs {
     int n, b, H, L, mode, body_layers;
     const int* gptr; const int* rowptr_t; const int* col_t; const float* invdeg;
@@ -563,8 +576,20 @@ template <int NT> __device__ __forceinline__ int dma_share2(int wave, int q, boo
 }
 
 // ================================================= forward =================================================
-template <int NT, int MATH>
-__global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
+// With JOBS (exact fp32 only; instantiated in qnet_fused_jobs.hip) the inference-only job-table form: workgroup j runs job
+// jobs[j] = (graph << 2 | weight set) instead of graph blockIdx.x, and everything that belongs to a weight set -- QSEL(field) --
+// comes from that set's row of the table in the kernel arguments (wave-uniform: the job word goes through readfirstlane, the row
+// is read with scalar loads); need_backward = 0, mode = 0 (QMODE), no activation / saved-tensor / head-scalar stores (compiled
+// out: two sets never write the same words), no TD tail.  A graph's arithmetic is the same instruction sequence in both forms.
+// (QSEL is a conditional on a constant, not a lambda or an accessor taking `a` by reference: either of those -- like moving the
+// body into a function called from two kernels -- changed the register allocation of the plain form.)
+__device__ __forceinline__ const QSet* qsets(const QFwdArgs&) { return nullptr; }
+__device__ __forceinline__ const QSet* qsets(const QFwdJobArgs& a) { return a.set; }
+#define QSEL(field) (JOBS ? qsets(a)[wset].field : a.field)
+#define QMODE (JOBS ? 0 : a.mode)
+template <int NT, int MATH, bool JOBS = false>
+__global__ __launch_bounds__(512) void qnet_fwd_kernel(std::conditional_t<JOBS, QFwdJobArgs, QFwdArgs> a) {
+    static_assert(!JOBS || MATH == 0, "the job-table form is exact fp32 only");
     using LD = QLds<NT>;
     constexpr int HP = LD::HP, XS = LD::XS, kHalf = LD::kHalf;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -575,17 +600,19 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
-    const int gi = blockIdx.x;
+    const int job = [&] { if constexpr (JOBS) return __builtin_amdgcn_readfirstlane(a.jobs[blockIdx.x]); else return 0; }();
+    const int gi = JOBS ? job >> 2 : (int)blockIdx.x, wset = JOBS ? job & (kMaxSets - 1) : 0;
+    (void)wset;
     QSTAMP(0, 0, 0);
     // Requested before anything that depends on the graph (round 4): W_r of the first hidden layer (half B) and the raw first
     // layer's weights -- their round trips overlap the chain gptr -> rowptr -> columns instead of following it.
     constexpr int kStage1 = (LD::kHalf + 511) / 512, kStage0 = (2 * HP * kSmallCin / 4 + 511) / 512;
     f32x4 wstg1[kStage1], wstg0[kStage0];
     {
-        const f32x4* src1 = reinterpret_cast<const f32x4*>(a.wpack + a.fwd_off[a.L > 1 ? 1 : 0]) + kHalf;
+        const f32x4* src1 = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.fwd_off[a.L > 1 ? 1 : 0]) + kHalf;
 #pragma unroll
         for (int k = 0; k < kStage1; ++k) { const int i = tid + 512 * k; if (a.L > 1 && i < kHalf) wstg1[k] = src1[i]; }
-        const f32x4* src0 = reinterpret_cast<const f32x4*>(a.wpack + a.fwd_off[0]);
+        const f32x4* src0 = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.fwd_off[0]);
 #pragma unroll
         for (int k = 0; k < kStage0; ++k) { const int i = tid + 512 * k; if (i < 2 * HP * kSmallCin / 4) wstg0[k] = src0[i]; }
     }
@@ -595,13 +622,15 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
         // a graph that does not fit the tile reached this kernel (stale size hint): flag it AND poison its outputs, so
         // the failure is visible in the data even if nobody reads the status word
         if (tid == 0) {
-            atomicOr(a.status, 2);
-            if (a.out_v) a.out_v[gi] = __builtin_nanf("");
-            if (a.td_sel && a.mode == 0) { a.td_out[gi] = __builtin_nanf(""); a.td_loss_part[gi] = __builtin_nanf(""); }
+            atomicOr(QSEL(status), 2);
+            if constexpr (!JOBS) {
+                if (a.out_v) a.out_v[gi] = __builtin_nanf("");
+                if (a.td_sel && a.mode == 0) { a.td_out[gi] = __builtin_nanf(""); a.td_loss_part[gi] = __builtin_nanf(""); }
+            }
         }
         for (int i = tid; i < cnt; i += 512) {
-            a.q[r0 + i] = __builtin_nanf("");
-            if (a.td_sel && a.mode == 0) a.td_dq[r0 + i] = __builtin_nanf("");
+            QSEL(q)[r0 + i] = __builtin_nanf("");
+            if constexpr (!JOBS) { if (a.td_sel && a.mode == 0) a.td_dq[r0 + i] = __builtin_nanf(""); }
         }
         return;
     }
@@ -620,15 +649,15 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     constexpr bool kBiasAhead = NT <= 4;
     f32x4 b0v[kBiasAhead ? NT : 1];
     if constexpr (kBiasAhead) {
-        const f32x4* b0 = reinterpret_cast<const f32x4*>(a.wpack + a.bias_off[0]);
+        const f32x4* b0 = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.bias_off[0]);
 #pragma unroll
         for (int t = 0; t < NT; ++t) b0v[t] = b0[4 * t + g];
     }
     // (exact fp32: the first hidden layer's bias row, which its accumulators start from)
     f32x4 b1stg = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (MATH == 0) { if (a.L > 1 && tid < HP / 4) b1stg = reinterpret_cast<const f32x4*>(a.wpack + a.bias_off[1])[tid]; }
+    if constexpr (MATH == 0) { if (a.L > 1 && tid < HP / 4) b1stg = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.bias_off[1])[tid]; }
     const int e0 = a.rowptr[r0], ne = a.rowptr[r1] - e0;
-    const bool csr_lds = load_csr<NT>(lds, a.rowptr, a.col, r0, cnt, e0, ne, a.status);
+    const bool csr_lds = load_csr<NT>(lds, a.rowptr, a.col, r0, cnt, e0, ne, QSEL(status));
     float* s_max = reinterpret_cast<float*>(lds + LD::off_max);      // per-wave maxima (math 1)
     if (tid < 16) s_max[tid] = 0.f;
     if (tid < XS) xbuf[kRows * XS + tid] = 0.f;                      // the gather's filler row
@@ -678,7 +707,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
                 }
 #pragma unroll
                 for (int qq = 0; qq < kSmallCin; ++qq) ag0[qq] *= sc0;
-                if (a.need_backward) {
+                if (!JOBS && a.need_backward) {
                     f32x4* ao = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.saved + a.agg_off[0]) + (size_t)row * kSmallCin);
                     ao[0] = f32x4{ag0[0], ag0[1], ag0[2], ag0[3]};
                     ao[1] = f32x4{ag0[4], ag0[5], ag0[6], ag0[7]};
@@ -700,7 +729,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
         for (int t = 0; t < NT; ++t) {
             f32x4 v;
             if constexpr (kBiasAhead) v = b0v[t];
-            else v = reinterpret_cast<const f32x4*>(a.wpack + a.bias_off[0])[4 * t + g];
+            else v = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.bias_off[0])[4 * t + g];
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) {
                 const int o = 16 * t + 4 * g + q4;
@@ -762,12 +791,12 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     for (int l = 1; l < a.L; ++l) {
         QSTAMP(0, l, 0);
         if (l > 1) publish_xmax(l - 1);
-        const f32x4* wsrc = reinterpret_cast<const f32x4*>(a.wpack + a.fwd_off[l]);
+        const f32x4* wsrc = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.fwd_off[l]);
         const bool more = l + 1 < a.L;
-        const f32x4* nsrc = reinterpret_cast<const f32x4*>(a.wpack + a.fwd_off[more ? l + 1 : l]) + kHalf;
+        const f32x4* nsrc = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.fwd_off[more ? l + 1 : l]) + kHalf;
         // exact fp32: the NEXT layer's bias row is staged (its accumulators start from it); split math: this layer's
         f32x4 bstg = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (tid < HP / 4) bstg = reinterpret_cast<const f32x4*>(a.wpack + a.bias_off[(MATH == 0 && more) ? l + 1 : l])[tid];
+        if (tid < HP / 4) bstg = reinterpret_cast<const f32x4*>(QSEL(wpack) + a.bias_off[(MATH == 0 && more) ? l + 1 : l])[tid];
         auto dmaS = [&](auto qq) {
             const int p = dma_share<NT>(wave, decltype(qq)::value, spare);
             if (p >= 0) dma_piece(wsrc + p * 64, lane16, lds_w + p * 1024);
@@ -813,7 +842,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
             constexpr int Q = decltype(qq)::value;
             gather_gap<NT, Q, kGaps, MATH>(xbuf, nbr, ag, tb);
             if constexpr (Q < kDma) dmaS(qq);
-            else if constexpr (Q < kDma + NT) buf_store(xs[Q - kDma], yprev, yprev_off + 64 * (Q - kDma));
+            else if constexpr (Q < kDma + NT && !JOBS) buf_store(xs[Q - kDma], yprev, yprev_off + 64 * (Q - kDma));
         };
         contract_half_fill<NT, MATH>(wbuf + kHalf, lane, xs, acc, rs, fillS);
         static_for<kTail, kFill>(fillS);
@@ -844,14 +873,14 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
             const float carry = rsa * rinv;
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] *= carry;
-            rinv = rinva * (reinterpret_cast<const float*>(a.wpack + a.bias_off[l]) + HP)[1];
+            rinv = rinva * (reinterpret_cast<const float*>(QSEL(wpack) + a.bias_off[l]) + HP)[1];
         }
         const __amdgpu_buffer_rsrc_t ao = slab_rsrc(a.saved + a.agg_off[l]);
         const unsigned ao_off = (rvalid && a.need_backward) ? rowoff : kOob;
         auto fillA = [&](auto qq) {
             constexpr int Q = decltype(qq)::value;
             if constexpr (Q < kDma) dmaA(qq);
-            else if constexpr (Q < kDma + NT) buf_store(ag[Q - kDma], ao, ao_off + 64 * (Q - kDma));
+            else if constexpr (Q < kDma + NT && !JOBS) buf_store(ag[Q - kDma], ao, ao_off + 64 * (Q - kDma));
         };
         contract_half_fill<NT, MATH>(wbuf, lane, ag, acc, rsa, fillA);
         static_for<kTail, kFill>(fillA);
@@ -875,7 +904,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
         lds_barrier();     // barrier 2: new rows + half B = W_r(l+1) visible; half A free
         QSTAMP(0, l, 7);
     }
-    {   // the last layer's rows (the only layer when L == 1)
+    if constexpr (!JOBS) {   // the last layer's rows (the only layer when L == 1)
         if (a.L > 1) publish_xmax(a.L - 1);
         const __amdgpu_buffer_rsrc_t ylast = slab_rsrc(a.acts + slab * (a.L - 1));
         const unsigned ylast_off = acts_off(a.L - 1);
@@ -896,15 +925,15 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     int* s_ax = reinterpret_cast<int*>(sc + 1920);   // [3][128]
     int* s_an = reinterpret_cast<int*>(sc + 2304);   // [3][128]
     const int H2 = H / 2, H4 = 4 * H;
-    if (tid < 128) s_w[tid] = tid < H ? a.lin_w[tid] : 0.f;
+    if (tid < 128) s_w[tid] = tid < H ? QSEL(lin_w)[tid] : 0.f;
     // the tail's small global operands are requested here, one round trip for all of them, instead of one each at the point
     // of use (four exposed round trips on a path with no other work to hide them)
-    const float lin_b0 = a.lin_b[0];
+    const float lin_b0 = QSEL(lin_b)[0];
     const int vk_ = tid >> 3;
-    const float v0b_k = (a.mode != 2 && vk_ < H2) ? a.v0_b[vk_] : 0.f;
-    const float v1w_l = (a.mode != 2 && wave == 0 && lane < H2) ? a.v1_w[lane] : 0.f;
-    const float v1b_0 = a.mode != 2 ? a.v1_b[0] : 0.f;
-    const bool td_on = a.td_sel != nullptr && a.mode == 0;
+    const float v0b_k = (QMODE != 2 && vk_ < H2) ? QSEL(v0_b)[vk_] : 0.f;
+    const float v1w_l = (QMODE != 2 && wave == 0 && lane < H2) ? QSEL(v1_w)[lane] : 0.f;
+    const float v1b_0 = QMODE != 2 ? QSEL(v1_b)[0] : 0.f;
+    const bool td_on = !JOBS && a.td_sel != nullptr && QMODE == 0;
     const long long td_s = td_on ? a.td_sel[gi] : -1;
     const float td_t = td_on ? a.td_tgt[gi] : 0.f;
     const float td_wg = (td_on && a.td_w) ? a.td_w[gi] : 1.f;
@@ -921,10 +950,10 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     adv += lin_b0;
     const float tadv = 2.f * tanhf(adv);
     if (g == 0 && rvalid) {
-        a.adv_raw[grow] = adv;
-        if (a.mode == 2) a.q[grow] = tadv;
+        if constexpr (!JOBS) a.adv_raw[grow] = adv;
+        if (QMODE == 2) QSEL(q)[grow] = tadv;
     }
-    if (a.mode == 2) return;
+    if (QMODE == 2) return;
     {   // sum of 2tanh(adv) over the graph: lanes g==0 of valid rows; fixed-shape tree
         float v = (g == 0 && rvalid) ? tadv : 0.f;
         v = wsum64(v);
@@ -936,7 +965,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     const int vk = tid >> 3, vpart = tid & 7;
     f32x4 wv[kVQ];
     {
-        const f32x4* wrow = reinterpret_cast<const f32x4*>(a.v0_w + (size_t)vk * H4);
+        const f32x4* wrow = reinterpret_cast<const f32x4*>(QSEL(v0_w) + (size_t)vk * H4);
 #pragma unroll
         for (int j = 0; j < kVQ; ++j) {
             const int q = vpart + 8 * j;
@@ -974,10 +1003,12 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
             if (cnt == 0) { mx = 0.f; mn = 0.f; }
             const float mean = sum / (float)max(cnt, 1);
             s_pool[c] = sum; s_pool[H + c] = mx; s_pool[2 * H + c] = mn; s_pool[3 * H + c] = mean;
-            float* pg = a.pooled + (size_t)gi * H4;
-            pg[c] = sum; pg[H + c] = mx; pg[2 * H + c] = mn; pg[3 * H + c] = mean;
-            a.amax[(size_t)gi * H + c] = ax >= 0 ? r0 + ax : -1;
-            a.amin[(size_t)gi * H + c] = an >= 0 ? r0 + an : -1;
+            if constexpr (!JOBS) {
+                float* pg = a.pooled + (size_t)gi * H4;
+                pg[c] = sum; pg[H + c] = mx; pg[2 * H + c] = mn; pg[3 * H + c] = mean;
+                a.amax[(size_t)gi * H + c] = ax >= 0 ? r0 + ax : -1;
+                a.amin[(size_t)gi * H + c] = an >= 0 ? r0 + an : -1;
+            }
         }
     }
     __syncthreads();
@@ -993,7 +1024,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
         if (vpart == 0 && vk < H2) {
             const float zz = fmaxf(p + v0b_k, 0.f);
             s_z[vk] = zz;
-            a.z[(size_t)gi * H2 + vk] = zz;
+            if constexpr (!JOBS) a.z[(size_t)gi * H2 + vk] = zz;
         }
     }
     __syncthreads();
@@ -1002,7 +1033,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
         p = wsum64(p);
         if (lane == 0) {
             const float v = p + v1b_0;
-            a.vraw[gi] = v;
+            if constexpr (!JOBS) a.vraw[gi] = v;
             s_misc[0] = tanhf(v);
         }
     }
@@ -1012,9 +1043,9 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     for (int w = 0; w < 8; ++w) adv_total += s_red[w];
     const float mean_adv = adv_total / (float)max(cnt, 1);
     const float V = s_misc[0];
-    if (a.mode == 1 && tid == 0) a.out_v[gi] = V;
-    const float qv = (a.mode == 0 ? V : 0.f) + tadv - mean_adv;
-    if (g == 0 && rvalid) a.q[grow] = qv;
+    if constexpr (!JOBS) { if (QMODE == 1 && tid == 0) a.out_v[gi] = V; }
+    const float qv = (QMODE == 0 ? V : 0.f) + tadv - mean_adv;
+    if (g == 0 && rvalid) QSEL(q)[grow] = qv;
     if (td_on) {
         // loss = mean_g w_g l(Q[sel_g] - target_g): the same per-entry expressions as td_loss_fused_kernel (head.hip), so dq
         // and td have its bits; the mean over the graphs is summed from td_loss_part by the backward's reduce launch
@@ -1038,6 +1069,9 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(QFwdArgs a) {
     }
     QSTAMP(0, 0, 2);
 }
+#undef QSEL
+#undef QMODE
+
 
 // ================================================= backward =================================================
 // Data-gradient chain of the whole network for one graph: head tail backward, then per layer
@@ -1471,7 +1505,9 @@ static int launch_qbwd_m(const QBwdArgs& a, hipStream_t st) {
     return HEXGNN_OK;
 }
 
-// one translation unit per math mode (co-compiled template variants perturb each other's register allocation)
+// one translation unit per math mode and one for the job-table form (co-compiled template variants perturb each other's
+// register allocation)
+int launch_qfwd_jobs(int nt, int njobs, const QFwdJobArgs& a, hipStream_t st);
 int launch_qfwd_math(int nt, int math, const QFwdArgs& a, hipStream_t st);
 int launch_qbwd_math(int nt, int math, const QBwdArgs& a, hipStream_t st);
 int launch_qfwd_split(int nt, const QFwdArgs& a, hipStream_t st);

@@ -1513,3 +1513,176 @@ def greedy_nodes(q: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
     _lib.check(_lib.lib().hexgnn_select_actions(b, gptr.data_ptr(), qf.data_ptr(), None, 0.0, None, None, rank.data_ptr(),
                                                 None, _stream()), "hexgnn_select_actions")
     return gptr[:-1].long() + rank.long()
+
+
+# ------------------------------------------------------------------------------------------------
+# several networks over ONE batch in one load-balanced forward launch; double-DQN targets
+# ------------------------------------------------------------------------------------------------
+MAX_SETS = 4          # HEXGNN_MAX_SETS
+
+
+def forward_jobs(ptr: torch.Tensor, k: int) -> torch.Tensor:
+    """The int32 job table ``[b * k]`` of a batch for ``k`` weight sets: job ``j`` = ``graph << 2 | set`` =
+    ``(order[j // k], j % k)``, ``order`` = the graphs by descending node count, ties by ascending graph index (built on the
+    device: no host sync).  The fused forward of ``multi_forward`` runs its workgroups in this order -- longest job first."""
+    _require_cuda(ptr, "ptr")
+    if not 1 <= int(k) <= MAX_SETS:
+        raise ValueError("1..%d weight sets" % MAX_SETS)
+    b = int(ptr.numel()) - 1
+    gptr = ptr.to(dtype=torch.int32).contiguous()
+    jobs = torch.empty(max(b, 0) * int(k), dtype=torch.int32, device=ptr.device)
+    if b > 0:
+        _lib.check(_lib.lib().hexgnn_qnet_forward_jobs(b, int(k), gptr.data_ptr(), jobs.data_ptr(), 0, 0, 0, None, None, None,
+                                                       None, _stream()), "hexgnn_qnet_forward_jobs")
+    return jobs
+
+
+def _multi_plan(models, x, edge_index, graph_indices, ptr):
+    """What the fused multi-set forward needs, or None when it does not apply (the callers then run every model's ordinary
+    forward): fused kernels on, exact fp32 math, every model a dueling Q-network with a parameter cache (no noisy head) and the
+    same (c_in, hidden, body layers, head layers), every graph within 128 nodes, hidden <= 112.  The side to move, the largest
+    graph and the CSR are found exactly as ``DuellingTwoHeaded.forward`` finds them (hints of ``x``, an attached
+    ``_hex_csr``, the one-launch build for a grouped batch)."""
+    if not _FUSED_ENABLED or _MATH != 0:
+        return None
+    hint, max_nodes = hints_of(x)
+    if hint is None:
+        assert torch.all(x[:, 2] == x[0, 2])
+        is_maker = bool(x[0, 2] == 1)
+    else:
+        is_maker = bool(hint)
+    dev, n = x.device, x.shape[0]
+    caches, dims = [], None
+    for m in models:
+        entry = getattr(m, "_fused_entry", None)
+        if entry is None:
+            return None
+        ent = entry(m._modules["maker_head" if is_maker else "breaker_head"])
+        c_in, h, n_body, n_head, fusable, noisy = ent[3]
+        cache = ent[2]
+        if not fusable or noisy or cache is None or (dims is not None and dims != (c_in, h, n_body, n_head)):
+            return None
+        dims = (c_in, h, n_body, n_head)
+        if not cache.valid():
+            cache.refresh()
+        if not all(p.is_cuda and p.device == dev and p.dtype == torch.float32 and p.is_contiguous() for p in cache.params):
+            return None
+        caches.append(cache)
+    c_in, h, n_body, n_head = dims
+    x2 = x[:, :2]
+    if x2.shape[1] != c_in:
+        return None
+    gptr = None
+    if max_nodes is None:
+        gptr, b = graph_ptr(graph_indices, ptr, n, dev)
+        max_nodes = int((gptr[1:] - gptr[:-1]).max()) if b > 0 else 0         # host sync (no size hint given)
+    if not qnet_fused_supported(c_in, h, max_nodes):
+        return None
+    gs = getattr(edge_index, "_hex_csr", None)
+    if gs is not None and gs.n != n:
+        gs = None
+    if gs is None and gptr is None and getattr(edge_index, "_hex_grouped", False) and max_nodes <= 2048 and ptr is not None \
+            and ptr.dtype == torch.int64 and ptr.is_cuda and ptr.is_contiguous() and int(ptr.numel()) > 1 \
+            and edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.is_contiguous() and edge_index.is_cuda:
+        b = int(ptr.numel()) - 1
+        gs = GraphStructure.grouped(edge_index, n, b, ptr)        # the one-launch build; carries its int32 node ranges
+    else:
+        if gptr is None:
+            gptr, b = graph_ptr(graph_indices, ptr, n, dev)
+        if gs is None:
+            grouped = getattr(edge_index, "_hex_grouped", False) and max_nodes <= 2048 and b > 0
+            gs = GraphStructure(edge_index, n, gptr, b) if grouped else GraphStructure(edge_index, n)
+    return caches, x2, gs, gptr, b, c_in, h, n_body + n_head
+
+
+def _multi_run(plan):
+    """packs + job table (one launch, two beyond two sets), then ONE forward launch over b * k jobs.  Returns the k Q vectors
+    and the int32 node ranges' address."""
+    caches, x, gs, gptr, b, c_in, hidden, tot = plan
+    L = _lib.lib()
+    dev, n, k = x.device, x.shape[0], len(caches)
+    if x.dtype != torch.float32 or x.stride(1) != 1:
+        x = x.float().contiguous()
+    x_stride = x.stride(0) if n > 0 else c_in
+    gp = gs._ptrs
+    if gp is None:
+        gp = (gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.rowptr_t.data_ptr(), gs.col_t.data_ptr(), gs.invdeg.data_ptr(),
+              gptr.data_ptr(), gs.status.data_ptr())
+    key = ("multi", n, b, k)
+    sizes = caches[0].sizes.get(key)
+    if sizes is None:
+        w_bytes = (L.hexgnn_sage_stack_pack_bytes(c_in, hidden, tot) + 255) & ~255
+        total = L.hexgnn_qnet_multi_workspace_bytes(n, b, c_in, hidden, tot, k)
+        if total == 0:
+            raise _lib.HexGnnError("hexgnn_qnet_multi_workspace_bytes: unsupported configuration")
+        sizes = caches[0].sizes[key] = (w_bytes, total)
+    w_bytes, total = sizes
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)       # [pack 0 | .. | pack k-1 | jobs]
+    base = buf.data_ptr()
+    jobs = base + k * w_bytes
+    q = torch.empty((k, n), dtype=torch.float32, device=dev)
+    vp = C.c_void_p
+    wpack = (vp * k)(*[base + s * w_bytes for s in range(k)])
+    arr = lambda name: (vp * k)(*[C.cast(getattr(c, name), vp).value for c in caches])      # noqa: E731
+    stream = _stream()
+    _lib.check(L.hexgnn_qnet_forward_jobs(b, k, gp[5], jobs, c_in, hidden, tot, arr("wl"), arr("bl"), arr("wr"), wpack, stream),
+               "hexgnn_qnet_forward_jobs")
+    tails = [(vp * 6)(*c.tail) for c in caches]
+    tail = (vp * k)(*[C.cast(t, vp).value for t in tails])
+    qs = (vp * k)(*[q.data_ptr() + 4 * n * s for s in range(k)])
+    status = (vp * k)(*([gp[6]] * k))
+    _lib.check(L.hexgnn_qnet_forward_multi(n, b, k, c_in, hidden, tot, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, jobs,
+                                           wpack, tail, qs, status, stream), "hexgnn_qnet_forward_multi")
+    return [q[s] for s in range(k)], gp[5]
+
+
+def multi_forward(models, x: torch.Tensor, edge_index, graph_indices=None, ptr=None) -> List[torch.Tensor]:
+    """Q-values of 1..4 models over ONE batch: ``[m(x, edge_index, graph_indices, ptr) for m in models]`` under
+    ``torch.no_grad()``, bit for bit, from ONE forward launch whose b * k workgroups run largest graph first (a replay batch
+    has graphs of very different sizes, and the launch is otherwise bound by its largest graph per CU).  The CSR is built or
+    taken once (an attached ``_hex_csr`` as it is; a grouped batch takes the one-launch build); beyond it: the weight packs
+    with the job table, and the forward.  Forward only: nothing is saved for a backward, ``model._fca`` /
+    ``final_conv_acts`` and every ``.grad`` stay as they are.
+
+    Where the fused form does not apply -- graphs above 128 nodes, hidden > 112, ``set_math("f16x3")``,
+    ``set_fused(False)``, a noisy head, models of different shape -- every model's ordinary forward runs instead (same
+    values; that path does set ``final_conv_acts``).  CPU tensors raise ``HexGnnError``."""
+    models = list(models)
+    if not 1 <= len(models) <= MAX_SETS:
+        raise ValueError("multi_forward takes 1..%d models" % MAX_SETS)
+    _require_cuda(x, "x")
+    with torch.no_grad():
+        plan = _multi_plan(models, x, edge_index, graph_indices, ptr)
+        if plan is None:
+            return [m(x, edge_index, graph_indices, ptr) for m in models]
+        return _multi_run(plan)[0]
+
+
+def double_dqn_targets(online, target, x: torch.Tensor, edge_index, graph_indices, ptr, reward: torch.Tensor,
+                       done: torch.Tensor, gamma_n: float):
+    """Double-DQN targets of an update (the RainbowDQN step): ``(y, a2)`` with ``a2 = greedy_nodes(online(next states), ptr)``
+    and ``y = reward + gamma_n * target(next states)[a2] * (~done).float()``, bit for bit -- ``multi_forward([online,
+    target], ...)`` plus ONE launch that forms both (no torch arithmetic in between; no host sync when ``ptr`` and the
+    size hints of ``x`` are there).  Falls back to the plain sequence where ``multi_forward`` does."""
+    _require_cuda(x, "x")
+    with torch.no_grad():
+        plan = _multi_plan([online, target], x, edge_index, graph_indices, ptr)
+        b = int(ptr.numel()) - 1 if ptr is not None else -1
+        # (the target launch takes float32 rewards and boolean flags, one per graph: what the torch expression is then bit-equal to)
+        if plan is None or ptr is None or reward.dtype != torch.float32 or done.dtype != torch.bool \
+                or tuple(reward.shape) != (b,) or tuple(done.shape) != (b,) or reward.device != x.device \
+                or done.device != x.device:
+            q_on = online(x, edge_index, graph_indices, ptr)
+            q_tg = target(x, edge_index, graph_indices, ptr)
+            if ptr is None:
+                ptr = graph_ptr(graph_indices, None, x.shape[0], x.device)[0]
+            a2 = greedy_nodes(q_on, ptr)
+            return reward + gamma_n * q_tg[a2] * (~done).float(), a2
+        (q_on, q_tg), gptr = _multi_run(plan)
+        dev = x.device
+        r, d = reward.contiguous(), done.contiguous().view(torch.uint8)
+        y = torch.empty(b, dtype=torch.float32, device=dev)
+        a2 = torch.empty(b, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().hexgnn_dqn_targets(b, gptr, q_on.data_ptr(), q_tg.data_ptr(), r.data_ptr(), d.data_ptr(),
+                                                 float(gamma_n), y.data_ptr(), a2.data_ptr(), _stream()), "hexgnn_dqn_targets")
+        return y, a2

@@ -453,6 +453,43 @@ int hexgnn_qnet_backward_flat_td(int n, int b, int c_in, int hidden, int total_l
                                  int stages, int layer_lo, int layer_hi,
                                  const float* loss_part /*[b]*/, float* loss /*[1]*/, hexgnn_stream_t stream);
 
+/* ---- double-DQN targets: several weight sets over ONE batch in one load-balanced forward launch.  Entry points added to
+ *      ABI 6 (nothing existing changes).  The RainbowDQN update (README.md:5,7: the double-DQN step) runs the
+ *      online and the target network on the same next states, takes the per-graph argmax of the online Q over the non-terminal
+ *      nodes (the argmax of GN0/RainbowDQN/evaluate_elo.py:253-266) and forms y = r + gamma^n * Q_target[argmax] * (1 - done).
+ *      Here: one job table + the sets' weight packs (hexgnn_qnet_forward_jobs), ONE forward launch of b * k workgroups ordered
+ *      largest graph first (hexgnn_qnet_forward_multi), one target launch (hexgnn_dqn_targets).  Exact fp32 math, inference
+ *      only (no saved tensors, no activations); every set's q has the bits of hexgnn_qnet_forward (mode 0, math 0) with that
+ *      set's weights.  All k sets share (c_in, hidden, total_layers); hexgnn_qnet_supported must hold. ---- */
+#define HEXGNN_MAX_SETS 4
+/* jobs: [b * k] int32, job j = (graph << 2 | set) = (order[j / k], j % k), order = the graphs by DESCENDING node count, ties by
+ * ascending graph index (built on the device from gptr: no host sync). */
+size_t hexgnn_qnet_jobs_bytes(int b, int k);
+/* k weight packs (each hexgnn_sage_stack_pack_bytes rounded up to 256) followed by the job table (rounded up to 256): what a
+ * caller that keeps them in one buffer allocates.  0: unsupported configuration or bad argument. */
+size_t hexgnn_qnet_multi_workspace_bytes(int n, int b, int c_in, int hidden, int total_layers, int k);
+/* The job table of a batch and -- unless wl, bl, wr and wpack are all NULL -- the forward weight packs of the k sets:
+ * wl / bl / wr = HOST arrays [k] of HOST arrays [total_layers] of device pointers (hexgnn_qnet_forward's per set),
+ * wpack = HOST array [k] of device buffers of hexgnn_sage_stack_pack_bytes each (forward fragments and bias rows are written:
+ * the packs serve hexgnn_qnet_forward_multi only).  One launch for k <= 2, two beyond. */
+int hexgnn_qnet_forward_jobs(int b, int k, const int* gptr, int* jobs, int c_in, int hidden, int total_layers,
+                             const float* const* const* wl, const float* const* const* bl, const float* const* const* wr,
+                             void* const* wpack, hexgnn_stream_t stream);
+/* Q of every set over the batch: q[s][n] (HOST array [k] of distinct device buffers) from wpack[s] and the head-tail parameters
+ * tail[s] = HOST array of the six device pointers (lin_w, lin_b, v0_w, v0_b, v1_w, v1_b); status[s] (HOST array [k], entries may
+ * coincide) as hexgnn_qnet_forward's status word.  A graph above 128 nodes gets NaN rows in every set's q and status bit 2. */
+int hexgnn_qnet_forward_multi(int n, int b, int k, int c_in, int hidden, int total_layers, const int* gptr,
+                              const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
+                              const int* jobs, const void* const* wpack, const float* const* const* tail,
+                              float* const* q, int* const* status, hexgnn_stream_t stream);
+/* a2[g] = gptr[g] + 2 + argmax(q_sel[gptr[g]+2 : gptr[g+1]]) (first maximum, hexgnn_select_actions' comparison; int64, a global
+ * row), y[g] = reward[g] + (gamma_n * q_val[a2[g]]) * (done[g] ? 0 : 1) as three separately rounded fp32 operations: the bits of
+ * the torch expression `r + gamma_n * q_val[a2] * (~done).float()`, NaN propagation included.  A graph of two or fewer nodes has
+ * no non-terminal node: a2[g] = gptr[g] - 1 (hexgnn_select_actions' rank -1) and q_val's term counts as zero. */
+int hexgnn_dqn_targets(int b, const int* gptr, const float* q_sel /*[n]*/, const float* q_val /*[n]*/,
+                       const float* reward /*[b]*/, const uint8_t* done /*[b]*/, float gamma_n, float* y /*[b]*/,
+                       int64_t* a2 /*[b]*/, hexgnn_stream_t stream);
+
 /* ---- batched board-graph builder: num_envs lock-stepped Hex / Shannon node-switching games on the device.
  *      Replaces Hex_game / Node_switching_game (graph_game/graph_tools_games.py:20-29,
  *      graph_game/shannon_node_switching_game.py:80-205, graph_game/hex_board_game.py:214-233) as driven by

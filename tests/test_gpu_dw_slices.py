@@ -29,29 +29,12 @@ import torch
 
 from helpers import (DW_MODELS, batch_tensors, dw_case_list, dw_has_empty, dw_launches, model_args, sel_and_targets,
                      sharpen_)
+from helpers import PoisonedTorch as _PoisonedTorch
 
 pytestmark = pytest.mark.gpu
 
 CASES = {c[0]: c[1:] for c in dw_case_list()}
 _cache = {}
-
-
-class _PoisonedTorch:
-    """Stands in for the name ``torch`` inside gnn_hex_amd.ops while a test runs: ``empty`` fills device uint8 tensors (the
-    library's scratch) with one byte before the library sees them; everything else is torch's own."""
-
-    def __init__(self, byte):
-        self.byte, self.filled = byte, 0
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-    def empty(self, *args, **kwargs):
-        t = torch.empty(*args, **kwargs)
-        if t.dtype == torch.uint8 and t.is_cuda:
-            t.fill_(self.byte)
-            self.filled += 1
-        return t
 
 
 def _run(model, x, ei, batch, ptr, sel, tgt, gscale):

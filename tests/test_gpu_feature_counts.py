@@ -45,17 +45,21 @@ import copy
 import pytest
 import torch
 
-from helpers import (feature_batch, feature_loss, one_row_per_graph, qnet_hip_call, qnet_params, qnet_ref, qnet_ref_forward,
-                     sharpen_)
+from helpers import MARGIN, SEEDS, QnetCases
+from helpers import (abs_bound as _abs_bound, check_grads as _check_grads, column_shares as _column_shares, rel_bound as _rel_bound,
+                     same_bits as _same_bits, stack_forward as _stack_forward, stack_model as _stack_model,
+                     stack_params as _stack_params, stack_run as _stack_run)
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 2, 3, 17, 40, 128, 5]
 BODY, HEAD = 2, 2
-MARGIN = 2.0 ** -16
-SEEDS = 400
 PATHS = [("fused", "fp32"), ("fused", "f16x3"), ("layered", "fp32")]
-_batches, _oracles, _stacks = {}, {}, {}
+# the oracle of a Q-network case, its conditions, its weight seed and the parity rule: tests/helpers.py, shared with
+# tests/test_gpu_wide_parity.py
+_cases = QnetCases(SIZES, BODY, HEAD)
+_batch, _oracle, _check = _cases.batch, _cases.oracle, _cases.check
+_stacks = {}
 
 
 @pytest.fixture(params=PATHS, ids=["fused", "fused-f16x3", "layered"])
@@ -78,165 +82,12 @@ def fp32_path(request):
     ops.set_math("fp32")
 
 
-def _batch(c_in):
-    if c_in not in _batches:
-        x, ei, batch, ptr = feature_batch(SIZES, c_in, seed=100 + c_in)
-        _batches[c_in] = (x, ei, batch, ptr) + one_row_per_graph(ptr)
-    return _batches[c_in]
-
-
-# ---- the float64 oracle of a Q-network case, its conditions, its weight seed ------------------------------------------------
-
-def _ref_run(model, x, ei, batch, sel, tgt, mode):
-    model.zero_grad(set_to_none=True)
-    q, v = qnet_ref_forward(model, x, ei, batch, mode)
-    feature_loss(q, v, sel, tgt, mode).backward()
-    grads = [None if p.grad is None else p.grad.detach().clone() for _, p in qnet_params(model)]
-    return q.detach(), None if v is None else v.detach(), grads
-
-
-def _relu_margin(model, run):
-    """min |ReLU input| / rms over the SAGE layers of body and maker head and the value MLP's first layer, during run()."""
-    store, hooks = {}, []
-    for conv in list(model.gnn.convs) + list(model.maker_head.gnn.convs):
-        hooks.append(conv.register_forward_hook(lambda mod, inp, out: store.__setitem__(id(mod), out.detach())))
-    hooks.append(model.maker_head.value_head.layers[0].register_forward_hook(
-        lambda mod, inp, out: store.__setitem__("value", out.detach())))
-    try:
-        with torch.no_grad():
-            run()
-    finally:
-        for h in hooks:
-            h.remove()
-    return min((t.abs().min() / t.pow(2).mean().sqrt().clamp(min=1e-300)).item() for t in store.values())
-
-
-def _column_shares(g, c_in):
-    return [(g[:, k].norm() / g.norm()).item() for k in range(c_in)]
-
-
-def _conditions(ref64, c_in, mode):
-    """The four input conditions on the float64 oracle: (ok, text, q64, v64, g64)."""
-    x, ei, batch, ptr, sel, tgt = _batch(c_in)
-    x64, tgt64 = x.double(), tgt.double()
-    q64, v64, g64 = _ref_run(ref64, x64, ei, batch, sel, tgt64, mode)
-    sens = []
-    with torch.no_grad():
-        for k in range(c_in):
-            xz = x64.clone()
-            xz[:, k] = 0
-            sens.append((qnet_ref_forward(ref64, xz, ei, batch, mode)[0] - q64).abs().max().item())
-    shares = _column_shares(g64[0], c_in) + _column_shares(g64[2], c_in)
-    spread = (q64.max() - q64.min()).item()
-    gmax = min(g.abs().max().item() for g in g64 if g is not None)
-    margin = _relu_margin(ref64, lambda: qnet_ref_forward(ref64, x64, ei, batch, mode))
-    ok = min(sens) > 0.1 and min(shares) >= 0.02 and spread >= 0.5 and gmax >= 1e-2 and margin >= MARGIN
-    text = "Q sensitivity per feature %.3g..%.3g (> 0.1), layer-0 gradient column share %.3g..%.3g (>= 0.02), Q spread %.3g " \
-           "(>= 0.5), smallest |g|max %.3g (>= 1e-2), smallest |ReLU input| / rms %.3g (>= 2^-16)" \
-           % (min(sens), max(sens), min(shares), max(shares), spread, gmax, margin)
-    return ok, text, q64, v64, g64
-
-
-def _oracle(c_in, hidden, mode=0):
-    """fp32 and float64 oracle results of one case, once per session.  The weight seed is the first at which the conditions
-    hold in all three modes (the modes share their weights)."""
-    key = (c_in, hidden)
-    if key not in _oracles:
-        for seed in range(SEEDS):
-            ref64 = qnet_ref(c_in, hidden, BODY, HEAD, seed).double()
-            if all(_conditions(ref64, c_in, m)[0] for m in (0, 1, 2)):
-                break
-        else:
-            raise AssertionError("c_in %d hidden %d: no weight seed below %d meets the oracle conditions" % (c_in, hidden, SEEDS))
-        _oracles[key] = {"seed": seed}
-    ent = _oracles[key]
-    if mode not in ent:
-        x, ei, batch, ptr, sel, tgt = _batch(c_in)
-        ref = qnet_ref(c_in, hidden, BODY, HEAD, ent["seed"])
-        ref64 = copy.deepcopy(ref).double()
-        ok, text, q64, v64, g64 = _conditions(ref64, c_in, mode)
-        q32, v32, g32 = _ref_run(ref, x, ei, batch, sel, tgt, mode)
-        ent[mode] = dict(ref=ref, ok=ok, text=text, q64=q64, v64=v64, g64=g64, q32=q32, v32=v32, g32=g32)
-        print("oracle c_in %d hidden %d mode %d: weight seed %d; %s" % (c_in, hidden, mode, ent["seed"], text))
-    o = ent[mode]
-    assert o["ok"], "c_in %d hidden %d mode %d: %s" % (c_in, hidden, mode, o["text"])
-    return o
-
-
-# ---- the parity rule ------------------------------------------------------------------------------------------------------
-
-def _rel_bound(tag, name, g, g32, g64, floor=2e-3):
-    """||g - g64|| / ||g64|| <= max(3 x the fp32 oracle's own, floor); absolute 1e-6 for a vanishing tensor.  Returns the pair."""
-    g, g32 = g.detach().cpu().double(), g32.double()
-    assert torch.isfinite(g).all(), "%s %s: not finite" % (tag, name)
-    nrm = g64.norm().item()
-    if nrm < 1e-6:
-        assert (g - g64).abs().max().item() < 1e-6, "%s %s" % (tag, name)
-        return 0.0, 0.0
-    rel, rel32 = (g - g64).norm().item() / nrm, (g32 - g64).norm().item() / nrm
-    assert rel <= max(3.0 * rel32, floor), \
-        "%s %s: ||g - g64|| / ||g64|| = %.3g, the fp32 oracle's own %.3g, floor %g" % (tag, name, rel, rel32, floor)
-    return rel, rel32
-
-
-def _abs_bound(tag, name, y, y32, y64, const):
-    y = y.detach().cpu().double()
-    assert torch.isfinite(y).all(), "%s %s: not finite" % (tag, name)
-    e, e32 = (y - y64).abs().max().item(), (y32.double() - y64).abs().max().item()
-    assert e <= max(3.0 * e32, const), "%s: |%s - %s64| %.3g (fp32 oracle %.3g, constant %g)" % (tag, name, name, e, e32, const)
-    return e, e32
-
-
-def _check_grads(tag, names, grads, g32, g64, c_in, first=(0, 2)):
-    """Every gradient tensor, and every column k < c_in of the raw first layer's d_wl / d_wr (positions ``first``) against
-    that column's own float64 norm.  Returns the worst (ratio, oracle32's, name) of the tensors and of the columns."""
-    worst, worst_col = (0.0, 0.0, ""), (0.0, 0.0, "")
-    assert len(grads) == len(g64) == len(names)
-    for i, (name, g, a32, a64) in enumerate(zip(names, grads, g32, g64)):
-        if a64 is None:
-            assert g is None, name
-            continue
-        assert g is not None and tuple(g.shape) == tuple(a64.shape), name
-        r = _rel_bound(tag, name, g, a32, a64)
-        worst = max(worst, r + (name,))
-        if i in first:
-            assert a64.shape[1] == c_in
-            for k in range(c_in):
-                cname = "%s[:, %d]" % (name, k)
-                r = _rel_bound(tag, cname, g[:, k], a32[:, k], a64[:, k])
-                worst_col = max(worst_col, r + (cname,))
-    return worst, worst_col
-
-
-def _check(tag, o, q, out_v, grads, c_in, mode, split):
-    const = 8e-6 if split else 5e-6
-    eq = _abs_bound(tag, "Q", q, o["q32"], o["q64"], const)
-    ev = _abs_bound(tag, "out_v", out_v, o["v32"], o["v64"], const) if mode == 1 else None
-    names = [k for k, _ in qnet_params(o["ref"])]
-    worst, worst_col = _check_grads(tag, names, list(grads), o["g32"], o["g64"], c_in)
-    print("%s: |Q-Q64| %.3g (oracle32 %.3g)%s; worst gradient tensor %s rel %.3g (oracle32 %.3g); worst layer-0 column %s rel %.3g "
-          "(oracle32 %.3g)" % (tag, eq[0], eq[1], "" if ev is None else "; |v-v64| %.3g (oracle32 %.3g)" % ev, worst[2], worst[0],
-                               worst[1], worst_col[2], worst_col[0], worst_col[1]))
-
-
 def _dev(c_in):
-    x, ei, batch, ptr, sel, tgt = _batch(c_in)
-    return x.cuda(), ei.cuda(), ptr.cuda(), sel.cuda(), tgt.cuda()
-
-
-def _same_bits(tag, a, b):
-    assert torch.equal(a[0], b[0]), "%s: Q differs" % tag
-    assert (a[1] is None) == (b[1] is None) and (a[1] is None or torch.equal(a[1], b[1])), "%s: out_v differs" % tag
-    for i, (ga, gb) in enumerate(zip(a[2], b[2])):
-        assert (ga is None) == (gb is None) and (ga is None or torch.equal(ga, gb)), "%s: gradient %d differs" % (tag, i)
+    return _cases.dev(c_in)
 
 
 def _run_case(c_in, hidden, mode, path, x=None, deferred=False, gs=None, out=None):
-    o = _oracle(c_in, hidden, mode)
-    xd, eid, ptrd, seld, tgtd = _dev(c_in)
-    res = qnet_hip_call(o["ref"], xd if x is None else x, eid, ptrd, c_in, hidden, BODY, HEAD, mode, path[0] == "layered",
-                        deferred, seld, tgtd, gs=gs, out=out)
-    return o, res
+    return _cases.run_case(c_in, hidden, mode, path[0] == "layered", x=x, deferred=deferred, gs=gs, out=out)
 
 
 # ---- 1. feature counts ----------------------------------------------------------------------------------------------------
@@ -312,50 +163,6 @@ def test_tiny_widths(c_in, hidden, mode, path):
 
 
 # ---- 4. / 5. the layer-major stack through autograd -------------------------------------------------------------------------
-
-def _stack_model(kind, c_in, hidden, seed):
-    from oracle.model_ref import GraphSAGERef, SAGEConvRef
-    torch.manual_seed(seed)
-    if kind == "single":                # a bare SAGEConv(c_in, H): no ReLU behind it
-        m = torch.nn.Module()
-        m.convs, m.norms = torch.nn.ModuleList([SAGEConvRef(c_in, hidden)]), None
-    else:
-        m = GraphSAGERef(c_in, hidden, 3, norm=True if kind == "norm" else None)
-    return sharpen_(m)
-
-
-def _stack_forward(kind, m, x, ei, store=None):
-    """GraphSAGERef.forward / SAGEConvRef.forward; ``store`` receives every tensor a ReLU is applied to."""
-    if kind == "single":
-        return m.convs[0](x, ei)
-    for l, conv in enumerate(m.convs):
-        x = conv(x, ei)
-        if m.norms is not None:
-            x = m.norms[l](x)
-        if store is not None:
-            store.append(x.detach())
-        x = torch.relu(x)
-    return x
-
-
-def _stack_params(m):
-    names, ps = [], []
-    for l, conv in enumerate(m.convs):
-        names += ["convs.%d.lin_l.weight" % l, "convs.%d.lin_l.bias" % l, "convs.%d.lin_r.weight" % l]
-        ps += [conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight]
-        if m.norms is not None:
-            names += ["norms.%d.weight" % l, "norms.%d.bias" % l]
-            ps += [m.norms[l].weight, m.norms[l].bias]
-    return names, ps
-
-
-def _stack_run(kind, m, x, ei, r, want_dx):
-    m.zero_grad(set_to_none=True)
-    x = x.detach().clone().requires_grad_(want_dx)
-    y = _stack_forward(kind, m, x, ei)
-    ((y * r).sum() / y.shape[0]).backward()
-    return y.detach(), [p.grad.detach().clone() for p in _stack_params(m)[1]], x.grad.detach().clone() if want_dx else None
-
 
 def _stack_conditions(kind, m64, c_in, x64, ei, r64, padded):
     y64, g64, dx64 = _stack_run(kind, m64, x64, ei, r64, padded)

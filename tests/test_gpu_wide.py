@@ -2,7 +2,8 @@
 497-508); beyond the 128 columns the LDS-resident kernels are compiled for the same entry points run plain kernels (mean
 gather, exact-fp32 MFMA GEMM from L2, one wave per weight-gradient tile, simple head tails).  Q and every gradient against
 the oracle, board graphs and graphs above 128 nodes, all three output modes, the stand-alone modules, a width curriculum
-across the 128 boundary."""
+across the 128 boundary.  The float64 parity rule at every padded width, odd widths, the weight-gradient slice edges and the
+stand-alone head's backward: tests/test_gpu_wide_parity.py."""
 import pytest
 import torch
 

@@ -516,3 +516,234 @@ def stack_run(kind, m, x, ei, r, want_dx, scale=1.0):
     y = stack_forward(kind, m, x, ei)
     ((y * r).sum() * scale / y.shape[0]).backward()
     return y.detach(), [p.grad.detach().clone() for p in stack_params(m)[1]], x.grad.detach().clone() if want_dx else None
+
+
+# ---- the whole-batch norms under the float64 rule (tests/test_gpu_norm_parity.py) ------------------------------------------------
+
+NORM_EPS = 1e-5
+NORM_KINDS = ("layernorm", "colnorm", "colnorm-cached")
+DEAD_ZERO, DEAD_CONST, DEAD_MS1 = (3, 17), 5, 7          # columns of the "dead" variant
+
+
+def ref_layernorm(x, w, b, relu, pre=None):
+    """torch_geometric LayerNorm(mode="graph") without a batch vector (oracle/model_ref.py: LayerNormRef), ReLU behind it."""
+    xc = x - x.mean()
+    y = xc / (xc.std(unbiased=False) + NORM_EPS) * w + b
+    if pre is not None:
+        pre.append(y.detach())
+    return torch.relu(y) if relu else y
+
+
+def ref_colnorm(x, w, b, ms, relu, cache=None, pre=None):
+    """CachedGraphNorm without a batch vector (oracle/model_ref.py: CachedGraphNormRef): (y, [2, H] = mean | var as used)."""
+    if cache is None:
+        mean = x.mean(0, keepdim=True)
+        out = x - mean * ms
+        var = out.pow(2).mean(0, keepdim=True)
+    else:
+        mean, var = cache[0:1], cache[1:2]
+        out = x - mean * ms
+    y = w * out / (var + NORM_EPS).sqrt() + b
+    if pre is not None:
+        pre.append(y.detach())
+    return (torch.relu(y) if relu else y), torch.cat([mean, var]).detach()
+
+
+def norm_inputs(kind, n, hidden, variant, seed):
+    """x = randn * 3 + 1.5 [n, hidden], weight ~ U(0.5, 1.5), bias ~ 0.3 N(0, 1), mean_scale ~ U(0.6, 1.4), R ~ U(-1, 1), cached
+    statistics mean ~ 1.5 + 0.5 N(0, 1), var ~ 9 U(0.5, 1.5).  Variants: "shift" moves x to a mean of ten standard deviations;
+    "dead" (colnorm) zeroes columns 3 and 17, holds column 5 at 1.5 and sets mean_scale[7] = 1; "const" holds every element
+    at 1.5; "corr" adds (x - 1.5) / 3 to R, so that sum(dy * xhat) grows with the element count instead of its square root
+    and the statistics' own share of dx (k (x - mu) of the LayerNorm, B o of CachedGraphNorm) is of the size of dx."""
+    gen = torch.Generator().manual_seed(((seed * 1031 + n) * 257 + hidden) * 3 + NORM_KINDS.index(kind))
+    x = torch.randn(n, hidden, generator=gen) * 3.0 + 1.5
+    t = dict(w=torch.rand(hidden, generator=gen) + 0.5, b=torch.randn(hidden, generator=gen) * 0.3,
+             ms=torch.rand(hidden, generator=gen) * 0.8 + 0.6, r=torch.rand(n, hidden, generator=gen) * 2 - 1)
+    cache = torch.stack([1.5 + 0.5 * torch.randn(hidden, generator=gen), 9.0 * (torch.rand(hidden, generator=gen) + 0.5)])
+    if variant == "shift":
+        x, cache[0] = x + 28.5, cache[0] + 28.5
+    elif variant == "dead":
+        x[:, list(DEAD_ZERO)], x[:, DEAD_CONST], t["ms"][DEAD_MS1] = 0.0, 1.5, 1.0
+    elif variant == "const":
+        x[:] = 1.5
+    elif variant == "corr":
+        t["r"] = t["r"] + (x - 1.5) / 3.0
+    else:
+        assert variant == "plain", variant
+    t["x"] = x
+    if kind == "layernorm":
+        del t["ms"]
+    if kind == "colnorm-cached":
+        t["cache"] = cache
+    return t
+
+
+def norm_leaves(kind):
+    return ("x", "w", "b") if kind == "layernorm" else ("x", "w", "b", "ms")
+
+
+def norm_fwd_bwd(kind, inp, relu, dtype=torch.float32, device=None, pre=None):
+    """Forward and backward of sum(y * R): dict(y, stats, grads {x, w, b[, ms]}).  ``device``: through ops.graph_layernorm /
+    ops.graph_colnorm, and ``raw_dx`` is the gradient tensor as the backward returned it; else the torch expression on the
+    CPU in ``dtype``."""
+    leaves = {k: inp[k].to(dtype=dtype, device=device).clone().requires_grad_(True) for k in norm_leaves(kind)}
+    r = inp["r"].to(dtype=dtype, device=device)
+    cache = inp["cache"].to(dtype=dtype, device=device) if kind == "colnorm-cached" else None
+    raw = []
+    if device is not None:
+        from gnn_hex_amd import ops
+        leaves["x"].register_hook(raw.append)
+        if kind == "layernorm":
+            y, stats = ops.graph_layernorm(leaves["x"], leaves["w"], leaves["b"], NORM_EPS, relu), None
+        else:
+            y, stats = ops.graph_colnorm(leaves["x"], leaves["w"], leaves["b"], leaves["ms"], NORM_EPS, relu, cache)
+    elif kind == "layernorm":
+        y, stats = ref_layernorm(leaves["x"], leaves["w"], leaves["b"], relu, pre), None
+    else:
+        y, stats = ref_colnorm(leaves["x"], leaves["w"], leaves["b"], leaves["ms"], relu, cache, pre)
+    (y * r).sum().backward()
+    if device is not None:
+        torch.cuda.synchronize()
+    return dict(y=y.detach(), stats=None if stats is None else stats.detach(), grads={k: v.grad for k, v in leaves.items()},
+                raw_dx=raw[0] if raw else None)
+
+
+def relu_margin_of(tensors):
+    """min |t| / rms(t) over the tensors a ReLU is applied to (1 when there is none)."""
+    return min([(t.abs().min() / t.pow(2).mean().sqrt().clamp(min=1e-300)).item() for t in tensors if t.numel()] + [1.0])
+
+
+def norm_kernel_oracle(kind, n, hidden, variant, zero_grads=()):
+    """float64 and fp32 results of one kernel case, with and without the ReLU, at the first input seed below SEEDS whose float64
+    pre-ReLU tensor keeps MARGIN and whose gradient tensors (with and without the ReLU; not those of ``zero_grads``, which vanish
+    identically in this variant) all reach |g|max >= 1e-2."""
+    for seed in range(SEEDS):
+        inp = norm_inputs(kind, n, hidden, variant, seed)
+        pre = []
+        r64 = {False: norm_fwd_bwd(kind, inp, False, torch.float64, pre=pre)}
+        margin = relu_margin_of(pre)
+        if margin < MARGIN:
+            continue
+        r64[True] = norm_fwd_bwd(kind, inp, True, torch.float64)
+        gmax = min(g.abs().max().item() for relu in (False, True) for k, g in r64[relu]["grads"].items() if k not in zero_grads)
+        if gmax >= 1e-2:
+            break
+    else:
+        raise AssertionError("%s n %d hidden %d %s: no input seed below %d meets the oracle conditions" % (kind, n, hidden, variant, SEEDS))
+    for relu in (False, True):
+        for k in zero_grads:
+            assert float(r64[relu]["grads"][k].abs().max()) == 0.0, k
+    text = "smallest |ReLU input| / rms %.3g (>= 2^-16), smallest |g|max %.3g (>= 1e-2)" % (margin, gmax)
+    print("oracle %s n %d hidden %d %s: input seed %d; %s" % (kind, n, hidden, variant, seed, text))
+    r32 = {relu: norm_fwd_bwd(kind, inp, relu, torch.float32) for relu in (False, True)}
+    return dict(inp=inp, seed=seed, ok=margin >= MARGIN and gmax >= 1e-2, text=text, r64=r64, r32=r32)
+
+
+# ---- the norm stack (ops.sage_norm_stack) on batches of any size --------------------------------------------------------------
+
+def stack_conditions(kind, m64, c_in, x64, ei, r64, padded):
+    """The input conditions of a SAGE stack on its float64 oracle, with the loss scaled by the smallest power of two at which every
+    gradient tensor reaches |g|max >= 1e-2 (exact in every arithmetic, no relative figure changes): (ok, text, scale, y64, g64, dx64)."""
+    pre = []
+    with torch.no_grad():
+        stack_forward(kind, m64, x64, ei, pre)
+    margin = relu_margin_of(pre)
+    if margin < MARGIN:
+        return False, "smallest |ReLU input| / rms %.3g" % margin, 1.0, None, None, None
+    y64, g64, dx64 = stack_run(kind, m64, x64, ei, r64, padded)
+    scale, gmax = 1.0, min(g.abs().max().item() for g in g64 + ([dx64] if padded else []))
+    while gmax * scale < 1e-2 and scale < 2.0 ** 12:
+        scale *= 2.0
+    if scale != 1.0:
+        y64, g64, dx64 = stack_run(kind, m64, x64, ei, r64, padded, scale)
+    sens = []
+    with torch.no_grad():
+        for k in range(c_in if not padded else 0):
+            xz = x64.clone()
+            xz[:, k] = 0
+            sens.append((stack_forward(kind, m64, xz, ei) - y64).abs().max().item())
+    shares = [1.0] if padded else column_shares(g64[0], c_in) + column_shares(g64[2], c_in)
+    sens = sens or [1.0]
+    spread = (y64.max() - y64.min()).item()
+    ok = min(sens) > 0.1 and min(shares) >= 0.02 and spread >= 0.5 and gmax * scale >= 1e-2
+    text = "output sensitivity per feature %.3g..%.3g (> 0.1), layer-0 gradient column share %.3g..%.3g (>= 0.02), output spread " \
+           "%.3g (>= 0.5), smallest |g|max %.3g (>= 1e-2) at loss scale %g, smallest |ReLU input| / rms %.3g (>= 2^-16)" \
+           % (min(sens), max(sens), min(shares), max(shares), spread, gmax * scale, scale, margin)
+    return ok, text, scale, y64, g64, dx64
+
+
+def stack_oracle(kind, c_in, hidden, sizes):
+    """A three-layer stack on ``feature_batch(sizes, c_in, seed=100 + c_in)``, loss scale * sum(y * R) / n with R ~ U(-1, 1): the
+    float64 and fp32 oracle results at the first weight seed below SEEDS that meets ``stack_conditions``."""
+    import copy
+    x, ei, _, _ = feature_batch(sizes, c_in, seed=100 + c_in)
+    gen = torch.Generator().manual_seed(7)
+    r = torch.rand(x.shape[0], hidden, generator=gen) * 2 - 1
+    padded = c_in == hidden
+    for seed in range(SEEDS):
+        m = stack_model(kind, c_in, hidden, seed)
+        if kind == "norm":                  # non-trivial affine parameters (the default is weight 1, bias 0)
+            with torch.no_grad():
+                for nm in m.norms:
+                    nm.weight.add_(torch.randn(hidden) * 0.2)
+                    nm.bias.add_(torch.randn(hidden) * 0.2)
+        ok, text, scale, y64, g64, dx64 = stack_conditions(kind, copy.deepcopy(m).double(), c_in, x.double(), ei, r.double(), padded)
+        if ok:
+            break
+    else:
+        raise AssertionError("%s c_in %d hidden %d rows %d: no weight seed below %d meets the oracle conditions"
+                             % (kind, c_in, hidden, x.shape[0], SEEDS))
+    y32, g32, dx32 = stack_run(kind, m, x, ei, r, padded, scale)
+    print("oracle %s c_in %d hidden %d rows %d: weight seed %d; %s" % (kind, c_in, hidden, x.shape[0], seed, text))
+    return dict(m=m, x=x, ei=ei, r=r, scale=scale, seed=seed, ok=ok, text=text, y64=y64, g64=g64, dx64=dx64, y32=y32, g32=g32, dx32=dx32)
+
+
+# ---- the two model families with their norms ----------------------------------------------------------------------------------------
+
+def norm_model_ref(family, layers, hidden, seed, head_layers=2):
+    """The oracle's ``modern_two_headed`` (whole-batch LayerNorm) or ``two_headed`` (CachedGraphNorm) with norm=True, sharpened,
+    every norm's weight, bias and mean_scale moved by 0.2 N(0, 1)."""
+    from oracle.model_ref import get_pre_defined_ref
+    args = Namespace(num_layers=layers, hidden_channels=hidden, norm=True, noisy_dqn=False, noisy_sigma0=0.5, num_head_layers=head_layers)
+    torch.manual_seed(seed)
+    ref = sharpen_(get_pre_defined_ref(family, args))
+    with torch.no_grad():
+        for k, p in ref.named_parameters():
+            if "norm" in k:
+                p.add_(torch.randn(p.shape) * 0.2)
+    return ref
+
+
+def norm_model_hip(family, ref, layers, hidden, head_layers=2):
+    from gnn_hex_amd.models import get_pre_defined
+    args = Namespace(num_layers=layers, hidden_channels=hidden, norm=True, noisy_dqn=False, noisy_sigma0=0.5, num_head_layers=head_layers)
+    hip = get_pre_defined(family, args)
+    res = hip.load_state_dict(ref.state_dict())
+    assert not res.missing_keys and not res.unexpected_keys
+    return hip.cuda()
+
+
+def model_step(model, batch, sel, tgt, **kw):
+    """mse(Q[sel], tgt) forward and backward: (Q, final_conv_acts, {name: gradient or None})."""
+    model.zero_grad(set_to_none=True)
+    q = model(*batch, **kw)
+    torch.nn.functional.mse_loss(q.reshape(-1)[sel], tgt).backward()
+    return (q.detach().reshape(-1), model.final_conv_acts.detach().clone(),
+            {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in model.named_parameters()})
+
+
+def norm_model_margin(ref64, maker, run):
+    """min |ReLU input| / rms during run(): the outputs of the body's and the playing head's norms (the ReLU follows the norm; no
+    ReLU follows after_embed_norm) and of the value MLP's first layer where there is one."""
+    head = ref64.maker_head if maker else ref64.breaker_head
+    mods = list(ref64.gnn.norms) + list(head.gnn.norms)
+    if hasattr(head.value_head, "layers"):
+        mods.append(head.value_head.layers[0])
+    pre, hooks = [], [m.register_forward_hook(lambda mod, inp, out: pre.append(out.detach())) for m in mods]
+    try:
+        out = run()
+    finally:
+        for h in hooks:
+            h.remove()
+    assert len(pre) >= len(mods) - 1              # advantages_only runs no value MLP
+    return relu_margin_of(pre), out

@@ -27,6 +27,16 @@ static bool block_table_ok(int n, const int* block_starts, int num_blocks) {
     return num_blocks >= (n + 127) / 128 && num_blocks >= 1 && num_blocks <= kStackFlagWords;
 }
 
+// groups of a block table (hexgnn_sage_stack_*_groups): a HOST list of block indices, checked here before anything else runs:
+// 0 = group_starts[0] < group_starts[1] < ... < group_starts[num_groups] = num_blocks <= kStackFlagWords, over a table
+static bool block_groups_ok(const int* block_starts, int num_blocks, const int* group_starts, int num_groups) {
+    if (num_groups == 0) return true;
+    if (num_groups < 0 || !group_starts || !block_starts || num_blocks < 1 || num_blocks > kStackFlagWords) return false;
+    if (group_starts[0] != 0 || group_starts[num_groups] != num_blocks) return false;
+    for (int g = 0; g < num_groups; ++g) if (group_starts[g + 1] <= group_starts[g]) return false;
+    return true;
+}
+
 // the backward workspace of a plan: G (per-layer masked output gradients), the weight-gradient slabs, the raw first layer's partials
 struct BwdWs { float *G, *part, *part0; };
 static BwdWs carve_workspace(void* workspace, const BwdPlan& b) {
@@ -67,8 +77,8 @@ int hexgnn_sage_stack_forward(int n, int c_in, int hidden, int num_layers, const
                               const float* invdeg, const float* x, int x_stride, const float* const* wl,
                               const float* const* bl, const float* const* wr, void* wpack, float* acts,
                               void* saved, int need_backward, int flags, hexgnn_stream_t stream_) {
-    return hexgnn_sage_stack_forward_blocks(n, c_in, hidden, num_layers, rowptr, col, invdeg, x, x_stride, wl, bl, wr, wpack, acts,
-                                            saved, need_backward, flags, nullptr, 0, stream_);
+    return hexgnn_sage_stack_forward_groups(n, c_in, hidden, num_layers, rowptr, col, invdeg, x, x_stride, wl, bl, wr, wpack, acts,
+                                            saved, need_backward, flags, nullptr, 0, nullptr, 0, stream_);
 }
 
 int hexgnn_sage_stack_forward_blocks(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
@@ -76,8 +86,18 @@ int hexgnn_sage_stack_forward_blocks(int n, int c_in, int hidden, int num_layers
                                      const float* const* bl, const float* const* wr, void* wpack, float* acts,
                                      void* saved, int need_backward, int flags, const int* block_starts, int num_blocks,
                                      hexgnn_stream_t stream_) {
+    return hexgnn_sage_stack_forward_groups(n, c_in, hidden, num_layers, rowptr, col, invdeg, x, x_stride, wl, bl, wr, wpack, acts,
+                                            saved, need_backward, flags, block_starts, num_blocks, nullptr, 0, stream_);
+}
+
+int hexgnn_sage_stack_forward_groups(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
+                                     const float* invdeg, const float* x, int x_stride, const float* const* wl,
+                                     const float* const* bl, const float* const* wr, void* wpack, float* acts,
+                                     void* saved, int need_backward, int flags, const int* block_starts, int num_blocks,
+                                     const int* group_starts, int num_groups, hexgnn_stream_t stream_) {
     hipStream_t st = (hipStream_t)stream_;
     StackPlan p;
+    if (!block_groups_ok(block_starts, num_blocks, group_starts, num_groups)) return HEXGNN_EINVAL;
     if (n < 0 || (flags & ~HEXGNN_SAGE_LINEAR_LAST)) return HEXGNN_EINVAL;
     if (n > 0 && !block_table_ok(n, block_starts, num_blocks)) return HEXGNN_EINVAL;
     if (hidden > 16 * kMaxNT) {        // 129..256: the plain kernels of wide.hip (always materialise the aggregates in `saved`)
@@ -103,7 +123,9 @@ int hexgnn_sage_stack_forward_blocks(int n, int c_in, int hidden, int num_layers
     rc = stack_status(true);
     if (rc != HEXGNN_OK) return rc;
     const int fh = p.small_first ? 1 : 0;
-    const bool one_launch = choose_stack_launch(n, &block_starts, &num_blocks, p.nt, p.L - fh, st, false);
+    // groups whose largest fits the resident-workgroup budget run one launch each; otherwise they are ignored
+    const bool grouped = num_groups > 0 && stack_groups_fit(n, group_starts, num_groups, p.nt, p.L - fh, st, false);
+    const bool one_launch = grouped || choose_stack_launch(n, &block_starts, &num_blocks, p.nt, p.L - fh, st, false);
     for (int l = 0; l < p.L; ++l) {
         float* y = acts + slab * l;
         const float* bias = (const float*)(wp + p.bias_off[l]);
@@ -124,7 +146,10 @@ int hexgnn_sage_stack_forward_blocks(int n, int c_in, int hidden, int num_layers
             a.astride = p.L - l > 1 ? p.agg_off[l + 1] - p.agg_off[l] : 0;
             a.flags = reinterpret_cast<unsigned*>(wp + p.flag_off);
             a.bstart = block_starts; a.nblocks = num_blocks;
-            rc = launch_stack(false, p.nt, a, st);
+            for (int g = 0; g < (grouped ? num_groups : 1) && rc == HEXGNN_OK; ++g) {
+                if (grouped) { a.gbase = group_starts[g]; a.gcount = group_starts[g + 1] - group_starts[g]; }
+                rc = launch_stack(false, p.nt, a, st, !grouped || g + 1 == num_groups);
+            }
             if (rc != HEXGNN_OK) return rc;
             break;
         } else {
@@ -162,9 +187,9 @@ int hexgnn_sage_stack_backward_tap(int n, int c_in, int hidden, int num_layers, 
                                    const float* dy, float* dx, float* const* d_wl, float* const* d_bl,
                                    float* const* d_wr, void* workspace, size_t workspace_bytes, int flags,
                                    int tap_layer, float* tap_out, hexgnn_stream_t stream_) {
-    return hexgnn_sage_stack_backward_blocks(n, c_in, hidden, num_layers, rowptr, col, rowptr_t, col_t, invdeg, x, x_stride, acts,
+    return hexgnn_sage_stack_backward_groups(n, c_in, hidden, num_layers, rowptr, col, rowptr_t, col_t, invdeg, x, x_stride, acts,
                                              saved, wpack, dy, dx, d_wl, d_bl, d_wr, workspace, workspace_bytes, flags,
-                                             tap_layer, tap_out, nullptr, 0, stream_);
+                                             tap_layer, tap_out, nullptr, 0, nullptr, 0, stream_);
 }
 
 int hexgnn_sage_stack_backward_blocks(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
@@ -174,9 +199,22 @@ int hexgnn_sage_stack_backward_blocks(int n, int c_in, int hidden, int num_layer
                                       float* const* d_wr, void* workspace, size_t workspace_bytes, int flags,
                                       int tap_layer, float* tap_out, const int* block_starts, int num_blocks,
                                       hexgnn_stream_t stream_) {
+    return hexgnn_sage_stack_backward_groups(n, c_in, hidden, num_layers, rowptr, col, rowptr_t, col_t, invdeg, x, x_stride, acts,
+                                             saved, wpack, dy, dx, d_wl, d_bl, d_wr, workspace, workspace_bytes, flags,
+                                             tap_layer, tap_out, block_starts, num_blocks, nullptr, 0, stream_);
+}
+
+int hexgnn_sage_stack_backward_groups(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
+                                      const int* rowptr_t, const int* col_t, const float* invdeg, const float* x,
+                                      int x_stride, const float* acts, const void* saved, const void* wpack,
+                                      const float* dy, float* dx, float* const* d_wl, float* const* d_bl,
+                                      float* const* d_wr, void* workspace, size_t workspace_bytes, int flags,
+                                      int tap_layer, float* tap_out, const int* block_starts, int num_blocks,
+                                      const int* group_starts, int num_groups, hexgnn_stream_t stream_) {
     (void)rowptr; (void)col;
     hipStream_t st = (hipStream_t)stream_;
     StackPlan p;
+    if (!block_groups_ok(block_starts, num_blocks, group_starts, num_groups)) return HEXGNN_EINVAL;
     if (n < 0 || (flags & ~(HEXGNN_SAGE_LINEAR_LAST | HEXGNN_SAGE_DY_IN_PLACE))) return HEXGNN_EINVAL;
     if (n > 0 && !block_table_ok(n, block_starts, num_blocks)) return HEXGNN_EINVAL;
     if ((flags & HEXGNN_SAGE_DY_IN_PLACE) && (flags & HEXGNN_SAGE_LINEAR_LAST)) return HEXGNN_EINVAL;
@@ -221,7 +259,8 @@ int hexgnn_sage_stack_backward_blocks(int n, int c_in, int hidden, int num_layer
     rc = stack_status(true);
     if (rc != HEXGNN_OK) return rc;
     const int lo = (first_hidden == 0 && !dx) ? 1 : first_hidden;        // last layer whose data gradient is wanted
-    const bool one_launch = choose_stack_launch(n, &block_starts, &num_blocks, p.nt, p.L - lo, st, true);
+    const bool grouped = num_groups > 0 && stack_groups_fit(n, group_starts, num_groups, p.nt, p.L - lo, st, true);
+    const bool one_launch = grouped || choose_stack_launch(n, &block_starts, &num_blocks, p.nt, p.L - lo, st, true);
     if (one_launch) {
         StackKArgs a{};
         a.n = n; a.l_first = p.L - 1; a.n_layers = p.L - lo;
@@ -232,7 +271,10 @@ int hexgnn_sage_stack_backward_blocks(int n, int c_in, int hidden, int num_layer
         a.w0 = wp + p.bwd_off[p.L - 1]; a.wstride = p.bwd_off[p.L - 1] - p.bwd_off[p.L - 2];
         a.flags = reinterpret_cast<unsigned*>(const_cast<char*>(wp) + p.flag_off) + kStackFlagWords;
         a.bstart = block_starts; a.nblocks = num_blocks;
-        rc = launch_stack(true, p.nt, a, st);
+        for (int g = 0; g < (grouped ? num_groups : 1) && rc == HEXGNN_OK; ++g) {
+            if (grouped) { a.gbase = group_starts[g]; a.gcount = group_starts[g + 1] - group_starts[g]; }
+            rc = launch_stack(true, p.nt, a, st, !grouped || g + 1 == num_groups);
+        }
         if (rc != HEXGNN_OK) return rc;
     }
     for (int l = p.L - 1; l >= first_hidden && !one_launch; --l) {

@@ -36,6 +36,8 @@ struct StackKArgs {
     unsigned* flags;                   // [blocks] progress counters, zero at launch
     const int* bstart;                 // null: block b = rows [128 b, 128 b + 128); else [nblocks + 1] row offsets (block b =
     int nblocks;                       //   rows [bstart[b], bstart[b + 1]), at most 128 each, a partition of [0, n))
+    int gbase, gcount;                 // the launch runs blocks [gbase, gbase + gcount) of the table, one per workgroup (a group of
+                                       //   whole graphs: hexgnn_sage_stack_*_groups); gcount == 0: the whole table, filled by launch_stack
     int* status;
     unsigned skew;                     // test aid (HEXGNN_STACK_SKEW): != 0 delays every block by a pseudo-random time per layer;
 };                                     // 0xDE00bbbb: block bbbb never publishes its progress (its readers must time out)
@@ -45,7 +47,11 @@ int stack_status(bool clear);
 // true: the hidden layers run as ONE launch (launch_stack), false: per layer.  A block table whose blocks do not fit the
 // resident-workgroup budget while the default 128-row blocks do is dropped (*block_starts = null, *num_blocks = 0).
 bool choose_stack_launch(int n, const int** block_starts, int* num_blocks, int nt, int layers, hipStream_t st, bool bwd);
-int launch_stack(bool bwd, int nt, StackKArgs a, hipStream_t st);      // fills a.status and a.skew
+// groups of a block table (host list [num_groups + 1] of block indices): true when the largest group passes the same
+// residency test -- the groups then run one launch_stack each, in order, on one stream
+bool stack_groups_fit(int n, const int* group_starts, int num_groups, int nt, int layers, hipStream_t st, bool bwd);
+// fills a.status and a.skew; `last`: the launch that the in-flight event of this call is recorded behind
+int launch_stack(bool bwd, int nt, StackKArgs a, hipStream_t st, bool last = true);
 
 // ---- sage_dw.hip ----------------------------------------------------------------------------------------------------------
 // out = dxs + sum_{j in T(i)} dagg_j (dagg null: none), masked by ymask > 0 (null: unmasked)

@@ -86,14 +86,17 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
     // the block's rows.  With a block table (graph-aligned blocks: hexgnn_sage_stack_forward_blocks) the range comes from the
     // table and is checked HERE (the table is device data the host never saw): a range that is not a piece of a partition of
     // [0, n) in pieces of at most 128 rows makes the block empty and sets HEXGNN_EINVAL in the status word
-    int brow0 = blockIdx.x * 128, bcnt = min(128, n - brow0);
+    // (a launch runs the blocks [gbase, gbase + gridDim.x) of a table of nblocks: a group of whole graphs.  Block indices,
+    // progress counters and rows are those of the WHOLE table; only the grid is the group's)
+    const int blk = __builtin_amdgcn_readfirstlane((int)blockIdx.x + a.gbase);
+    const int nbk = a.nblocks;
+    int brow0 = blk * 128, bcnt = min(128, n - brow0);
     if (a.bstart) {
-        const int nbk = (int)gridDim.x;
-        brow0 = __builtin_amdgcn_readfirstlane(a.bstart[blockIdx.x]);
-        const int bend = __builtin_amdgcn_readfirstlane(a.bstart[blockIdx.x + 1]);
+        brow0 = __builtin_amdgcn_readfirstlane(a.bstart[blk]);
+        const int bend = __builtin_amdgcn_readfirstlane(a.bstart[blk + 1]);
         bcnt = bend - brow0;
-        const bool ok = brow0 >= 0 && bcnt >= 0 && bcnt <= 128 && bend <= n && (blockIdx.x != 0 || brow0 == 0) &&
-                        ((int)blockIdx.x != nbk - 1 || bend == n);
+        const bool ok = brow0 >= 0 && bcnt >= 0 && bcnt <= 128 && bend <= n && (blk != 0 || brow0 == 0) &&
+                        (blk != nbk - 1 || bend == n);
         if (!ok) {
             if (a.status && tid == 0) *a.status = HEXGNN_EINVAL;
             brow0 = 0; bcnt = 0;          // (stays in the protocol: a reader of the rows it should have owned must not time out)
@@ -195,7 +198,6 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
     constexpr bool kNs = BWD && !RL::on;          // per-slot factors only where every neighbour comes from global memory
     float ns[kNs ? kEll : 1];
     const __amdgpu_buffer_rsrc_t ir_ = slab_rsrc(a.invdeg);
-    const int blk = blockIdx.x;
     int dlo = blk, dhi = blk;                     // blocks this wave reads rows from
     {
         int nid[kEll];
@@ -212,7 +214,6 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
         // registers -- a graph cut by a block boundary continues in the next block --, anything else by bisection (every index
         // stays inside the table whatever it holds)
         int pb0 = 0, nb1 = 0, nb2 = 0;
-        const int nbk = (int)gridDim.x;
         if (a.bstart) {
             pb0 = a.bstart[blk > 0 ? blk - 1 : 0];
             nb1 = a.bstart[blk + 1];
@@ -272,6 +273,15 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
     wmax = __builtin_amdgcn_readfirstlane(wmax);
     dlo = __builtin_amdgcn_readfirstlane(dlo);
     dhi = __builtin_amdgcn_readfirstlane(dhi);
+    // a group must hold whole graphs: a wave that reads rows of a block OUTSIDE this launch's range (a cut that an edge
+    // crosses -- that block ran in an earlier launch or runs in a later one) must not wait for it.  The wait is clamped to the
+    // group, the status word says HEXGNN_EINVAL (written at the kernel's end, where the store's registers cost no spill) and
+    // everything the wave stores is NaN, as after a timed-out wait
+    const int glo = a.gbase, ghi = a.gbase + a.gcount - 1;          // (gcount: the grid, from the argument block)
+    const bool crossed = dlo < glo || dhi > ghi;                    // wave-uniform
+    if (crossed) {
+        dlo = max(dlo, glo); dhi = min(dhi, ghi);
+    }
     // a row with more than kEll neighbours finishes its sum from GLOBAL memory, rows of its own block included: such a wave
     // also waits for its own block's counter (the other waves' stores acknowledged)
     const bool longrow = __ballot(deg > kEll) != 0ull;
@@ -299,7 +309,7 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
             if ((c & 7u) == 7u) __hip_atomic_fetch_add(a.flags + blk, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
-    bool dead = false;                 // wave-uniform: a wait of this wave timed out -> everything it stores from now on is NaN
+    bool dead = crossed;               // wave-uniform: a wait of this wave timed out -> everything it stores from now on is NaN
     const f32x4 kNan4 = f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
     const float* xin = a.in0;
     for (int it = 0; it < a.n_layers; ++it) {
@@ -601,6 +611,7 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
         if (tid == 0 && !muted) __hip_atomic_fetch_add(a.flags + blk, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         xin = out;
     }
+    if (crossed && a.status && lane == 0) *a.status = HEXGNN_EINVAL;
 }
 
 template <int NT>
@@ -734,9 +745,20 @@ bool choose_stack_launch(int n, const int** block_starts, int* num_blocks, int n
     *block_starts = nullptr; *num_blocks = 0;     // the table's blocks do not fit the resident-workgroup budget, the default ones do
     return true;
 }
+// Groups of a table: graphs are independent, so a range of blocks that holds whole graphs never waits for a block outside it
+// and can be a launch of its own.  The residency test is the one above with the LARGEST group in the place of the table (the
+// launches of a call follow each other on one stream: never two of them resident at once).
+bool stack_groups_fit(int n, const int* group_starts, int num_groups, int nt, int layers, hipStream_t st, bool bwd) {
+    int largest = 0;
+    for (int g = 0; g < num_groups; ++g) {
+        const int c = group_starts[g + 1] - group_starts[g];
+        if (c > largest) largest = c;
+    }
+    return largest > 0 && persist_fits(n, largest, nt, layers, st, bwd);
+}
 
 template <int NT, bool BWD>
-static void launch_stack_nt(StackKArgs a, hipStream_t st) {
+static void launch_stack_nt(StackKArgs a, hipStream_t st, bool last) {
     static bool once = [] {
         const void* f = BWD ? reinterpret_cast<const void*>(&sage_stack_bwd_kernel<NT>)
                             : reinterpret_cast<const void*>(&sage_stack_fwd_kernel<NT>);
@@ -748,15 +770,17 @@ static void launch_stack_nt(StackKArgs a, hipStream_t st) {
     a.skew = stack_skew();
     {
         KernelTimer kt(BWD ? HEXGNN_K_SAGE_BWD : HEXGNN_K_SAGE_FWD, st);
-        const int grid = a.bstart ? a.nblocks : (a.n + 127) / 128;
+        if (!a.bstart) a.nblocks = (a.n + 127) / 128;
+        if (a.gcount <= 0) { a.gbase = 0; a.gcount = a.nblocks; }
+        const int grid = a.gcount;
         if constexpr (NT >= 3 && BWD) sage_stack_bwd_kernel<NT><<<grid, 512, stack_lds_bytes<NT>(), st>>>(a);
         else if constexpr (NT >= 3) sage_stack_fwd_kernel<NT><<<grid, 512, stack_lds_bytes<NT>(), st>>>(a);
     }
-    note_stack_launch(st);
+    if (last) note_stack_launch(st);
 }
-int launch_stack(bool bwd, int nt, StackKArgs a, hipStream_t st) {
-    if (bwd) { HEXGNN_NT_SWITCH(nt, (launch_stack_nt<NT_, true>(a, st))); }
-    else { HEXGNN_NT_SWITCH(nt, (launch_stack_nt<NT_, false>(a, st))); }
+int launch_stack(bool bwd, int nt, StackKArgs a, hipStream_t st, bool last) {
+    if (bwd) { HEXGNN_NT_SWITCH(nt, (launch_stack_nt<NT_, true>(a, st, last))); }
+    else { HEXGNN_NT_SWITCH(nt, (launch_stack_nt<NT_, false>(a, st, last))); }
     return HEXGNN_OK;
 }
 

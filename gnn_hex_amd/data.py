@@ -15,6 +15,7 @@ import torch
 
 
 BLOCK_ROWS = 128         # rows of one workgroup of the layer-major kernels (gnn_hex_amd/csrc/sage_layer.hip, sage_stack.hip)
+MAX_TABLE_BLOCKS = 512   # blocks of one table (kStackFlagWords: the progress counters of a call, indexed by block)
 
 
 def blocks_for_order(sizes: List[int], block: int = BLOCK_ROWS, head: int = 64) -> List[int]:
@@ -83,40 +84,93 @@ def pack_order(sizes: List[int], block: int = BLOCK_ROWS, max_blocks: Optional[i
     sizes = [int(v) for v in sizes]
     if max_blocks is not None and -(-sum(sizes) // block) > max_blocks:
         return list(range(n_graphs)), None           # (not even full blocks fit the budget: nothing to pack for)
-    big = sorted((g for g in range(n_graphs) if sizes[g] > block), key=lambda g: (-sizes[g], g))
-    small = sorted((g for g in range(n_graphs) if sizes[g] <= block), key=lambda g: (-sizes[g], g))
-
-    def build(hd: int):
-        bins = []            # [free rows, big graph whose tail opens the bin or None, small graphs]
-        order = []
-        for g in big:
-            if hd:
-                order.append(g)
-            else:
-                tail = sizes[g] % block
-                bins.append([block - tail if tail else 0, g, []])
-        for g in small:
-            best = None
-            for b in bins:                       # best fit: the fullest bin that still takes the graph
-                if b[0] >= sizes[g] and (best is None or b[0] < best[0]):
-                    best = b
-            if best is None:
-                best = [block, None, []]
-                bins.append(best)
-            best[0] -= sizes[g]
-            best[2].append(g)
-        for _free, bg, members in bins:
-            if bg is not None:
-                order.append(bg)
-            order.extend(members)
-        return order, blocks_for_order([sizes[g] for g in order], block, hd)
-
-    order, starts = build(head if head and head > 0 else 0)
+    order, starts = _pack_layout(sizes, block, head if head and head > 0 else 0)
     if max_blocks is not None and len(starts) - 1 > max_blocks:
-        order, starts = build(0)
+        order, starts = _pack_layout(sizes, block, 0)
         if len(starts) - 1 > max_blocks:
             return list(range(n_graphs)), None
     return order, starts
+
+
+def _pack_layout(sizes: List[int], block: int, hd: int):
+    """One of ``pack_order``'s two layouts: ``hd`` > 0 the head-block form, 0 the form with ``block``-row pieces."""
+    n_graphs = len(sizes)
+    big = sorted((g for g in range(n_graphs) if sizes[g] > block), key=lambda g: (-sizes[g], g))
+    small = sorted((g for g in range(n_graphs) if sizes[g] <= block), key=lambda g: (-sizes[g], g))
+    bins = []            # [free rows, big graph whose tail opens the bin or None, small graphs]
+    order = []
+    for g in big:
+        if hd:
+            order.append(g)
+        else:
+            tail = sizes[g] % block
+            bins.append([block - tail if tail else 0, g, []])
+    for g in small:
+        best = None
+        for b in bins:                       # best fit: the fullest bin that still takes the graph
+            if b[0] >= sizes[g] and (best is None or b[0] < best[0]):
+                best = b
+        if best is None:
+            best = [block, None, []]
+            bins.append(best)
+        best[0] -= sizes[g]
+        best[2].append(g)
+    for _free, bg, members in bins:
+        if bg is not None:
+            order.append(bg)
+        order.extend(members)
+    return order, blocks_for_order([sizes[g] for g in order], block, hd)
+
+
+def block_groups(sizes_in_order: List[int], starts: Optional[List[int]], max_blocks: int) -> Optional[List[int]]:
+    """Groups of a block table that has more blocks than can be resident at once (``hexgnn_sage_stack_*_groups``): block
+    indices ``[0, ..., nb]``, every group at most ``max_blocks`` blocks, a cut only where a block start is also a graph start --
+    a group then holds whole graphs and none of its blocks waits for a block of another group, so each group is one launch.
+    Greedy, every group up to the farthest cut it can reach: the fewest groups.  ``[0, nb]`` when the table fits as it is;
+    ``None`` when a stretch between two cuts is longer than ``max_blocks`` (Hex-19: four blocks per graph against a budget of
+    two) or the table has more than ``MAX_TABLE_BLOCKS`` blocks."""
+    if starts is None or len(starts) < 2 or max_blocks is None or int(max_blocks) < 1:
+        return None
+    nb = len(starts) - 1
+    if nb > MAX_TABLE_BLOCKS:
+        return None
+    graph_rows, row = {0}, 0
+    for sz in sizes_in_order:
+        row += int(sz)
+        graph_rows.add(row)
+    if row != starts[-1]:
+        return None
+    cuts = [i for i in range(nb + 1) if starts[i] in graph_rows and (i == 0 or starts[i] > starts[i - 1] or i == nb)]
+    groups, k = [0], 0
+    while groups[-1] < nb:
+        far = None
+        while k < len(cuts) and cuts[k] - groups[-1] <= max_blocks:
+            if cuts[k] > groups[-1]:
+                far = cuts[k]
+            k += 1
+        if far is None:
+            return None
+        groups.append(far)
+    return groups
+
+
+def pack_groups(sizes: List[int], block: int = BLOCK_ROWS, max_blocks: Optional[int] = None, head: int = 64):
+    """``pack_order`` for batches whose table exceeds ``max_blocks``: ``(order, starts, groups)`` with ``groups`` as
+    ``block_groups`` gives them.  Both layouts of ``pack_order`` are tried (the head-block form and the one with ``block``-row
+    pieces) and the one with fewer groups is kept, the head form on a tie.  ``(identity, None, None)`` when neither can be cut
+    into groups.  ``max_blocks = None``: no budget but the table's own limit."""
+    n_graphs = len(sizes)
+    if n_graphs == 0:
+        return [], None, None
+    sizes = [int(v) for v in sizes]
+    budget = MAX_TABLE_BLOCKS if max_blocks is None else int(max_blocks)
+    best = None
+    for hd in ([head, 0] if head and head > 0 else [0]):
+        order, starts = _pack_layout(sizes, block, hd)
+        groups = block_groups([sizes[g] for g in order], starts, budget)
+        if groups is not None and (best is None or len(groups) < len(best[2])):
+            best = (order, starts, groups)
+    return best if best is not None else (list(range(n_graphs)), None, None)
 
 
 def attach_blocks(edge_index: torch.Tensor, starts: Optional[List[int]]) -> None:
@@ -125,6 +179,15 @@ def attach_blocks(edge_index: torch.Tensor, starts: Optional[List[int]]) -> None
     if starts is None or len(starts) < 2:
         return
     edge_index._hex_blocks = (torch.tensor(starts, dtype=torch.int32).to(edge_index.device), len(starts) - 1)
+
+
+def attach_block_groups(edge_index: torch.Tensor, starts: Optional[List[int]], groups: Optional[List[int]]) -> None:
+    """Attach a row-block table that runs in groups (``pack_groups`` / ``block_groups``) to a collated batch's ``edge_index``.
+    Kept apart from ``_hex_blocks``: that attribute promises a table within the budget."""
+    if starts is None or groups is None or len(starts) < 2 or len(groups) < 2:
+        return
+    edge_index._hex_block_groups = (torch.tensor(starts, dtype=torch.int32).to(edge_index.device), len(starts) - 1,
+                                    tuple(int(g) for g in groups))
 
 
 class Data:
@@ -175,27 +238,37 @@ class Batch(Data):
     """``Batch.from_data_list`` + ``batch`` / ``ptr`` / ``num_graphs``."""
 
     @classmethod
-    def from_data_list(cls, data_list: List[Data], pack: bool = False, max_blocks: Optional[int] = None) -> "Batch":
+    def from_data_list(cls, data_list: List[Data], pack: bool = False, max_blocks: Optional[int] = None,
+                       groups: bool = False) -> "Batch":
         """``pack=True`` (graphs above 128 nodes in the batch -- Hex-12 and larger, mixed sizes): the graphs are collated in
         ``pack_order`` order with its row-block table attached, and ``batch.order`` (LongTensor [num_graphs]) says which entry
         of ``data_list`` sits at each position -- per-graph quantities of the caller (actions, targets, weights) go through
         ``t[batch.order]``.  Without ``pack`` the order is the caller's and the table follows its graph boundaries when that fits
         (``blocks_for_order``).  ``max_blocks``: see ``pack_order`` (default: ``ops.stack_block_budget``, the CUs the one-launch
-        kernels may fill)."""
+        kernels may fill).
+
+        ``groups=True``: a batch with more rows than ``max_blocks`` blocks of 128 (a uniform Hex-13 batch of 256 graphs: it
+        runs one launch per layer otherwise) carries its table in groups of whole graphs (``pack_groups`` / ``block_groups``:
+        ``edge_index._hex_block_groups``) and runs one launch per group.  Off by default, and never used where the default
+        128-row blocks fit the budget: one launch over those was measured faster than two over aligned blocks."""
         if hasattr(data_list, "to_batch"):      # an Env_manager observation is already batched on the device
             return data_list.to_batch()
         out = cls()
         if len(data_list) == 0:
             raise ValueError("empty data_list")
-        starts = None
+        want_groups, starts, groups = bool(groups), None, None
         dev0 = data_list[0].x.device
         sizes = [int(d.x.shape[0]) for d in data_list]
         if dev0.type == "cuda" and max(sizes) > BLOCK_ROWS:
             if max_blocks is None:
                 from . import ops
                 max_blocks = ops.stack_block_budget(dev0)
+            # (groups: only where not even the default 128-row blocks can be resident at once)
+            want_groups = want_groups and -(-sum(sizes) // BLOCK_ROWS) > max_blocks
             if pack:
                 order, starts = pack_order(sizes, BLOCK_ROWS, max_blocks)
+                if starts is None and want_groups:      # whole graphs in groups, a launch each
+                    order, starts, groups = pack_groups(sizes, BLOCK_ROWS, max_blocks)
                 data_list = [data_list[g] for g in order]
                 out.order = torch.tensor(order, dtype=torch.long)
             elif -(-sum(sizes) // BLOCK_ROWS) <= max_blocks:
@@ -203,6 +276,11 @@ class Batch(Data):
                 # shorter blocks than a packing needs: the Hex-5..13 round robin takes 254 of 256)
                 starts = blocks_for_order(sizes)
                 if len(starts) - 1 > max_blocks:
+                    starts = None
+            elif want_groups:
+                starts = blocks_for_order(sizes)
+                groups = block_groups(sizes, starts, max_blocks)
+                if groups is None:
                     starts = None
         elif pack:
             out.order = torch.arange(len(sizes))
@@ -236,7 +314,10 @@ class Batch(Data):
         ecnt = torch.tensor([0] + [int(d.edge_index.shape[1]) for d in data_list], dtype=torch.long)
         out.edge_index._hex_edge_ptr = ecnt.cumsum(0).to(device)
         if starts is not None and out.edge_index.is_cuda:
-            attach_blocks(out.edge_index, starts)
+            if groups is not None:
+                attach_block_groups(out.edge_index, starts, groups)
+            else:
+                attach_blocks(out.edge_index, starts)
         return out
 
     @property

@@ -105,6 +105,40 @@ def _blocks_of(edge_index, n: int):
     return (t, nb)
 
 
+def _groups_of(edge_index, n: int):
+    """The collation's block table of a batch that needs more blocks than can be resident at once, with its groups
+    (``edge_index._hex_block_groups`` = (int32 device tensor [nb + 1], nb, groups), ``data.attach_block_groups``): every group
+    is one launch of the one-launch stack kernels (``hexgnn_sage_stack_*_groups``).  Returns (table, nb, groups, the groups as
+    a C int array) or None; anything malformed is ignored."""
+    grp = getattr(edge_index, "_hex_block_groups", None)
+    if grp is None:
+        return None
+    try:
+        t, nb, groups = grp
+        nb = int(nb)
+        groups = tuple(int(g) for g in groups)
+    except (TypeError, ValueError):
+        return None
+    if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+            and t.numel() == nb + 1 and (int(n) + 127) // 128 <= nb <= min(512, max(int(n), 1))):
+        return None
+    if len(groups) < 2 or groups[0] != 0 or groups[-1] != nb or any(b <= a for a, b in zip(groups, groups[1:])):
+        return None
+    return (t, nb, groups, (C.c_int * len(groups))(*groups))
+
+
+def _stack_entry(L, gs, forward: bool):
+    """Entry point of the layer-major stack for a batch and its trailing table arguments: the ``_groups`` form when the batch
+    carries a grouped table, the ``_blocks`` form otherwise."""
+    grp = gs.groups
+    if grp is not None:
+        name = "hexgnn_sage_stack_forward_groups" if forward else "hexgnn_sage_stack_backward_groups"
+        return getattr(L, name), name, (grp[0].data_ptr(), grp[1], grp[3], len(grp[2]) - 1)
+    blk = gs.blocks
+    name = "hexgnn_sage_stack_forward_blocks" if forward else "hexgnn_sage_stack_backward_blocks"
+    return getattr(L, name), name, (blk[0].data_ptr() if blk else None, blk[1] if blk else 0)
+
+
 class GraphStructure:
     """Target-major CSR of a batch + its transpose + 1/deg, built once per batch on the device.
 
@@ -112,7 +146,7 @@ class GraphStructure:
     Replaces the per-layer x[edge_index[0]] / scatter(edge_index[1]) indexing of the reference
     (GN0/models.py:276)."""
 
-    __slots__ = ("n", "e", "rowptr", "col", "rowptr_t", "col_t", "invdeg", "status", "_ptrs", "blocks")
+    __slots__ = ("n", "e", "rowptr", "col", "rowptr_t", "col_t", "invdeg", "status", "_ptrs", "blocks", "groups")
 
     def __init__(self, edge_index: torch.Tensor, num_nodes: int, gptr: Optional[torch.Tensor] = None, b: int = 0,
                  ptr64: Optional[torch.Tensor] = None):
@@ -124,6 +158,7 @@ class GraphStructure:
         if edge_index.dim() != 2 or edge_index.shape[0] != 2:
             raise ValueError("edge_index must be [2, E]")
         blocks = _blocks_of(edge_index, num_nodes)
+        groups = _groups_of(edge_index, num_nodes) if blocks is None else None
         if edge_index.dtype != torch.int64:
             edge_index = edge_index.long()
         edge_index = edge_index.contiguous()
@@ -133,6 +168,7 @@ class GraphStructure:
         self.n, self.e = n, e
         self._ptrs = None
         self.blocks = blocks
+        self.groups = groups
         if gptr is not None and b > 0:
             ibuf = torch.empty(2 * (n + 1), dtype=torch.int32, device=dev)
             self.rowptr, self.rowptr_t = ibuf[:n + 1], ibuf[n + 1:2 * (n + 1)]
@@ -176,6 +212,7 @@ class GraphStructure:
         n, e = int(num_nodes), int(edge_index.shape[1])
         self.n, self.e = n, e
         self.blocks = _blocks_of(edge_index, n)
+        self.groups = _groups_of(edge_index, n) if self.blocks is None else None
         e1 = e if e > 0 else 1
         o1, o2 = n + 1, 2 * (n + 1)
         o3, o4 = o2 + e1, o2 + 2 * e1
@@ -196,7 +233,7 @@ class GraphStructure:
                                        and ep.numel() == int(b) + 1):
                 ep = None
             tbl, budget = None, 0
-            if device_blocks and self.blocks is None and _DEVICE_BLOCKS:
+            if device_blocks and self.blocks is None and self.groups is None and _DEVICE_BLOCKS:
                 # the layer-major path of a batch that carries no block table (raw tensors: another collation): built on the device
                 # in this launch, in the batch's own graph order (the host never sees the sizes)
                 budget = stack_block_budget()
@@ -228,6 +265,7 @@ class GraphStructure:
         self.status = sticky_status(rowptr.device)
         self._ptrs = None
         self.blocks = None
+        self.groups = None
         return self
 
     def check(self) -> None:
@@ -353,12 +391,12 @@ class SageStackFn(torch.autograd.Function):
         wpack = _bytes(L.hexgnn_sage_stack_pack_bytes(c_in, hidden, num_layers), dev)
         # (hidden > 128: the plain kernels materialise every layer's aggregate, with or without a backward)
         saved = _bytes(L.hexgnn_sage_stack_saved_bytes(n, c_in, hidden, num_layers), dev) if (need_bwd or hidden > 128) else None
-        blk = gs.blocks
-        _lib.check(L.hexgnn_sage_stack_forward_blocks(
+        fn, name, tbl = _stack_entry(L, gs, True)
+        _lib.check(fn(
             n, c_in, hidden, num_layers, gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.invdeg.data_ptr(),
             xin.data_ptr(), x_stride, _ptr_array(wl), _ptr_array(bl), _ptr_array(wr), wpack.data_ptr(),
             acts.data_ptr(), saved.data_ptr() if saved is not None else None, int(need_bwd), int(flags),
-            blk[0].data_ptr() if blk else None, blk[1] if blk else 0, _stream()), "hexgnn_sage_stack_forward_blocks")
+            *tbl, _stream()), name)
         if need_bwd:
             ctx.gs = gs
             ctx.flags = int(flags)
@@ -380,14 +418,13 @@ class SageStackFn(torch.autograd.Function):
         grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.param_shapes]
         ws_bytes = L.hexgnn_sage_stack_backward_workspace_bytes(n, c_in, hidden, num_layers)
         ws = _bytes(ws_bytes, dev)
-        blk = gs.blocks
-        _lib.check(L.hexgnn_sage_stack_backward_blocks(
+        fn, name, tbl = _stack_entry(L, gs, False)
+        _lib.check(fn(
             n, c_in, hidden, num_layers, gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.rowptr_t.data_ptr(),
             gs.col_t.data_ptr(), gs.invdeg.data_ptr(), xin.data_ptr(), x_stride, acts.data_ptr(),
             saved.data_ptr(), wpack.data_ptr(), dy.data_ptr(), dx.data_ptr() if dx is not None else None,
             _ptr_array(grads[0::3]), _ptr_array(grads[1::3]), _ptr_array(grads[2::3]), ws.data_ptr(), ws_bytes,
-            ctx.flags, -1, None, blk[0].data_ptr() if blk else None, blk[1] if blk else 0, _stream()),
-            "hexgnn_sage_stack_backward_blocks")
+            ctx.flags, -1, None, *tbl, _stream()), name)
         gx = _logical(dx, hidden) if dx is not None else None
         return (gx, None, None, None, None, None) + tuple(grads)
 
@@ -1081,11 +1118,9 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
     stream = _stream()
     td = None
     if layered:
-        blk = gs.blocks
-        _lib.check(L.hexgnn_sage_stack_forward_blocks(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl,
-                                                      bl, wr, wpack, base, saved, int(need_bwd), 0,
-                                                      blk[0].data_ptr() if blk else None, blk[1] if blk else 0, stream),
-                   "hexgnn_sage_stack_forward_blocks")
+        fn, name, tbl = _stack_entry(L, gs, True)
+        _lib.check(fn(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr, wpack, base, saved,
+                      int(need_bwd), 0, *tbl, stream), name)
         _lib.check(L.hexgnn_head_forward(n, b, hidden, mode, gp[5], base + 4 * (tot - 1) * n * hp, t[0], t[1], t[2], t[3],
                                          t[4], t[5], q.data_ptr(), out_v.data_ptr() if out_v is not None else None,
                                          saved + bwd_bytes[0], stream), "hexgnn_head_forward")
@@ -1201,12 +1236,12 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
         d_wl = vp(*[fb + 4 * offs[3 * l] for l in range(tot)])
         d_bl = vp(*[fb + 4 * offs[3 * l + 1] for l in range(tot)])
         d_wr = vp(*[fb + 4 * offs[3 * l + 2] for l in range(tot)])
-        blk = call.gs.blocks
-        _lib.check(L.hexgnn_sage_stack_backward_blocks(
+        fn, name, tbl = _stack_entry(L, call.gs, False)
+        _lib.check(fn(
             n, c_in, hidden, tot, gp[0], gp[1], gp[2], gp[3], gp[4], call.x.data_ptr(), x_stride, base,
             base + a_bytes + w_bytes, base + a_bytes, dh_ptr, None, d_wl, d_bl, d_wr, ws.data_ptr(), ws_bytes, 2,
             body_layers - 1 if d_emb is not None else -1, d_emb.data_ptr() if d_emb is not None else None,
-            blk[0].data_ptr() if blk else None, blk[1] if blk else 0, stream), "hexgnn_sage_stack_backward_blocks")
+            *tbl, stream), name)
     else:
         ws_bytes = bwd_bytes
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)

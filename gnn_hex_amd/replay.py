@@ -11,13 +11,14 @@ against that oracle; method names follow the upstream buffer (``put`` / ``sample
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional
 
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .data import Batch
+from .data import Batch, block_groups, blocks_for_order, pack_groups, pack_order
 
 
 def _pow2_at_least(n: int) -> int:
@@ -32,13 +33,18 @@ class GraphReplayBuffer:
     buffer for maker and one for breaker transitions, multi_env_manager.py:139)."""
 
     def __init__(self, capacity: int, hex_size: int, prioritized: bool = True, alpha: float = 0.5, eps: float = 1e-6,
-                 burnin: int = 0, device="cuda", pack_blocks: bool = True):
+                 burnin: int = 0, device="cuda", pack_blocks: bool = True, group_blocks: bool = False):
         """``pack_blocks`` (boards above 128 nodes, Hex-12 and larger, which run on the one-launch SAGE stack kernels): a draw is
         listed in ``data.pack_order`` order -- indices, weights, both batches, actions, rewards and done flags alike, the order of
         a random draw carries no meaning -- with the row-block tables attached, so that workgroups hold whole graphs or their own
-        pieces of a large one instead of whatever a multiple of 128 rows cuts."""
+        pieces of a large one instead of whatever a multiple of 128 rows cuts.
+
+        ``group_blocks``: a draw with more rows than can be resident at once (256 Hex-13 boards: one launch per layer otherwise)
+        is packed with ``data.pack_groups`` and both batches carry their table in groups of whole graphs, one launch per group
+        (``hexgnn_sage_stack_*_groups``).  Off by default: see ``Batch.from_data_list``."""
         self.capacity, self.hex_size = int(capacity), int(hex_size)
         self.pack_blocks = bool(pack_blocks) and hex_size * hex_size + 2 > 128
+        self.group_blocks = bool(group_blocks)
         self._max_blocks = None
         self.prioritized, self.alpha, self.eps, self.burnin = prioritized, float(alpha), float(eps), int(burnin)
         self.device = torch.device(device)
@@ -222,6 +228,12 @@ class GraphReplayBuffer:
         gs = ops.GraphStructure.from_csr(N, E, rowptr, col, invdeg)
         if starts is not None and len(starts) - 1 <= self._max_blocks:
             gs.blocks = (torch.tensor(starts, dtype=torch.int32).to(dev, non_blocking=True), len(starts) - 1)
+        elif starts is not None and self.group_blocks and -(-N // 128) > self._max_blocks:
+            # more rows than can be resident at once: whole graphs in groups, one launch of the stack kernels each
+            groups = block_groups(self.n_nodes[slots_host], starts, self._max_blocks)
+            if groups is not None:
+                gs.groups = (torch.tensor(starts, dtype=torch.int32).to(dev, non_blocking=True), len(starts) - 1,
+                             tuple(groups), (ctypes.c_int * len(groups))(*groups))
         b.edge_index._hex_csr = gs
         return b
 
@@ -266,9 +278,10 @@ class GraphReplayBuffer:
         batch_size = len(host)
         st_blocks = nx_blocks = None
         if self.pack_blocks and batch_size:
-            from .data import blocks_for_order, pack_order
             self._max_blocks = ops.stack_block_budget(self.device)      # (a host-side query; changes with GradSync.enable_overlap)
             order, st_blocks = pack_order(self.n_nodes[host], max_blocks=self._max_blocks)
+            if st_blocks is None and self.group_blocks and self._max_blocks > 0:
+                order, st_blocks, _ = pack_groups(self.n_nodes[host], max_blocks=self._max_blocks)
             if st_blocks is not None:
                 perm = np.asarray(order, dtype=np.int64)
                 host = host[perm]

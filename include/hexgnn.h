@@ -194,6 +194,33 @@ int hexgnn_sage_stack_backward_blocks(int n, int c_in, int hidden, int num_layer
                                       int tap_layer, float* tap_out, const int* block_starts, int num_blocks,
                                       hexgnn_stream_t stream);
 
+/* The same with the table's blocks in GROUPS, for batches whose table has more blocks than can be resident at once (a uniform
+ * Hex-13 replay batch of 256 graphs: 512 blocks on 256 CUs).  Graphs are independent: a range of blocks that holds whole graphs
+ * never waits for a block outside it, so the one-launch kernel runs group after group on the caller's stream -- one launch per
+ * group and direction instead of one per layer.  group_starts (HOST array, num_groups + 1 block indices, read before the call
+ * returns): group_starts[0] = 0 < group_starts[1] < ... < group_starts[num_groups] = num_blocks; every cut must fall where a
+ * block start is also a graph start (gnn_hex_amd.data.block_groups / pack_groups).  Rejected with HEXGNN_EINVAL on the host,
+ * before anything is launched: groups without a table, a list that is not strictly ascending (an empty group), wrong end
+ * points, num_blocks outside [1, 512] (the progress counters of a call are indexed by the table's block index, so 512 caps the
+ * whole table, not a group).  A cut that an edge crosses cannot be seen by the host; the kernel does not wait across it: the
+ * rows of a wave that would read a block outside its launch's group become NaN and hexgnn_stack_status reports HEXGNN_EINVAL.
+ * If the largest group does not pass the residency test of the one-launch kernels (budget, CU mask, another stream in flight),
+ * under HEXGNN_NO_PERSIST / hexgnn_debug_stack_mode(0, ...), for hidden <= 32 and for hidden > 128 the groups are ignored and
+ * the call is the _blocks one.  num_groups == 0: exactly the _blocks call.  A block's arithmetic depends on the table only:
+ * results are bit-identical to one launch over the same table. */
+int hexgnn_sage_stack_forward_groups(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
+                                     const float* invdeg, const float* x, int x_stride, const float* const* wl,
+                                     const float* const* bl, const float* const* wr, void* wpack, float* acts,
+                                     void* saved, int need_backward, int flags, const int* block_starts, int num_blocks,
+                                     const int* group_starts, int num_groups, hexgnn_stream_t stream);
+int hexgnn_sage_stack_backward_groups(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
+                                      const int* rowptr_t, const int* col_t, const float* invdeg, const float* x,
+                                      int x_stride, const float* acts, const void* saved, const void* wpack,
+                                      const float* dy, float* dx, float* const* d_wl, float* const* d_bl,
+                                      float* const* d_wr, void* workspace, size_t workspace_bytes, int flags,
+                                      int tap_layer, float* tap_out, const int* block_starts, int num_blocks,
+                                      const int* group_starts, int num_groups, hexgnn_stream_t stream);
+
 /* ---- head tail: HeadNetwork.forward after its gnn (GN0/models.py:374-384), MLP value head
  *      (GN0/models.py:36-82: Linear(4H,H/2) -> relu -> Linear(H/2,1)) and the dueling combine of
  *      DuellingTwoHeaded.forward (GN0/models.py:567-584).

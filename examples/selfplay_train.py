@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gnn_hex_amd import ops  # noqa: E402
 from gnn_hex_amd.models import get_pre_defined  # noqa: E402
 from gnn_hex_amd.multi_env_manager import DeviceRollout, Env_manager, RolloutStitcher  # noqa: E402
-from gnn_hex_amd.replay import GraphReplayBuffer  # noqa: E402
+from gnn_hex_amd.replay import GraphedUpdate, GraphReplayBuffer  # noqa: E402
 
 
 def main():
@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--async-rollout", action="store_true",
                     help="issue the next rollout before this iteration's updates: the GPU plays while the host prepares "
                          "the update batches; the actor's weights are then one iteration (4 updates) old")
+    ap.add_argument("--graph-updates", action="store_true",
+                    help="every update as ONE HIP graph per side (replay.GraphedUpdate): the draw is sized on the device, so "
+                         "the host neither waits for the drawn slots nor issues the update's launches one by one "
+                         "(fp32 only; with --no-graph the same sequence is issued eagerly, still without a host wait)")
     args = ap.parse_args()
     ops.set_math(args.math)
     gamma, n_step = 0.97, 2
@@ -49,7 +53,9 @@ def main():
     torch.manual_seed(0)
     q_net = get_pre_defined("modern_two_headed", margs).cuda()
     target_net = copy.deepcopy(q_net)
-    opt = torch.optim.Adam(q_net.parameters(), lr=4e-4, fused=True)     # one launch for all 66 parameter tensors
+    # one launch for all 66 parameter tensors; capturable (step counts on the device) when it runs inside the updates' graphs
+    opt = torch.optim.Adam(q_net.parameters(), lr=4e-4, fused=True, capturable=args.graph_updates)
+    graphed = {}                       # --graph-updates: side -> GraphedUpdate, built when its buffer first holds a batch
     mgr = Env_manager(args.envs, args.hex_size, gamma=gamma, n_steps=[n_step])
     mgr.reset()
     cap = 65536
@@ -76,12 +82,19 @@ def main():
         # update) is started right after its update is issued: while the host waits for those indices and builds that
         # batch, the GPU runs the OTHER buffer's update.
         sides = [sd for sd in (True, False) if len(bufs[sd]) >= args.batch]
-        pending = {sd: bufs[sd].sample_begin(args.batch, beta=0.6) for sd in sides}
+        pending = {} if args.graph_updates else {sd: bufs[sd].sample_begin(args.batch, beta=0.6) for sd in sides}
         # (after put_block: the run overwrites the snapshot ring; after the first draws: they need not wait for the rollout)
         ahead = rollout.run_begin() if args.async_rollout else None
         for k in range(args.updates):
             for side in sides:
                 buf = bufs[side]
+                if args.graph_updates:
+                    if side not in graphed:
+                        graphed[side] = GraphedUpdate(buf, q_net, target_net, opt, args.batch, gamma ** n_step, "mse",
+                                                      graph=not args.no_graph)
+                    last_loss, _ = graphed[side].step(beta=0.6)
+                    updates += 1
+                    continue
                 idx, w, s, s2, act, r, d = buf.sample_end(pending[side])
                 # double DQN: argmax of the online net over each next state's non-terminal nodes, target net's value there --
                 # both networks in one forward launch, y = r + gamma^n * q_tg[argmax] * (~d).float() formed by one more
@@ -102,8 +115,9 @@ def main():
         rollout.run_end(ahead)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print("hex %d, %d envs, GNN %dx%d, math %s%s: %.0f env frames/s, %.1f updates/s (batch %d), %d games finished, last loss %.4f"
-          % (args.hex_size, args.envs, args.layers, args.hidden, args.math, ", rollout one iteration ahead" if args.async_rollout else "", frames / dt, updates / dt, args.batch, games,
+    print("hex %d, %d envs, GNN %dx%d, math %s%s%s: %.0f env frames/s, %.1f updates/s (batch %d), %d games finished, last loss %.4f"
+          % (args.hex_size, args.envs, args.layers, args.hidden, args.math, ", rollout one iteration ahead" if args.async_rollout else "",
+             ", graphed updates" if args.graph_updates else "", frames / dt, updates / dt, args.batch, games,
              float(last_loss)))
 
 

@@ -98,6 +98,8 @@ _SIGS = {
                                     vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
     "hexgnn_qnet_backward_flat_td": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp, sz, vp, ci, ci, ci, vp, vp, vp]),
+    "hexgnn_qnet_backward_flat_td_live": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp,
+                                               vp, vp, vp, sz, vp, ci, ci, ci, vp, vp, vp, vp]),
     "hexgnn_qnet_jobs_bytes": (sz, [ci, ci]),
     "hexgnn_qnet_multi_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
     "hexgnn_qnet_forward_jobs": (ci, [ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
@@ -119,6 +121,8 @@ _SIGS = {
     "hexgnn_per_update": (ci, [ci, ci, vp, vp, vp, vp, vp]),
     "hexgnn_per_update_td": (ci, [ci, ci, vp, ci, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
     "hexgnn_per_sample": (ci, [ci, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "hexgnn_per_sample_dev": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
+    "hexgnn_replay_offsets": (ci, [ci, vp, ci, ci, vp, vp, vp, vp, vp]),
     "hexgnn_select_actions": (ci, [ci, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),

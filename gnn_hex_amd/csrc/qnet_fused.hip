@@ -304,7 +304,7 @@ static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int tot
                                 float* const* d_wr, float* d_lin_w, float* d_lin_b, float* d_v0_w, float* d_v0_b,
                                 float* d_v1_w, float* d_v1_b, void* workspace, size_t workspace_bytes, int* status,
                                 int stages, int layer_lo, int layer_hi, const float* loss_part, float* loss,
-                                hexgnn_stream_t stream_) {
+                                hexgnn_stream_t stream_, const int* n_live = nullptr) {
     hipStream_t st = (hipStream_t)stream_;
     if (n < 0 || b < 0 || mode < 0 || mode > 2 || math < 0 || math > 1 || body_layers < 1 || body_layers > total_layers)
         return HEXGNN_EINVAL;
@@ -374,7 +374,7 @@ static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int tot
         if (nh > 0) {
             rc = launch_weight_grads(n, c_in, hidden, qp.sp, qp.bp, x, x_stride, acts, sv, G, d_wl, d_bl, d_wr, spart,
                                      part0, st, math, (const unsigned*)(sv + qp.xmax_off), a.gmax,
-                                     /*hidden_only_no_reduce=*/true, lo, hi);
+                                     /*hidden_only_no_reduce=*/true, lo, hi, n_live);
             if (rc != HEXGNN_OK) return rc;
         }
         GradReduceArgs r;
@@ -476,6 +476,29 @@ int hexgnn_qnet_backward_flat_td(int n, int b, int c_in, int hidden, int total_l
                                      d_wr, flat + t[0], flat + t[1], flat + t[2], flat + t[3], flat + t[4], flat + t[5],
                                      workspace, workspace_bytes, status, stages, layer_lo, layer_hi, loss_part, loss,
                                      stream_);
+}
+
+int hexgnn_qnet_backward_flat_td_live(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int math,
+                                      const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
+                                      const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
+                                      const float* lin_w, const float* v0_w, const float* v1_w, const float* dq,
+                                      float* d_embeds, float* flat, const int64_t* offsets, void* workspace,
+                                      size_t workspace_bytes, int* status, int stages, int layer_lo, int layer_hi,
+                                      const float* loss_part, float* loss, const int* n_live, hexgnn_stream_t stream_) {
+    if (!flat || !offsets || total_layers < 1 || total_layers > kMaxLayers || !loss_part || !loss || !n_live || math < 0 ||
+        math > 1)
+        return HEXGNN_EINVAL;
+    if (math == 1) return HEXGNN_EUNSUPPORTED;      // (the split-f16 GEMM walks rows by the host's count)
+    float* d_wl[kMaxLayers]; float* d_bl[kMaxLayers]; float* d_wr[kMaxLayers];
+    for (int l = 0; l < total_layers; ++l) {
+        d_wl[l] = flat + offsets[3 * l]; d_bl[l] = flat + offsets[3 * l + 1]; d_wr[l] = flat + offsets[3 * l + 2];
+    }
+    const int64_t* t = offsets + 3 * total_layers;      // lin_w, lin_b, v0_w, v0_b, v1_w, v1_b
+    return qnet_backward_staged_impl(n, b, c_in, hidden, total_layers, body_layers, 0, math, gptr, rowptr_t, col_t, invdeg, x,
+                                     x_stride, acts, saved, wpack, lin_w, v0_w, v1_w, dq, nullptr, d_embeds, d_wl, d_bl,
+                                     d_wr, flat + t[0], flat + t[1], flat + t[2], flat + t[3], flat + t[4], flat + t[5],
+                                     workspace, workspace_bytes, status, stages, layer_lo, layer_hi, loss_part, loss,
+                                     stream_, n_live);
 }
 
 #ifdef HEXGNN_STAMPS

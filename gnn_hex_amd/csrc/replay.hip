@@ -88,9 +88,9 @@ __global__ __launch_bounds__(1024) void per_update_kernel(int cap, int k, const 
     }
 }
 
-__global__ void per_sample_kernel(int cap, int size, int b, double beta, const double* __restrict__ u,
-                                  const double* __restrict__ sum_tree, const double* __restrict__ min_tree,
-                                  int* __restrict__ out_idx, float* __restrict__ out_w) {
+__device__ __forceinline__ void per_sample_body(int cap, int size, int b, double beta, const double* __restrict__ u,
+                                                const double* __restrict__ sum_tree, const double* __restrict__ min_tree,
+                                                int* __restrict__ out_idx, float* __restrict__ out_w) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b) return;
     const double total = sum_tree[1];
@@ -108,6 +108,58 @@ __global__ void per_sample_kernel(int cap, int size, int b, double beta, const d
     const double max_w = pow(p_min * (double)size, -beta);
     const double p = sum_tree[cap + leaf] / total;
     out_w[i] = (float)(pow(p * (double)size, -beta) / max_w);
+}
+__global__ void per_sample_kernel(int cap, int size, int b, double beta, const double* __restrict__ u,
+                                  const double* __restrict__ sum_tree, const double* __restrict__ min_tree,
+                                  int* __restrict__ out_idx, float* __restrict__ out_w) {
+    per_sample_body(cap, size, b, beta, u, sum_tree, min_tree, out_idx, out_w);
+}
+// the same draw with the fill level and beta read from device memory: both change while a run goes on (the ring fills, beta is
+// annealed), and a captured graph must not bake them in.  A fill level outside [1, cap] is clamped (no slot index ever leaves
+// the trees).
+__global__ void per_sample_dev_kernel(int cap, const int* __restrict__ size_p, int b, const double* __restrict__ beta_p,
+                                      const double* __restrict__ u, const double* __restrict__ sum_tree,
+                                      const double* __restrict__ min_tree, int* __restrict__ out_idx, float* __restrict__ out_w) {
+    int size = *size_p;
+    size = size < 1 ? 1 : (size > cap ? cap : size);
+    per_sample_body(cap, size, b, *beta_p, u, sum_tree, min_tree, out_idx, out_w);
+}
+
+// Exclusive prefix sums of the graph sizes of k drawn slots (slot = slots[i] + shift: shift 0 = the states, shift capacity = the
+// next states), sizes[slot] = {nodes, directed edges} as stored by GraphReplayBuffer.put / put_block: node_off / edge_off
+// [k + 1] int32 (what hexgnn_states_observe takes) and ptr [k + 1] int64 (Batch.ptr); the last entries are the live totals.
+// One wave walks the list 64 slots at a time with running totals (hexgnn_env_offsets' scheme), so any k works; a slot outside
+// [0, n_slots) counts as an empty graph.
+__global__ __launch_bounds__(64) void replay_offsets_kernel(int k, const int* __restrict__ slots, int shift, int n_slots,
+                                                            const int* __restrict__ sizes, int* __restrict__ node_off,
+                                                            int* __restrict__ edge_off, long long* __restrict__ ptr) {
+    const int lane = threadIdx.x;
+    int run_n = 0, run_e = 0;
+    for (int base = 0; base < k; base += 64) {
+        const int i = base + lane;
+        int vn = 0, ve = 0;
+        if (i < k) {
+            const long long slot = (long long)slots[i] + shift;
+            if (slot >= 0 && slot < (long long)n_slots) { vn = sizes[2 * slot]; ve = sizes[2 * slot + 1]; }
+        }
+        int pn = vn, pe = ve;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int a = __shfl_up(pn, off), b = __shfl_up(pe, off);
+            if (lane >= off) { pn += a; pe += b; }
+        }
+        if (i < k) {
+            node_off[i] = run_n + pn - vn;
+            edge_off[i] = run_e + pe - ve;
+            if (ptr) ptr[i] = run_n + pn - vn;
+        }
+        run_n += __shfl(pn, 63);
+        run_e += __shfl(pe, 63);
+    }
+    if (lane == 0) {
+        node_off[k] = run_n;
+        edge_off[k] = run_e;
+        if (ptr) ptr[k] = run_n;
+    }
 }
 
 __global__ void per_fill_kernel(int n, double v_sum, double v_min, double* __restrict__ sum_tree,
@@ -168,6 +220,24 @@ int hexgnn_per_sample(int capacity_pow2, int size, int b, double beta, const dou
         return HEXGNN_EINVAL;
     per_sample_kernel<<<(b + 255) / 256, 256, 0, (hipStream_t)stream_>>>(capacity_pow2, size, b, beta, u, sum_tree,
                                                                          min_tree, out_idx, out_w);
+    return check_launch();
+}
+
+int hexgnn_per_sample_dev(int capacity_pow2, const int* size, int b, const double* beta, const double* u,
+                          const double* sum_tree, const double* min_tree, int* out_idx, float* out_w, hexgnn_stream_t stream_) {
+    if (capacity_pow2 < 1 || (capacity_pow2 & (capacity_pow2 - 1)) || !size || !beta || b < 1 || !u || !sum_tree || !min_tree ||
+        !out_idx || !out_w)
+        return HEXGNN_EINVAL;
+    per_sample_dev_kernel<<<(b + 255) / 256, 256, 0, (hipStream_t)stream_>>>(capacity_pow2, size, b, beta, u, sum_tree,
+                                                                             min_tree, out_idx, out_w);
+    return check_launch();
+}
+
+int hexgnn_replay_offsets(int k, const int* slots, int shift, int n_slots, const int* sizes, int* node_off, int* edge_off,
+                          int64_t* ptr, hexgnn_stream_t stream_) {
+    if (k < 0 || n_slots < 1 || !sizes || !node_off || !edge_off || (k > 0 && !slots)) return HEXGNN_EINVAL;
+    replay_offsets_kernel<<<1, 64, 0, (hipStream_t)stream_>>>(k, slots, shift, n_slots, sizes, node_off, edge_off,
+                                                              reinterpret_cast<long long*>(ptr));
     return check_launch();
 }
 

@@ -326,7 +326,8 @@ void launch_combine(int n, int hp, const int* rowptr_t, const int* col_t, const 
 template <int NT>
 static void launch_dw(const DwArgs& a, int layers, float* part, hipStream_t st) {
     KernelTimer kt(HEXGNN_K_SAGE_DW, st);
-    sage_dw_kernel<NT><<<dim3(a.S, layers), 64 * DwShape<NT>::kWaves, 0, st>>>(a, part);
+    if (a.n_live) sage_dw_kernel<NT, 0, 2, 0, true><<<dim3(a.S, layers), 64 * DwShape<NT>::kWaves, 0, st>>>(a, part);
+    else sage_dw_kernel<NT><<<dim3(a.S, layers), 64 * DwShape<NT>::kWaves, 0, st>>>(a, part);
 }
 
 template <int NT>
@@ -387,7 +388,10 @@ int launch_weight_grads(int n, int c_in, int hidden, const StackPlan& p, const B
                         int x_stride, const float* acts, const char* sv, const float* G, float* const* d_wl,
                         float* const* d_bl, float* const* d_wr, float* part, float* part0, hipStream_t st,
                         int math, const unsigned* xmax, const unsigned* gmax, bool hidden_only_no_reduce,
-                        int layer_lo, int layer_hi) {
+                        int layer_lo, int layer_hi, const int* n_live) {
+    // a device-side row count: the exact-fp32 hidden-layer GEMM of the fused path only (the raw first layer's row-slice kernel
+    // and the split-f16 GEMM walk rows by the host's n)
+    if (n_live && (math == 1 || !hidden_only_no_reduce || layer_lo < 1)) return HEXGNN_EUNSUPPORTED;
     const size_t slab = (size_t)n * p.hp;
     const int lo = layer_lo < 0 ? (p.small_first ? 1 : 0) : layer_lo;
     const int first_hidden = lo;                    // first layer of this launch (hidden-input layers only)
@@ -405,7 +409,7 @@ int launch_weight_grads(int n, int c_in, int hidden, const StackPlan& p, const B
         }
         const int S = dw_slices_for(n, nh, (math == 1 && xmax && gmax) ? 1 : 0, p.L - (p.small_first ? 1 : 0));
         const int rps = dw_rows_per_slice(n, S);
-        da.n = n; da.rows_per_slice = rps; da.S = S;
+        da.n = n; da.rows_per_slice = rps; da.S = S; da.n_live = n_live;
         ra.S = S; ra.hp = p.hp; ra.hidden = hidden;
         if (math == 1 && xmax && gmax) {
             Dw16Args d16;

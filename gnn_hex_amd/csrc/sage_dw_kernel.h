@@ -14,6 +14,7 @@ struct DwArgs {
     const float* agg[kMaxLayers];
     const float* g[kMaxLayers];
     int n, rows_per_slice, S;
+    const int* n_live;      // LIVE kernels only: device-side row count (<= n), see sage_dw_kernel
 };
 
 // Work split of one workgroup.  Wave w < NT owns output channels 16w..16w+15 (one 16-row tile of dW) against the first
@@ -39,7 +40,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // MV = 1 (NT >= 4, E = 2): the extra wave hands its last tile (output tile NT-1 x input tile 2NT-1) to wave 2, so that the SIMD
 // pairs (w, w + 4) carry 24 / 24 / 25 / 25 MFMAs per k-step instead of 24 / 24 / 24 / 26.
-template <int NT, int VT = 0, int E = 2, int MV = 0>
+//
+// LIVE: the buffers are capacity-sized (a.n rows) and only the first *a.n_live rows hold graphs (a replay draw sized on the
+// device: rows behind them are uninitialised and must not reach a slab).  The grid keeps the slice count planned for a.n; the
+// live rows are spread over those slices here (rows per slice from *n_live, rounded up to 32 as the host plan rounds), slices
+// behind them are empty and store zero slabs like the empty trailing slices of an exact-size plan.  *n_live == a.n reproduces
+// the host's plan, and with it every bit.  LIVE = false is the kernel as it always was.
+template <int NT, int VT = 0, int E = 2, int MV = 0, bool LIVE = false>
 __global__ __launch_bounds__((64 * DwShape<NT, VT, E, MV>::kWaves)) void sage_dw_kernel(DwArgs a, float* __restrict__ part) {
     using SH = DwShape<NT, VT, E, MV>;
     constexpr bool kMove = MV == 1 && SH::kBal && E == 2 && VT == 0;
@@ -60,8 +67,13 @@ __global__ __launch_bounds__((64 * DwShape<NT, VT, E, MV>::kWaves)) void sage_dw
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int m = lane & 15, kq = lane >> 4;
     const bool extra = SH::kBal && w == NT;     // wave-uniform
-    const int r_beg = s * a.rows_per_slice;
-    const int r_end = min(a.n, r_beg + a.rows_per_slice);
+    int n_rows = a.n, rps = a.rows_per_slice;
+    if constexpr (LIVE) {
+        n_rows = min(max(*a.n_live, 0), a.n);
+        rps = ((n_rows + a.S - 1) / a.S + 31) / 32 * 32;
+    }
+    const int r_beg = s * rps;
+    const int r_end = min(n_rows, r_beg + rps);
 
     constexpr int kAcc = (NB + (kMove ? 1 : 0)) > NE * NT ? NB + (kMove ? 1 : 0) : NE * NT;
     f32x4 acc[kAcc];         // regular wave: tile t < NB; extra wave: [NE * t + tb]

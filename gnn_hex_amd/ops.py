@@ -1051,9 +1051,10 @@ class QNetParamCache:
 class _QNetCall:
     """Everything one fused forward leaves behind for its backward (plain attributes: cheaper than ctx.save_for_backward).
     ``assign``: the direct form (the backward assigns ``p.grad``) rather than the autograd form (it returns the gradients);
-    ``nonleaf``: a parameter of the call is computed per forward (no staging, see qnet_backward)."""
+    ``nonleaf``: a parameter of the call is computed per forward (no staging, see qnet_backward); ``live``: td_step() over
+    capacity-sized buffers -- the 1-element int32 device tensor that holds the live row count (``x._hex_live_rows``)."""
     __slots__ = ("cache", "gs", "gptr", "dims", "x", "bufs", "math", "sink", "gp", "done", "layered", "td", "pending", "versions",
-                 "assign", "nonleaf")
+                 "assign", "nonleaf", "live")
 
 
 def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
@@ -1116,7 +1117,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
               gptr.data_ptr(), gs.status.data_ptr())
     t = cache.tail
     stream = _stream()
-    td = None
+    td = live = None
     if layered:
         fn, name, tbl = _stack_entry(L, gs, True)
         _lib.check(fn(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr, wpack, base, saved,
@@ -1138,6 +1139,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
                 sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
                 tp + 4 * (n + b), stream), "hexgnn_qnet_forward_td")
             td = (tb, n, b)
+            live = getattr(_TD_STEP, "live", None)
         else:
             _lib.check(L.hexgnn_qnet_forward(
                 n, b, c_in, hidden, tot, mode, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
@@ -1149,7 +1151,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
     call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, bwd_bytes)
     call.bufs, call.math, call.gp = buf, 0 if layered else _MATH, gp
     call.sink, call.done, call.layered, call.td, call.pending = None, False, layered, td, None
-    call.assign, call.nonleaf = assign, False
+    call.assign, call.nonleaf, call.live = assign, False, live
     # the backward reads the head tail's weights LIVE (the SAGE layers' from the pack made by this forward): an in-place update
     # between the two would mix old and new weights without autograd's saved-tensor version check to notice it
     call.versions = tuple(p._version for p in cache.params[-6:]) if need_bwd else None
@@ -1214,6 +1216,11 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
     else:
         flat, gviews = torch.empty(cache.total, dtype=torch.float32, device=dev), None
     base, gp, t, fb = call.bufs.data_ptr(), call.gp, cache.tail, flat.data_ptr()
+    live = call.live
+    if live is not None and (call.layered or call.math != 0 or call.td is None or dq.data_ptr() != call.td[0].data_ptr()
+                             or defer_lower or _GRAD_STAGE_HOOK is not None):
+        raise NotImplementedError("a device-side live row count (x._hex_live_rows) is taken by td_step()'s fused form in exact "
+                                  "fp32 only: no layer-major path, no set_math(\"f16x3\"), no staged backward")
     if call.layered:
         s_bytes, ws_bytes, hws_bytes = bwd_bytes
         ws = torch.empty(ws_bytes + hws_bytes, dtype=torch.uint8, device=dev)
@@ -1259,8 +1266,13 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
             tb, tn, tbb = td
             tp = tb.data_ptr()
             ctd = common[:6] + common[7:21] + common[22:]          # (no mode, no d_out_v: mode 0)
-            _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
-                                                      _stream()), "hexgnn_qnet_backward_flat_td")
+            if live is not None:
+                # capacity-sized buffers: the weight-gradient GEMM takes the live row count from the device
+                _lib.check(L.hexgnn_qnet_backward_flat_td_live(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
+                                                               live.data_ptr(), _stream()), "hexgnn_qnet_backward_flat_td_live")
+            else:
+                _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
+                                                          _stream()), "hexgnn_qnet_backward_flat_td")
         else:
             _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, mid, tot, _stream()), "hexgnn_qnet_backward_flat")
         if split and defer_lower:
@@ -1498,19 +1510,38 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
 
     ``defer_lower=True`` returns ``(loss, td, q, call)`` with only the first stage of the staged backward issued (see
     ``qnet_backward``); ``finish_backward(call)`` issues the rest (a no-op returning (None, 0) where the step did not
-    take the fused path and ran whole)."""
+    take the fused path and ran whole).
+
+    Capacity-sized batches (``GraphReplayBuffer.sample_device``): ``x._hex_live_rows``, a 1-element int32 device tensor, says
+    how many of the rows hold graphs (``ptr[-1]``); rows at or behind it are never read -- the per-graph kernels work from
+    ``ptr``, the batched weight-gradient GEMM takes the count from the device (``hexgnn_qnet_backward_flat_td_live``).  Only the
+    fused form above in exact fp32 takes such a batch: anything else raises ``NotImplementedError``."""
     if not x.is_cuda:
         raise _lib.HexGnnError("td_step runs only on the MI355X HIP path (no CPU fallback)")
+    live = getattr(x, "_hex_live_rows", None)
+    if live is not None:
+        if not (torch.is_tensor(live) and live.is_cuda and live.dtype == torch.int32 and live.numel() == 1):
+            raise ValueError("x._hex_live_rows: a 1-element int32 device tensor")
+        if _MATH != 0 or defer_lower or _GRAD_STAGE_HOOK is not None or not _FUSED_ENABLED:
+            raise NotImplementedError("td_step over a capacity-sized batch (x._hex_live_rows) runs on the fused per-graph kernels "
+                                      "in exact fp32 only: no set_math(\"f16x3\"), no set_fused(False), no staged backward")
     sel, target, weights = _td_args(sel, target, weights, x.device)
     lfn = {"mse": 0, "huber": 1}[loss_fn]
     _TD_STEP.args = (sel, target, weights, lfn)
+    _TD_STEP.live = live
     try:
         q = model(x, edge_index, graph_indices, ptr)
     finally:
         _TD_STEP.args = None
+        _TD_STEP.live = None
     q = q.__dict__.get("_hex_plain", q)      # (td_step hands back the ordinary tensor, not the QValues wrapper)
     call = getattr(q, "_hex_call", None)
     td = call.td if call is not None else None
+    if live is not None and (td is None or call.live is None):
+        raise NotImplementedError("td_step over a capacity-sized batch (x._hex_live_rows): this model / batch does not take the "
+                                  "fused per-graph kernels (norm layers, a noisy head, hidden > 112, graphs above 128 nodes, "
+                                  "frozen or hooked parameters, or not one selected node per graph), and every other path "
+                                  "reads all rows of its buffers")
     if td is None:
         loss, tde = td_loss(q, sel, target, weights, loss_fn)
         direct = getattr(loss, "_hex_direct", None)

@@ -479,6 +479,23 @@ int hexgnn_qnet_backward_flat_td(int n, int b, int c_in, int hidden, int total_l
                                  void* workspace, size_t workspace_bytes, int* status,
                                  int stages, int layer_lo, int layer_hi,
                                  const float* loss_part /*[b]*/, float* loss /*[1]*/, hexgnn_stream_t stream);
+/* hexgnn_qnet_backward_flat_td over CAPACITY-sized buffers whose live row count is known on the device only (entry point added
+ * to ABI 6, nothing existing changes): n is the row count the buffers, the workspace and the launch shapes are planned for,
+ * *n_live (device, 0 <= *n_live <= n; larger values are clamped to n) the rows that hold graphs -- gptr[b] == *n_live.  Replaces
+ * the exact-size call of a replay draw whose sizes the host had to read back first.  The per-graph kernels work from gptr; the
+ * batched weight-gradient GEMM, the one kernel that walks rows by n, keeps the slice COUNT of n and spreads the live rows over
+ * those slices on the device (rows per slice = ceil(*n_live / slices) rounded up to 32; slices behind the live rows write zero
+ * slabs), so rows at or behind *n_live are never read.  *n_live == n gives the bits of hexgnn_qnet_backward_flat_td.
+ * Exact fp32 only: math 1 returns HEXGNN_EUNSUPPORTED, n_live == NULL HEXGNN_EINVAL, before any launch. */
+int hexgnn_qnet_backward_flat_td_live(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int math,
+                                      const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
+                                      const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
+                                      const float* lin_w, const float* v0_w, const float* v1_w,
+                                      const float* dq, float* d_embeds, float* flat, const int64_t* offsets /* HOST */,
+                                      void* workspace, size_t workspace_bytes, int* status,
+                                      int stages, int layer_lo, int layer_hi,
+                                      const float* loss_part /*[b]*/, float* loss /*[1]*/, const int* n_live /* device */,
+                                      hexgnn_stream_t stream);
 
 /* ---- double-DQN targets: several weight sets over ONE batch in one load-balanced forward launch.  Entry points added to
  *      ABI 6 (nothing existing changes).  The RainbowDQN update (README.md:5,7: the double-DQN step) runs the
@@ -589,6 +606,18 @@ int hexgnn_per_update_td(int capacity_pow2, int k, const void* idx, int idx_bits
                          double* max_priority, double* sum_tree, double* min_tree, hexgnn_stream_t stream);
 int hexgnn_per_sample(int capacity_pow2, int size, int b, double beta, const double* u, const double* sum_tree,
                       const double* min_tree, int* out_idx, float* out_w, hexgnn_stream_t stream);
+/* Replay draws sized on the device (entry points added to ABI 6, nothing existing changes).
+ * hexgnn_per_sample_dev is hexgnn_per_sample with size[1] (int32) and beta[1] (fp64) read from DEVICE memory: both change
+ * while a run goes on, and a captured graph must not bake them in (a fill level outside [1, capacity] is clamped).  Same bits.
+ * hexgnn_replay_offsets replaces the host-side cumsum over the drawn slots' graph sizes (and the read-back of the drawn slots
+ * it needed): sizes [n_slots][2] int32 (device) = (nodes, directed edges) of every stored state, slots [k] int32 (device) the
+ * draw; slot i + shift is looked up (shift 0: the states, shift capacity: the next states; outside [0, n_slots): an empty
+ * graph).  node_off / edge_off [k + 1] int32 feed hexgnn_states_observe, ptr [k + 1] int64 (may be NULL) is Batch.ptr; the last
+ * entries are the live totals.  Any k >= 0 (one wave walks the list with running totals). */
+int hexgnn_per_sample_dev(int capacity_pow2, const int* size, int b, const double* beta, const double* u,
+                          const double* sum_tree, const double* min_tree, int* out_idx, float* out_w, hexgnn_stream_t stream);
+int hexgnn_replay_offsets(int k, const int* slots, int shift, int n_slots, const int* sizes, int* node_off, int* edge_off,
+                          int64_t* ptr, hexgnn_stream_t stream);
 
 /* ---- in-library kernel timing: HIP events recorded on the launch stream around every launch of ONE
  *      kernel class (bench.py's live roofline measurement; torch.cuda.Event would only see torch's current

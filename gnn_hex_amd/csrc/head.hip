@@ -1,11 +1,14 @@
-// Head tail: per-node advantage Linear(H,1), 4-way graph pooling [sum|max|min|mean], value MLP
-// Linear(4H,H/2)->relu->Linear(H/2,1) and the dueling combine, one workgroup per graph.
+// The two dueling head tails, one workgroup per graph, with their plans, launch_head_param_grads / launch_lin_grad_reduce and
+// the hexgnn_head_* entry points.
+// MLP value head: per-node advantage Linear(H,1), 4-way graph pooling [sum|max|min|mean], value MLP
+// Linear(4H,H/2)->relu->Linear(H/2,1) and the dueling combine.  Linear value head (two_headed family): further down.
 //
 // Reference: HeadNetwork.forward GN0/models.py:374-384, MLP GN0/models.py:36-82,
 // DuellingTwoHeaded.forward GN0/models.py:567-584, torch_scatter.scatter (sum/max/min/mean).
 // HBM/L2-bound (reads h once forward, writes dh once backward); no MFMA: the dense parts are
 // [1 x 4H] x [4H x H/2] per graph.
 #include "hexgnn_internal.h"
+#include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
@@ -33,21 +36,6 @@ HeadWs head_ws_plan(int n, int b, int hidden) {
     w.part_off = off; off += align_up(sizeof(float) * (size_t)(b > 0 ? b : 1) * (hp + 1), 256);
     w.total = off;
     return w;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float* s4) {
-    // fixed-shape reduction (wave butterflies + 4 partials): deterministic
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s4[0] + s4[1] + s4[2] + s4[3];
 }
 
 // block = 256 threads (4 waves), one graph per block
@@ -396,15 +384,9 @@ __global__ __launch_bounds__(256) void head_value_wgrad_kernel(int b, int H, con
     const int H2 = H / 2, H4 = 4 * H;
     const int k = blockIdx.y;
     const int tid = threadIdx.x, cl = tid & 63, ph = tid >> 6;
-    if (k == H2) {      // the extra row of workgroups: the advantage linear's gradient from the per-graph partials (one wave
-                        // per column, same order as head_lin_grad_reduce_kernel)
-        for (int c = blockIdx.x * 4 + ph; c <= H; c += 4 * gridDim.x) {
-            const int src = c < H ? c : hp;
-            float s = 0.f;
-            for (int g = cl; g < b; g += 64) s += lin_part[(size_t)g * (hp + 1) + src];
-            s = wave_sum(s);
-            if (cl == 0) { if (c < H) d_lin_w[c] = s; else d_lin_b[0] = s; }
-        }
+    if (k == H2) {      // the extra row of workgroups: the advantage linear's gradient from the per-graph partials
+        for (int c = blockIdx.x * 4 + ph; c <= H; c += 4 * gridDim.x)
+            lin_part_column_sum(b, hp, H, lin_part, c, cl, d_lin_w, d_lin_b);
         return;
     }
     const int c = blockIdx.x * 64 + cl;
@@ -416,31 +398,16 @@ __global__ __launch_bounds__(256) void head_value_wgrad_kernel(int b, int H, con
     if (ph > 0) red[ph - 1][cl] = s;
     __syncthreads();
     if (ph == 0 && c < H4) d_v0_w[(size_t)k * H4 + c] = s + red[0][cl] + red[1][cl] + red[2][cl];
-    if (blockIdx.x == 0) {
-        // d_v0_b[k], d_v1_w[k] (wave 0 / wave 1), d_v1_b (block k == 0, wave 2)
-        const int lane = tid & 63, wave = tid >> 6;
-        float p = 0.f;
-        if (wave == 0) { for (int g = lane; g < b; g += 64) p += dz[(size_t)g * H2 + k]; }
-        else if (wave == 1) { for (int g = lane; g < b; g += 64) p += dvr[g] * z[(size_t)g * H2 + k]; }
-        else if (wave == 2 && k == 0) { for (int g = lane; g < b; g += 64) p += dvr[g]; }
-        p = wave_sum(p);
-        if (lane == 0) {
-            if (wave == 0) d_v0_b[k] = p;
-            else if (wave == 1) d_v1_w[k] = p;
-            else if (wave == 2 && k == 0) d_v1_b[0] = p;
-        }
-    }
+    if (blockIdx.x == 0) value_small_grads(b, H2, k, cl, ph, dz, dvr, z, d_v0_b, d_v1_w, d_v1_b);
 }
 
 // advantage Linear gradient: sum the per-graph partials; one wave per output column (hp+1 of them)
 __global__ __launch_bounds__(64) void head_lin_grad_reduce_kernel(int b, int hp, int H, const float* __restrict__ part,
                                                                  float* __restrict__ d_lin_w, float* __restrict__ d_lin_b) {
-    const int c = blockIdx.x, lane = threadIdx.x;   // c in [0, H]  (H == bias)
-    const int src = c < H ? c : hp;
-    float s = 0.f;
-    for (int g = lane; g < b; g += 64) s += part[(size_t)g * (hp + 1) + src];
-    s = wave_sum(s);
-    if (lane == 0) { if (c < H) d_lin_w[c] = s; else d_lin_b[0] = s; }
+    lin_part_column_sum(b, hp, H, part, blockIdx.x, threadIdx.x, d_lin_w, d_lin_b);
+}
+void launch_lin_grad_reduce(int b, int hp, int hidden, const float* part, float* d_w, float* d_b, hipStream_t st) {
+    head_lin_grad_reduce_kernel<<<hidden + 1, 64, 0, st>>>(b, hp, hidden, part, d_w, d_b);
 }
 
 // ---- head tail of the two_headed family (GN0/models.py:901-918): value_head_type="linear" over value_aggr_types=("mean",),
@@ -602,194 +569,6 @@ __global__ __launch_bounds__(256) void head_linear_bwd_kernel(
     }
 }
 
-// ---- HexAra policy head pieces (GN0/torch_script_models.py:286-379) ----------------------------------------------------------
-// (a) the policy head's LAST layer is a SAGEConv(H, 1) (ModifiedBaseNet with out_channels=1, lines 123-144, 296):
-//       out_i = b + w_r . h_i + mean_{j in N(i)} w_l . h_j
-//     two dot products per row, then the mean of a scalar over the CSR: HBM-bound, no MFMA.
-__global__ __launch_bounds__(256) void sage_scalar_dots_kernel(int n, int H, int hp, const float* __restrict__ h,
-                                                              const float* __restrict__ wl, const float* __restrict__ wr,
-                                                              float* __restrict__ s /*[n][2]*/) {
-    __shared__ __attribute__((aligned(16))) float s_l[128], s_r[128];
-    const int tid = threadIdx.x;
-    if (tid < 128) { s_l[tid] = tid < H ? wl[tid] : 0.f; s_r[tid] = tid < H ? wr[tid] : 0.f; }
-    __syncthreads();
-    const int sub = tid & 3, q4n = hp / 4;
-    const int row = blockIdx.x * 64 + (tid >> 2);
-    if (row >= n) return;                                   // (the four lanes of a row leave together)
-    const f32x4* hr = reinterpret_cast<const f32x4*>(h + (size_t)row * hp);
-    float a = 0.f, u = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = sub + 4 * k;
-        if (c < q4n) {
-            const f32x4 hv = hr[c], lw = reinterpret_cast<const f32x4*>(s_l)[c], rw = reinterpret_cast<const f32x4*>(s_r)[c];
-            a += hv[0] * lw[0] + hv[1] * lw[1] + hv[2] * lw[2] + hv[3] * lw[3];
-            u += hv[0] * rw[0] + hv[1] * rw[1] + hv[2] * rw[2] + hv[3] * rw[3];
-        }
-    }
-    a += __shfl_xor(a, 1); a += __shfl_xor(a, 2);
-    u += __shfl_xor(u, 1); u += __shfl_xor(u, 2);
-    if (sub == 0) { s[2 * (size_t)row] = a; s[2 * (size_t)row + 1] = u; }
-}
-
-__global__ __launch_bounds__(256) void sage_scalar_gather_kernel(int n, const int* __restrict__ rowptr,
-                                                                const int* __restrict__ col, const float* __restrict__ invdeg,
-                                                                const float* __restrict__ s, const float* __restrict__ bias,
-                                                                float* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float acc = 0.f;
-    for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) acc += s[2 * (size_t)col[e]];       // ascending neighbour order
-    out[i] = bias[0] + s[2 * (size_t)i + 1] + invdeg[i] * acc;
-}
-
-// backward: ds_r = dout,  ds_l[j] = sum_{i in T(j)} dout_i / deg_i,  dh_j = ds_l[j] w_l + ds_r[j] w_r;
-// block partials (64 rows): lpart[blk] = (sum ds_l h | sum dout), rpart[blk] = (sum ds_r h | 0)
-__global__ __launch_bounds__(256) void sage_scalar_bwd_kernel(int n, int H, int hp, const int* __restrict__ rowptr_t,
-                                                             const int* __restrict__ col_t, const float* __restrict__ invdeg,
-                                                             const float* __restrict__ h, const float* __restrict__ wl,
-                                                             const float* __restrict__ wr, const float* __restrict__ dout,
-                                                             float* __restrict__ dh, float* __restrict__ lpart,
-                                                             float* __restrict__ rpart) {
-    __shared__ float s_l[128], s_r[128];
-    __shared__ float s_dl[64], s_dr[64];
-    __shared__ float s_acc[2][129];
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 64, r1 = min(n, r0 + 64);
-    if (tid < 128) { s_l[tid] = tid < H ? wl[tid] : 0.f; s_r[tid] = tid < H ? wr[tid] : 0.f; }
-    if (tid < 64) {
-        const int j = r0 + tid;
-        float dl = 0.f, dr = 0.f;
-        if (j < n) {
-            dr = dout[j];
-            for (int e = rowptr_t[j]; e < rowptr_t[j + 1]; ++e) { const int i = col_t[e]; dl += dout[i] * invdeg[i]; }
-        }
-        s_dl[tid] = dl;
-        s_dr[tid] = dr;
-    }
-    __syncthreads();
-    {
-        const int sub = tid & 3, q4n = hp / 4, row = r0 + (tid >> 2);
-        if (row < n) {
-            const float dl = s_dl[tid >> 2], dr = s_dr[tid >> 2];
-            f32x4* d = reinterpret_cast<f32x4*>(dh + (size_t)row * hp);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int q = sub + 4 * k;
-                if (q < q4n) {
-                    f32x4 v;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) { const int c = 4 * q + jj; v[jj] = c < H ? dl * s_l[c] + dr * s_r[c] : 0.f; }
-                    d[q] = v;
-                }
-            }
-        }
-    }
-    {
-        const int c = tid & 127, ph = tid >> 7;
-        float al = 0.f, ar = 0.f, ab = 0.f;
-        for (int row = r0 + ph; row < r1; row += 2) {
-            const float hv = c < hp ? h[(size_t)row * hp + c] : 0.f;
-            al += s_dl[row - r0] * hv;
-            ar += s_dr[row - r0] * hv;
-            ab += s_dr[row - r0];
-        }
-        if (ph == 1) { s_acc[0][c] = al; s_acc[1][c] = ar; if (c == 0) s_acc[0][128] = ab; }
-        __syncthreads();
-        if (ph == 0) {
-            if (c < hp) {
-                lpart[(size_t)blockIdx.x * (hp + 1) + c] = al + s_acc[0][c];
-                rpart[(size_t)blockIdx.x * (hp + 1) + c] = ar + s_acc[1][c];
-            }
-            if (c == 0) {
-                lpart[(size_t)blockIdx.x * (hp + 1) + hp] = ab + s_acc[0][128];
-                rpart[(size_t)blockIdx.x * (hp + 1) + hp] = 0.f;
-            }
-        }
-    }
-}
-
-// (b) output surgery + scatter_log_softmax (lines 326-378): per graph g the output segment holds the logits of its
-//     non-terminal nodes (rows gptr[g]+2 ..) and, when swapping is allowed in g, the graph's swap logit behind them;
-//     segment start = gptr[g] - 2g + (number of swap slots of graphs < g) = output_batch_ptr[g]; log-softmax per segment.
-//     swap flag of graph g (lines 337-347): feature 2 of the graph's LAST node for g < b-1, of its FIRST node for g = b-1.
-__device__ __forceinline__ int swap_flag(int g, int b, const int* gptr, const float* x, int xs, int swap_allowed) {
-    if (!swap_allowed) return 0;
-    const int row = g < b - 1 ? gptr[g + 1] - 1 : gptr[g];
-    return x[(size_t)row * xs + 2] != 0.f ? 1 : 0;
-}
-__device__ __forceinline__ float block_max_256(float v, float* s4) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(s4[0], s4[1]), fmaxf(s4[2], s4[3]));
-}
-__device__ __forceinline__ int block_isum_256(int v, int* s4) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s4[0] + s4[1] + s4[2] + s4[3];
-}
-
-__global__ __launch_bounds__(256) void policy_lsm_fwd_kernel(int b, const int* __restrict__ gptr, const float* __restrict__ x,
-                                                            int xs, int swap_allowed, const float* __restrict__ pi_raw,
-                                                            const float* __restrict__ should_swap, float* __restrict__ out_pi,
-                                                            int64_t* __restrict__ out_gi, int64_t* __restrict__ out_ptr) {
-    __shared__ float s4[4];
-    __shared__ int i4[4];
-    const int g = blockIdx.x, tid = threadIdx.x;
-    int before = 0;
-    for (int j = tid; j < g; j += 256) before += swap_flag(j, b, gptr, x, xs, swap_allowed);
-    before = block_isum_256(before, i4);
-    const int flag = swap_flag(g, b, gptr, x, xs, swap_allowed);
-    const int r0 = gptr[g] + 2, r1 = gptr[g + 1];
-    const int len = max(r1 - r0, 0) + flag;
-    const int64_t o0 = (int64_t)gptr[g] - 2 * (int64_t)g + before;
-    auto val = [&](int k) { return k < r1 - r0 ? pi_raw[r0 + k] : should_swap[g]; };
-    float mx = -INFINITY;
-    for (int k = tid; k < len; k += 256) mx = fmaxf(mx, val(k));
-    mx = block_max_256(mx, s4);
-    float se = 0.f;
-    for (int k = tid; k < len; k += 256) se += expf(val(k) - mx);
-    se = block_sum_256(se, s4);
-    const float lse = logf(se);
-    for (int k = tid; k < len; k += 256) {
-        out_pi[o0 + k] = val(k) - mx - lse;
-        out_gi[o0 + k] = g;
-    }
-    if (tid == 0) {
-        out_ptr[g] = o0;
-        if (g == b - 1) out_ptr[b] = o0 + len;
-    }
-}
-
-// d logit_k = d out_k - softmax_k * sum(d out);  terminal rows get 0
-__global__ __launch_bounds__(256) void policy_lsm_bwd_kernel(int b, const int* __restrict__ gptr, const float* __restrict__ x,
-                                                            int xs, int swap_allowed, const int64_t* __restrict__ out_ptr,
-                                                            const float* __restrict__ out_pi, const float* __restrict__ d_out,
-                                                            float* __restrict__ d_pi_raw, float* __restrict__ d_should_swap) {
-    __shared__ float s4[4];
-    const int g = blockIdx.x, tid = threadIdx.x;
-    const int flag = swap_flag(g, b, gptr, x, xs, swap_allowed);
-    const int r0 = gptr[g] + 2, r1 = gptr[g + 1];
-    const int nn = max(r1 - r0, 0), len = nn + flag;
-    const int64_t o0 = out_ptr[g];
-    float sd = 0.f;
-    for (int k = tid; k < len; k += 256) sd += d_out[o0 + k];
-    sd = block_sum_256(sd, s4);
-    for (int k = tid; k < len; k += 256) {
-        const float d = d_out[o0 + k] - expf(out_pi[o0 + k]) * sd;
-        if (k < nn) d_pi_raw[r0 + k] = d;
-        else d_should_swap[g] = d;
-    }
-    if (tid < 2 && gptr[g] + tid < r1) d_pi_raw[gptr[g] + tid] = 0.f;
-    if (tid == 0 && !flag && d_should_swap) d_should_swap[g] = 0.f;
-}
-
 int launch_head_param_grads(int b, int hidden, int mode, const float* dz, const float* dvr, const float* pooled,
                             const float* z, const float* lin_part, float* d_lin_w, float* d_lin_b, float* d_v0_w,
                             float* d_v0_b, float* d_v1_w, float* d_v1_b, hipStream_t st) {
@@ -798,203 +577,8 @@ int launch_head_param_grads(int b, int hidden, int mode, const float* dz, const 
         head_value_wgrad_kernel<<<dim3((H4 + 63) / 64, H2 + 1), 256, 0, st>>>(b, hidden, dz, dvr, pooled, z, d_v0_w, d_v0_b,
                                                                               d_v1_w, d_v1_b, hp, lin_part, d_lin_w, d_lin_b);
     else
-        head_lin_grad_reduce_kernel<<<hidden + 1, 64, 0, st>>>(b, hp, hidden, lin_part, d_lin_w, d_lin_b);
+        launch_lin_grad_reduce(b, hp, hidden, lin_part, d_lin_w, d_lin_b, st);
     return HEXGNN_OK;
-}
-
-
-// ---- TD loss on the selected nodes: loss = mean_j w_j * l(q[sel_j] - tgt_j), l = d^2 ("mse") or Huber(delta 1) -----------
-// The reference's training loop gathers Q(s, a) with torch indexing and calls the loss in torch (Rainbow agent,
-// --loss_fn=mse, importance weights of the prioritized replay): ~15 tiny kernels forward + backward (gather, sub, pow,
-// mean, sort-based index_put ...).  Here: one single-workgroup kernel forward (fixed-shape tree => deterministic) and
-// one memset + one scatter kernel backward.  td[j] = q[sel_j] - tgt_j is returned for the priority update.
-__global__ __launch_bounds__(256) void td_loss_fwd_kernel(int n, int k, const float* __restrict__ q,
-                                                         const int64_t* __restrict__ sel, const float* __restrict__ tgt,
-                                                         const float* __restrict__ w, int loss_fn,
-                                                         float* __restrict__ loss, float* __restrict__ td) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int j = threadIdx.x; j < k; j += 256) {
-        const int64_t i = sel[j];
-        const float d = (i >= 0 && i < n) ? q[i] - tgt[j] : 0.f;
-        td[j] = d;
-        const float a = fabsf(d);
-        const float l = loss_fn == 0 ? d * d : (a <= 1.f ? 0.5f * d * d : a - 0.5f);
-        acc += (w ? w[j] : 1.f) * l;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0] / (float)(k > 0 ? k : 1);
-}
-
-// One launch: every workgroup clears its 1024-entry range of dq, then accumulates the selected nodes that fall into it
-// (the zeroing memset used to be a launch of its own).  Bit-reproducible with duplicated selections (PER samples with
-// replacement): an LDS counter per node of the range says how many entries of the current 1024-entry chunk name it (integer
-// atomics: order-free).  A node named once in the chunk gets one add (chunks are barrier-separated, so its adds arrive in
-// chunk order); a node named twice or more is summed in list order by its first entry and added once.  (Until round 3 two
-// entries went through two float atomics: order-free only onto a ZERO word, i.e. wrong from the second chunk on -- lists
-// above 1024 entries were not bit-reproducible; found by the 2300-entry test of the one-launch form.)
-__global__ __launch_bounds__(256) void td_loss_bwd_kernel(int n, int k, const int64_t* __restrict__ sel,
-                                                         const float* __restrict__ td, const float* __restrict__ w,
-                                                         int loss_fn, const float* __restrict__ gloss,
-                                                         float* __restrict__ dq) {
-    __shared__ __attribute__((aligned(16))) int s_i[1024];
-    __shared__ __attribute__((aligned(16))) float s_g[1024];
-    __shared__ int s_cnt[1024];
-    const int lo = blockIdx.x * 1024, hi = min(lo + 1024, n);
-    for (int i = lo + threadIdx.x; i < hi; i += 256) dq[i] = 0.f;
-    const float gl = gloss[0] / (float)k;
-    for (int c0 = 0; c0 < k; c0 += 1024) {
-        const int kk = min(1024, k - c0);
-        __syncthreads();
-        for (int j = threadIdx.x; j < 1024; j += 256) { s_cnt[j] = 0; s_i[j] = -1; s_g[j] = 0.f; }
-        __syncthreads();
-        for (int j = threadIdx.x; j < kk; j += 256) {
-            const int64_t i = sel[c0 + j];
-            const bool mine = i >= lo && i < hi;
-            const float d = td[c0 + j];
-            const float dl = loss_fn == 0 ? 2.f * d : fminf(fmaxf(d, -1.f), 1.f);
-            s_i[j] = mine ? (int)i : -1;
-            s_g[j] = gl * (w ? w[c0 + j] : 1.f) * dl;
-            if (mine) atomicAdd(&s_cnt[(int)i - lo], 1);
-        }
-        __syncthreads();
-        for (int j = threadIdx.x; j < kk; j += 256) {
-            const int i = s_i[j];
-            if (i < 0) continue;                       // not in this workgroup's range (most entries)
-            if (s_cnt[i - lo] == 1) { atomicAdd(dq + i, s_g[j]); continue; }
-            // three or more: is an earlier entry naming the same node? sum of the later ones, in list order
-            bool first = true;
-            float acc = s_g[j];
-            for (int q4 = 0; q4 < (kk + 3) / 4; ++q4) {
-                const int4 ii = reinterpret_cast<const int4*>(s_i)[q4];
-                const f32x4 gg = reinterpret_cast<const f32x4*>(s_g)[q4];
-                const int q = 4 * q4;
-                first = first && !((ii.x == i && q < j) || (ii.y == i && q + 1 < j) || (ii.z == i && q + 2 < j) ||
-                                   (ii.w == i && q + 3 < j));
-                acc += (ii.x == i && q > j) ? gg[0] : 0.f;
-                acc += (ii.y == i && q + 1 > j) ? gg[1] : 0.f;
-                acc += (ii.z == i && q + 2 > j) ? gg[2] : 0.f;
-                acc += (ii.w == i && q + 3 > j) ? gg[3] : 0.f;
-            }
-            if (first) atomicAdd(dq + i, acc);   // one add per node and chunk (chunks of 1024 entries are barrier-separated)
-        }
-    }
-}
-
-
-// Forward AND backward of the TD loss in ONE launch (the DQN update differentiates the loss itself, so d loss / d q is
-// known the moment the loss is: grad_loss == 1): every workgroup owns a 1024-node range of dq exactly as
-// td_loss_bwd_kernel does, with td_j = q[sel_j] - target_j formed on the fly; workgroup 0 additionally writes td[] and the
-// mean.  Same fixed-shape sums / commuting atomics as the two-launch form: bit-identical results.
-__global__ __launch_bounds__(256) void td_loss_fused_kernel(int n, int k, const float* __restrict__ q,
-                                                           const int64_t* __restrict__ sel, const float* __restrict__ tgt,
-                                                           const float* __restrict__ w, int loss_fn,
-                                                           float* __restrict__ loss, float* __restrict__ td,
-                                                           float* __restrict__ dq) {
-    __shared__ __attribute__((aligned(16))) int s_i[1024];
-    __shared__ __attribute__((aligned(16))) float s_g[1024];
-    __shared__ int s_cnt[1024];
-    __shared__ float red[256];
-    const int lo = blockIdx.x * 1024, hi = min(lo + 1024, n);
-    for (int i = lo + threadIdx.x; i < hi; i += 256) dq[i] = 0.f;
-    const float gl = 1.f / (float)(k > 0 ? k : 1);
-    float acc_loss = 0.f;
-    for (int c0 = 0; c0 < k; c0 += 1024) {
-        const int kk = min(1024, k - c0);
-        __syncthreads();
-        for (int j = threadIdx.x; j < 1024; j += 256) { s_cnt[j] = 0; s_i[j] = -1; s_g[j] = 0.f; }
-        __syncthreads();
-        for (int j = threadIdx.x; j < kk; j += 256) {
-            const int64_t i = sel[c0 + j];
-            const bool inside = i >= 0 && i < n;
-            const bool mine = i >= lo && i < hi;
-            const float d = inside ? q[i] - tgt[c0 + j] : 0.f;
-            const float wj = w ? w[c0 + j] : 1.f;
-            if (blockIdx.x == 0) {
-                td[c0 + j] = d;
-                const float a = fabsf(d);
-                acc_loss += wj * (loss_fn == 0 ? d * d : (a <= 1.f ? 0.5f * d * d : a - 0.5f));
-            }
-            const float dl = loss_fn == 0 ? 2.f * d : fminf(fmaxf(d, -1.f), 1.f);
-            s_i[j] = mine ? (int)i : -1;
-            s_g[j] = gl * wj * dl;
-            if (mine) atomicAdd(&s_cnt[(int)i - lo], 1);
-        }
-        __syncthreads();
-        for (int j = threadIdx.x; j < kk; j += 256) {
-            const int i = s_i[j];
-            if (i < 0) continue;
-            if (s_cnt[i - lo] == 1) { atomicAdd(dq + i, s_g[j]); continue; }
-            bool first = true;
-            float acc = s_g[j];
-            for (int q4 = 0; q4 < (kk + 3) / 4; ++q4) {
-                const int4 ii = reinterpret_cast<const int4*>(s_i)[q4];
-                const f32x4 gg = reinterpret_cast<const f32x4*>(s_g)[q4];
-                const int qq = 4 * q4;
-                first = first && !((ii.x == i && qq < j) || (ii.y == i && qq + 1 < j) || (ii.z == i && qq + 2 < j) ||
-                                   (ii.w == i && qq + 3 < j));
-                acc += (ii.x == i && qq > j) ? gg[0] : 0.f;
-                acc += (ii.y == i && qq + 1 > j) ? gg[1] : 0.f;
-                acc += (ii.z == i && qq + 2 > j) ? gg[2] : 0.f;
-                acc += (ii.w == i && qq + 3 > j) ? gg[3] : 0.f;
-            }
-            if (first) atomicAdd(dq + i, acc);
-        }
-    }
-    if (blockIdx.x == 0) {      // the mean, in td_loss_fwd_kernel's reduction shape (thread t sums entries t, t+256, ...)
-        red[threadIdx.x] = acc_loss;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) loss[0] = red[0] / (float)(k > 0 ? k : 1);
-    }
-}
-
-
-// ---- acting: per-graph epsilon-greedy / argmax over the non-terminal nodes, mapped to vertex ids ----------------------
-// One wave per graph.  Greedy = first node attaining the maximum of q[gptr[g]+2 : gptr[g+1]] (torch.argmax tie rule;
-// GN0/RainbowDQN/evaluate_elo.py:253-266); with u given, env g explores when u[2g] < eps and then plays node
-// 2 + floor(u[2g+1] * (n_g - 2)).  Outputs the node rank inside its graph, the vertex id (backmap, what
-// Env_manager.validate_actions returns, multi_env_manager.py:62-64) and the exploratory flag.
-__global__ __launch_bounds__(64) void select_actions_kernel(int b, const int* __restrict__ gptr, const float* __restrict__ q,
-                                                          const int64_t* __restrict__ backmap, float eps,
-                                                          const float* __restrict__ u, int* __restrict__ act_vertex,
-                                                          int* __restrict__ act_rank, unsigned char* __restrict__ expl) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const int r0 = gptr[g], r1 = gptr[g + 1];
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int i = r0 + 2 + lane; i < r1; i += 64) {
-        const float v = q[i];
-        if (v > best || (v == best && i < arg)) { best = v; arg = i; }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(arg, off);
-        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (lane == 0) {
-        int rank = arg == 0x7fffffff ? -1 : arg - r0;      // -1: graph without a legal move
-        unsigned char ex = 0;
-        const int nact = r1 - r0 - 2;
-        if (u && nact > 0 && u[2 * g] < eps) {
-            int k = (int)(u[2 * g + 1] * (float)nact);
-            if (k >= nact) k = nact - 1;
-            rank = 2 + k;
-            ex = 1;
-        }
-        act_rank[g] = rank;
-        if (act_vertex) act_vertex[g] = rank >= 0 ? (backmap ? (int)backmap[r0 + rank] : rank) : -1;
-        if (expl) expl[g] = ex;
-    }
 }
 
 }  // namespace hexgnn
@@ -1002,40 +586,6 @@ __global__ __launch_bounds__(64) void select_actions_kernel(int b, const int* __
 using namespace hexgnn;
 
 extern "C" {
-
-int hexgnn_select_actions(int b, const int* gptr, const float* q, const int64_t* backmap, float eps, const float* u,
-                          int* action_vertex, int* action_rank, uint8_t* exploratory, hexgnn_stream_t stream_) {
-    if (b < 0 || (b > 0 && (!gptr || !q || !action_rank))) return HEXGNN_EINVAL;
-    if (b == 0) return HEXGNN_OK;
-    select_actions_kernel<<<b, 64, 0, (hipStream_t)stream_>>>(b, gptr, q, backmap, eps, u, action_vertex, action_rank,
-                                                              exploratory);
-    return check_launch();
-}
-
-int hexgnn_td_loss_forward(int n, int k, const float* q, const int64_t* sel, const float* target, const float* weights,
-                           int loss_fn, float* loss, float* td, hexgnn_stream_t stream_) {
-    if (n < 0 || k < 0 || loss_fn < 0 || loss_fn > 1 || !loss || (k > 0 && (!q || !sel || !target || !td))) return HEXGNN_EINVAL;
-    td_loss_fwd_kernel<<<1, 256, 0, (hipStream_t)stream_>>>(n, k, q, sel, target, weights, loss_fn, loss, td);
-    return check_launch();
-}
-
-int hexgnn_td_loss_backward(int n, int k, const int64_t* sel, const float* td, const float* weights, int loss_fn,
-                            const float* grad_loss, float* dq, hexgnn_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    if (n < 0 || k < 0 || loss_fn < 0 || loss_fn > 1 || !grad_loss || (n > 0 && !dq) || (k > 0 && (!sel || !td))) return HEXGNN_EINVAL;
-    if (n > 0) td_loss_bwd_kernel<<<(n + 1023) / 1024, 256, 0, st>>>(n, k, sel, td, weights, loss_fn, grad_loss, dq);
-    return check_launch();
-}
-
-int hexgnn_td_loss_forward_backward(int n, int k, const float* q, const int64_t* sel, const float* target,
-                                    const float* weights, int loss_fn, float* loss, float* td, float* dq,
-                                    hexgnn_stream_t stream_) {
-    if (n < 0 || k < 0 || loss_fn < 0 || loss_fn > 1 || !loss || (n > 0 && !dq) || (k > 0 && (!q || !sel || !target || !td)))
-        return HEXGNN_EINVAL;
-    td_loss_fused_kernel<<<n > 0 ? (n + 1023) / 1024 : 1, 256, 0, (hipStream_t)stream_>>>(n, k, q, sel, target, weights,
-                                                                                        loss_fn, loss, td, dq);
-    return check_launch();
-}
 
 size_t hexgnn_head_saved_bytes(int n, int b, int hidden) {
     if (n < 0 || b < 0 || padded_width_wide(hidden) < 0) return 0;
@@ -1164,72 +714,8 @@ int hexgnn_head_linear_backward(int n, int b, int hidden, int mode, const int* g
         head_linear_bwd_kernel<<<b, 256, 0, st>>>(hidden, hp, mode, gptr, h, lin_w, val_w, (const float*)(sv + s.adv_off),
                                                   (const float*)(sv + s.v_off), dq, d_out_v, dh, (float*)(ws + w.dvr_off),
                                                   lpart, vpart, mask_dh);
-    head_lin_grad_reduce_kernel<<<hidden + 1, 64, 0, st>>>(b, hp, hidden, lpart, d_lin_w, d_lin_b);
-    if (has_value) head_lin_grad_reduce_kernel<<<hidden + 1, 64, 0, st>>>(b, hp, hidden, vpart, d_val_w, d_val_b);
-    return check_launch();
-}
-
-int hexgnn_sage_scalar_forward(int n, int hidden, const int* rowptr, const int* col, const float* invdeg, const float* h,
-                               const float* wl, const float* wr, const float* bias, float* out, float* dots,
-                               hexgnn_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    const int hp = padded_width(hidden);
-    if (hp < 0) return HEXGNN_EUNSUPPORTED;
-    if (n < 0 || !wl || !wr || !bias || (n > 0 && (!rowptr || !col || !invdeg || !h || !out || !dots))) return HEXGNN_EINVAL;
-    if (n == 0) return HEXGNN_OK;
-    sage_scalar_dots_kernel<<<(n + 63) / 64, 256, 0, st>>>(n, hidden, hp, h, wl, wr, dots);
-    sage_scalar_gather_kernel<<<(n + 255) / 256, 256, 0, st>>>(n, rowptr, col, invdeg, dots, bias, out);
-    return check_launch();
-}
-
-size_t hexgnn_sage_scalar_backward_workspace_bytes(int n, int hidden) {
-    const int hp = padded_width(hidden);
-    if (n < 0 || hp < 0) return 0;
-    return 2 * align_up(sizeof(float) * (size_t)((n + 63) / 64 + 1) * (hp + 1), 256);
-}
-
-int hexgnn_sage_scalar_backward(int n, int hidden, const int* rowptr_t, const int* col_t, const float* invdeg,
-                                const float* h, const float* wl, const float* wr, const float* dout, float* dh,
-                                float* d_wl, float* d_wr, float* d_bias, void* workspace, size_t workspace_bytes,
-                                hexgnn_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    const int hp = padded_width(hidden);
-    if (hp < 0) return HEXGNN_EUNSUPPORTED;
-    if (n < 0 || !wl || !wr || !d_wl || !d_wr || !d_bias) return HEXGNN_EINVAL;
-    if (n > 0 && (!rowptr_t || !col_t || !invdeg || !h || !dout || !dh)) return HEXGNN_EINVAL;
-    if (!workspace || workspace_bytes < hexgnn_sage_scalar_backward_workspace_bytes(n, hidden)) return HEXGNN_EWORKSPACE;
-    const int nblk = (n + 63) / 64;
-    float* lpart = (float*)workspace;
-    float* rpart = (float*)((char*)workspace + align_up(sizeof(float) * (size_t)(nblk + 1) * (hp + 1), 256));
-    if (nblk > 0)
-        sage_scalar_bwd_kernel<<<nblk, 256, 0, st>>>(n, hidden, hp, rowptr_t, col_t, invdeg, h, wl, wr, dout, dh, lpart, rpart);
-    // (the right part's bias slot is zero: its sum lands in the scratch float behind the partials)
-    head_lin_grad_reduce_kernel<<<hidden + 1, 64, 0, st>>>(nblk, hp, hidden, lpart, d_wl, d_bias);
-    head_lin_grad_reduce_kernel<<<hidden + 1, 64, 0, st>>>(nblk, hp, hidden, rpart, d_wr, rpart + (size_t)nblk * (hp + 1));
-    return check_launch();
-}
-
-int hexgnn_policy_log_softmax_forward(int n, int b, const int* gptr, const float* x, int x_stride, int swap_allowed,
-                                      const float* pi_raw, const float* should_swap, float* out_pi, int64_t* out_gi,
-                                      int64_t* out_ptr, hexgnn_stream_t stream_) {
-    if (n < 0 || b < 0 || !out_ptr) return HEXGNN_EINVAL;
-    if (b > 0 && (!gptr || !pi_raw || !out_pi || !out_gi)) return HEXGNN_EINVAL;
-    if (swap_allowed && b > 0 && (!x || x_stride < 3 || !should_swap)) return HEXGNN_EINVAL;
-    if (b == 0) { (void)hipMemsetAsync(out_ptr, 0, sizeof(int64_t), (hipStream_t)stream_); return check_launch(); }
-    policy_lsm_fwd_kernel<<<b, 256, 0, (hipStream_t)stream_>>>(b, gptr, x, x_stride, swap_allowed, pi_raw, should_swap, out_pi,
-                                                              out_gi, out_ptr);
-    return check_launch();
-}
-
-int hexgnn_policy_log_softmax_backward(int n, int b, const int* gptr, const float* x, int x_stride, int swap_allowed,
-                                       const int64_t* out_ptr, const float* out_pi, const float* d_out, float* d_pi_raw,
-                                       float* d_should_swap, hexgnn_stream_t stream_) {
-    if (n < 0 || b < 0) return HEXGNN_EINVAL;
-    if (b > 0 && (!gptr || !out_ptr || !out_pi || !d_out || !d_pi_raw)) return HEXGNN_EINVAL;
-    if (swap_allowed && b > 0 && (!x || x_stride < 3 || !d_should_swap)) return HEXGNN_EINVAL;
-    if (b == 0) return HEXGNN_OK;
-    policy_lsm_bwd_kernel<<<b, 256, 0, (hipStream_t)stream_>>>(b, gptr, x, x_stride, swap_allowed, out_ptr, out_pi, d_out,
-                                                              d_pi_raw, d_should_swap);
+    launch_lin_grad_reduce(b, hp, hidden, lpart, d_lin_w, d_lin_b, st);
+    if (has_value) launch_lin_grad_reduce(b, hp, hidden, vpart, d_val_w, d_val_b, st);
     return check_launch();
 }
 

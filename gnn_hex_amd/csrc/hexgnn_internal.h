@@ -1,5 +1,5 @@
 // Cross-translation-unit internals of libhexgnn.so (plans + launch helpers shared by the layer-major
-// path in sage*.hip / head.hip and the fused per-graph path in qnet_fused.hip).
+// path in sage*.hip / head.hip / hexara_head.hip and the fused per-graph path in qnet_fused*.hip).
 #pragma once
 #include "hexgnn_common.h"
 
@@ -91,5 +91,7 @@ HeadWs head_ws_plan(int n, int b, int hidden);
 int launch_head_param_grads(int b, int hidden, int mode, const float* dz, const float* dvr, const float* pooled,
                             const float* z, const float* lin_part, float* d_lin_w, float* d_lin_b, float* d_v0_w,
                             float* d_v0_b, float* d_v1_w, float* d_v1_b, hipStream_t st);
+// d_w[c] = sum_g part[g][c] (c < hidden), d_b[0] = sum_g part[g][hp] over b rows of hp + 1 partials, one wave per output
+void launch_lin_grad_reduce(int b, int hp, int hidden, const float* part, float* d_w, float* d_b, hipStream_t st);
 
 }  // namespace hexgnn

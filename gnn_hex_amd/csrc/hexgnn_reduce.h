@@ -1,0 +1,80 @@
+// The small fixed-shape reductions of libhexgnn.so, one copy each: every sum and comparison below has an order that depends on
+// nothing but the launch shape, so kernels that promise each other's bits call the same function instead of repeating it.
+#pragma once
+#include "hexgnn_common.h"
+
+namespace hexgnn {
+
+// sum over the 64 lanes of a wave (xor butterfly 32 .. 1); every lane receives the total
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// sum over a 256-thread block: wave butterflies + the four partials in wave order; every thread receives the total
+__device__ __forceinline__ float block_sum_256(float v, float* s4) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s4[0] + s4[1] + s4[2] + s4[3];
+}
+
+// mean over `count` entries of which thread t of a 256-thread block has summed t, t + 256, ... into acc: halving tree over
+// red[256], then one division (the shape of every TD-loss mean)
+__device__ __forceinline__ float tree_mean_256(float acc, float* red, int count) {
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return red[0] / (float)(count > 0 ? count : 1);
+}
+
+// One wave: first row attaining the maximum of q over a graph's non-terminal rows [r0 + 2, r1) (torch.argmax tie rule: among
+// equal values the lowest index).  Every lane receives best / arg; a graph without such a row leaves arg = 0x7fffffff.
+__device__ __forceinline__ void graph_first_max(const float* q, int r0, int r1, int lane, float& best, int& arg) {
+    best = -INFINITY;
+    arg = 0x7fffffff;
+    for (int i = r0 + 2 + lane; i < r1; i += 64) {
+        const float v = q[i];
+        if (v > best || (v == best && i < arg)) { best = v; arg = i; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oa = __shfl_xor(arg, off);
+        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+}
+
+// ---- the head's small parameter-gradient sums over the graphs, one wave per output (lanes stride over the graphs) ------------
+// advantage Linear: column c in [0, H] (H == bias, kept at column hp) of the per-graph partials lin_part [b][hp + 1]
+__device__ __forceinline__ void lin_part_column_sum(int b, int hp, int H, const float* lin_part, int c, int lane,
+                                                    float* d_lin_w, float* d_lin_b) {
+    const int src = c < H ? c : hp;
+    float s = 0.f;
+    for (int g = lane; g < b; g += 64) s += lin_part[(size_t)g * (hp + 1) + src];
+    s = wave_sum(s);
+    if (lane == 0) { if (c < H) d_lin_w[c] = s; else d_lin_b[0] = s; }
+}
+
+// value MLP, hidden unit k: wave 0 d_v0_b[k], wave 1 d_v1_w[k], wave 2 (k == 0 only) d_v1_b; further waves idle
+__device__ __forceinline__ void value_small_grads(int b, int H2, int k, int lane, int wave, const float* dz,
+                                                  const float* dvr, const float* z, float* d_v0_b, float* d_v1_w,
+                                                  float* d_v1_b) {
+    float p = 0.f;
+    if (wave == 0) { for (int g = lane; g < b; g += 64) p += dz[(size_t)g * H2 + k]; }
+    else if (wave == 1) { for (int g = lane; g < b; g += 64) p += dvr[g] * z[(size_t)g * H2 + k]; }
+    else if (wave == 2 && k == 0) { for (int g = lane; g < b; g += 64) p += dvr[g]; }
+    p = wave_sum(p);
+    if (lane == 0) {
+        if (wave == 0) d_v0_b[k] = p;
+        else if (wave == 1) d_v1_w[k] = p;
+        else if (wave == 2 && k == 0) d_v1_b[0] = p;
+    }
+}
+
+}  // namespace hexgnn

@@ -11,6 +11,7 @@
 // layer without ReLU, then this norm).  HBM-bound: forward = one read for the statistics + one read / one write to apply.
 // Reductions are block partials in fp64 combined in a fixed order: deterministic and accurate to fp32 rounding.
 #include "hexgnn_internal.h"
+#include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
@@ -224,8 +225,7 @@ __global__ __launch_bounds__(64) void norm_bwd_cols_kernel(int H, int hp, const 
     const int c = blockIdx.x, which = blockIdx.y, lane = threadIdx.x;
     float s = 0.f;
     for (int b = lane; b < kNormBlocks; b += 64) s += colpart[((size_t)b * 2 + which) * hp + c];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if (lane == 0) { if (which == 0) d_bias[c] = s; else d_weight[c] = s; }
 }
 

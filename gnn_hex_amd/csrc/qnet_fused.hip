@@ -1,5 +1,6 @@
 // C ABI of the fused per-graph path + the exact-fp32 instantiations (kernels: qnet_fused_kernels.h).
 #include "qnet_fused_kernels.h"
+#include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
@@ -42,16 +43,9 @@ struct GradReduceArgs {
     const float* dz; const float* dvr; const float* pooled; const float* z;
     float* d_v0_w; float* d_v0_b; float* d_v1_w; float* d_v1_b;
     int n0, n1, n2, n3, nbx3;
-    // R4 (one block, hexgnn_qnet_backward_flat_td): loss = (sum over the b graphs of loss_part) / b, in td_loss_fwd_kernel's
-    // reduction shape (thread t sums entries t, t + 256, ...; tree over the 256 threads): its bits
+    // R4 (one block, hexgnn_qnet_backward_flat_td): loss = (sum over the b graphs of loss_part) / b, by tree_mean_256
     const float* loss_part; float* loss;
 };
-
-__device__ __forceinline__ float wsum_all(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(GradReduceArgs a) {
     int blk = blockIdx.x;
@@ -61,13 +55,8 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(GradReduceArgs a)
         __shared__ float lred[256];
         float acc = 0.f;
         for (int j = tid; j < a.b; j += 256) acc += a.loss_part[j];
-        lred[tid] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) lred[tid] += lred[tid + o];
-            __syncthreads();
-        }
-        if (tid == 0) a.loss[0] = lred[0] / (float)(a.b > 0 ? a.b : 1);
+        const float mean = tree_mean_256(acc, lred, a.b);
+        if (tid == 0) a.loss[0] = mean;
         return;
     }
     if (blk < a.n0) {                     // ---- R0: slice slabs -> dW_l / dW_r / db of one hidden layer
@@ -107,7 +96,7 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(GradReduceArgs a)
         const int q = c < a.c_in ? c : (c < 2 * a.c_in ? kSmallCin + (c - a.c_in) : 2 * kSmallCin);
         float sum = 0.f;
         for (int g = lane; g < a.b; g += 64) sum += a.first_part[((size_t)g * 17 + q) * hp + o];
-        sum = wsum_all(sum);
+        sum = wave_sum(sum);
         if (lane == 0) {
             if (c < a.c_in) a.dwl0[o * a.c_in + c] = sum;
             else if (c < 2 * a.c_in) a.dwr0[o * a.c_in + (c - a.c_in)] = sum;
@@ -119,11 +108,7 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(GradReduceArgs a)
     if (blk < a.n2) {                     // ---- R2
         const int c = blk * 4 + wave;     // c in [0, H]  (H == bias)
         if (c > H) return;
-        const int src = c < H ? c : hp;
-        float s = 0.f;
-        for (int g = lane; g < a.b; g += 64) s += a.lin_part[(size_t)g * (hp + 1) + src];
-        s = wsum_all(s);
-        if (lane == 0) { if (c < H) a.d_lin_w[c] = s; else a.d_lin_b[0] = s; }
+        lin_part_column_sum(a.b, hp, H, a.lin_part, c, lane, a.d_lin_w, a.d_lin_b);
         return;
     }
     blk -= a.n2;
@@ -148,18 +133,7 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(GradReduceArgs a)
             for (int j = 1; j < 16; ++j) t += red16[j][cl];          // fixed order: deterministic
             a.d_v0_w[(size_t)k * H4 + c] = t;
         }
-        if (bx == 0) {
-            float p = 0.f;
-            if (wave == 0) { for (int g = lane; g < a.b; g += 64) p += a.dz[(size_t)g * H2 + k]; }
-            else if (wave == 1) { for (int g = lane; g < a.b; g += 64) p += a.dvr[g] * a.z[(size_t)g * H2 + k]; }
-            else if (wave == 2 && k == 0) { for (int g = lane; g < a.b; g += 64) p += a.dvr[g]; }
-            p = wsum_all(p);
-            if (lane == 0) {
-                if (wave == 0) a.d_v0_b[k] = p;
-                else if (wave == 1) a.d_v1_w[k] = p;
-                else if (wave == 2 && k == 0) a.d_v1_b[0] = p;
-            }
-        }
+        if (bx == 0) value_small_grads(a.b, H2, k, lane, wave, a.dz, a.dvr, a.z, a.d_v0_b, a.d_v1_w, a.d_v1_b);
     }
 }
 

@@ -1,6 +1,6 @@
 // Several weight sets over one batch in ONE load-balanced forward launch (double-DQN targets: online + target network on the
 // next states): the job-table instantiations of the fused forward (kernel body: qnet_fused_kernels.h), the kernel that builds the
-// job table and packs the sets' weights, the target-formation kernel, and their C ABI.
+// job table and packs the sets' weights, and their C ABI (the targets themselves: hexgnn_dqn_targets, acting.hip).
 #include "qnet_fused_kernels.h"
 #include "hexgnn_pack.h"
 
@@ -87,39 +87,6 @@ __global__ __launch_bounds__(256) void qnet_jobs_pack_kernel(JobsPackArgs a) {
         __syncthreads();
         if (key >= 0) atomicAdd(&start[key], 1);
         __syncthreads();
-    }
-}
-
-// ---- double-DQN targets: one wave per graph (as select_actions_kernel, head.hip) ------------------------------------------------
-//   a2[g] = first node attaining the maximum of q_sel[gptr[g]+2 : gptr[g+1]] (global index; the comparison of select_actions_kernel)
-//   y[g]  = reward[g] + (gamma_n * q_val[a2[g]]) * (done[g] ? 0 : 1): three separately rounded fp32 operations, the torch
-//           expression `r + gamma_n * q_tg[a2] * (~d).float()` bit for bit (an infinite q_val at a done graph gives NaN there too)
-// A graph of two or fewer nodes has no non-terminal node: a2[g] = gptr[g] - 1 (rank -1, what hexgnn_select_actions reports)
-// and q_val's term is taken as zero, y[g] = reward[g] + (gamma_n * 0) * notdone.
-__global__ __launch_bounds__(64) void dqn_targets_kernel(const int* __restrict__ gptr, const float* __restrict__ q_sel,
-                                                       const float* __restrict__ q_val, const float* __restrict__ reward,
-                                                       const unsigned char* __restrict__ done, float gamma_n,
-                                                       float* __restrict__ y, long long* __restrict__ a2) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const int r0 = gptr[g], r1 = gptr[g + 1];
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int i = r0 + 2 + lane; i < r1; i += 64) {
-        const float v = q_sel[i];
-        if (v > best || (v == best && i < arg)) { best = v; arg = i; }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(arg, off);
-        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
-    if (lane == 0) {
-        const bool none = arg == 0x7fffffff;
-        const float qv = none ? 0.f : q_val[arg];
-        const float notdone = done[g] ? 0.f : 1.f;
-        a2[g] = none ? (long long)r0 - 1 : (long long)arg;
-        y[g] = __fadd_rn(reward[g], __fmul_rn(__fmul_rn(gamma_n, qv), notdone));
     }
 }
 
@@ -234,14 +201,6 @@ int hexgnn_qnet_forward_multi(int n, int b, int k, int c_in, int hidden, int tot
         const int rcl = launch_qfwd_jobs(sp.nt, b * k, a, st);
         if (rcl != HEXGNN_OK) return rcl;
     }
-    return check_launch();
-}
-
-int hexgnn_dqn_targets(int b, const int* gptr, const float* q_sel, const float* q_val, const float* reward,
-                       const uint8_t* done, float gamma_n, float* y, int64_t* a2, hexgnn_stream_t stream_) {
-    if (b < 0 || (b > 0 && (!gptr || !q_sel || !q_val || !reward || !done || !y || !a2))) return HEXGNN_EINVAL;
-    if (b == 0) return HEXGNN_OK;
-    dqn_targets_kernel<<<b, 64, 0, (hipStream_t)stream_>>>(gptr, q_sel, q_val, reward, done, gamma_n, y, (long long*)a2);
     return check_launch();
 }
 

@@ -18,6 +18,8 @@
 #include <utility>
 #include "hexgnn_internal.h"
 #include "hexgnn_memops.h"
+#include "hexgnn_reduce.h"
+#include "td_loss.h"
 
 namespace hexgnn {
 
@@ -127,11 +129,6 @@ __device__ __forceinline__ float oct_sum(float v) {
     v += dpp(v, std::integral_constant<int, 0xB1>{});
     v += dpp(v, std::integral_constant<int, 0x4E>{});
     v += dpp(v, std::integral_constant<int, 0x141>{});    // row_half_mirror: lane i <-> 7 - i within each 8
-    return v;
-}
-__device__ __forceinline__ float wsum64(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
 
@@ -956,7 +953,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(std::conditional_t<JOBS, 
     if (QMODE == 2) return;
     {   // sum of 2tanh(adv) over the graph: lanes g==0 of valid rows; fixed-shape tree
         float v = (g == 0 && rvalid) ? tadv : 0.f;
-        v = wsum64(v);
+        v = wave_sum(v);
         if (lane == 0) s_red[wave] = v;
     }
     // value-MLP weights -> registers now (the loads fly during pooling): thread (k = tid / 8, part = tid % 8) takes hidden
@@ -1030,7 +1027,7 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(std::conditional_t<JOBS, 
     __syncthreads();
     if (wave == 0) {
         float p = lane < H2 ? v1w_l * s_z[lane] : 0.f;
-        p = wsum64(p);
+        p = wave_sum(p);
         if (lane == 0) {
             const float v = p + v1b_0;
             if constexpr (!JOBS) a.vraw[gi] = v;
@@ -1047,15 +1044,15 @@ __global__ __launch_bounds__(512) void qnet_fwd_kernel(std::conditional_t<JOBS, 
     const float qv = (QMODE == 0 ? V : 0.f) + tadv - mean_adv;
     if (g == 0 && rvalid) QSEL(q)[grow] = qv;
     if (td_on) {
-        // loss = mean_g w_g l(Q[sel_g] - target_g): the same per-entry expressions as td_loss_fused_kernel (head.hip), so dq
-        // and td have its bits; the mean over the graphs is summed from td_loss_part by the backward's reduce launch
+        // loss = mean_g w_g l(Q[sel_g] - target_g) with td_loss.h's per-entry expressions; the mean over the graphs is summed
+        // from td_loss_part by the backward's reduce launch
         if (g == 0 && rvalid) {
             float d = 0.f;
             if ((long long)grow == td_s) {
-                const float e = qv - td_t, ae = fabsf(e);
+                const float e = qv - td_t;
                 a.td_out[gi] = e;
-                a.td_loss_part[gi] = td_wg * (a.td_loss_fn == 0 ? e * e : (ae <= 1.f ? 0.5f * e * e : ae - 0.5f));
-                const float dl = a.td_loss_fn == 0 ? 2.f * e : fminf(fmaxf(e, -1.f), 1.f);
+                a.td_loss_part[gi] = td_wg * td_term(e, a.td_loss_fn);
+                const float dl = td_dterm(e, a.td_loss_fn);
                 d = (1.f / (float)a.b) * td_wg * dl;
             }
             a.td_dq[grow] = d;
@@ -1174,7 +1171,7 @@ __global__ __launch_bounds__(512) void qnet_bwd_kernel(QBwdArgs a) {
     float mean_dq = 0.f;
     const float inv_cnt = 1.f / (float)max(cnt, 1);
     if (a.mode != 2) {
-        float ps = wsum64(dq_t);
+        float ps = wave_sum(dq_t);
         if (lane == 0) s_red[wave] = ps;
         if (tid < H) {
             s_ax[tid] = ax_t >= 0 ? ax_t - r0 : -1;

@@ -4,6 +4,7 @@
 #include "sage_common.h"
 #include "sage_internal.h"
 #include "sage_dw_kernel.h"
+#include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
@@ -306,8 +307,7 @@ __global__ __launch_bounds__(64) void sage_first_dw_reduce_kernel(
     const int q = c < c_in ? c : (c < 2 * c_in ? kSmallCin + (c - c_in) : 16);
     float sum = 0.f;
     for (int s = lane; s < S; s += 64) sum += part[((size_t)s * hp + o) * 17 + q];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+    sum = wave_sum(sum);
     if (lane == 0) {
         if (c < c_in) dwl[o * c_in + c] = sum;
         else if (c < 2 * c_in) dwr[o * c_in + (c - c_in)] = sum;

@@ -10,6 +10,7 @@
 // points (sage.hip / head.hip dispatch here when hidden > 128).  Not covered at these widths: the fused per-graph kernels, the
 // norms, the two_headed tail and the HexAra pieces (their entry points refuse loudly).
 #include "hexgnn_internal.h"
+#include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
@@ -595,19 +596,6 @@ int wide_stack_backward(int n, int c_in, int hidden, int L, const int* rowptr_t,
 
 // ---- head tail (advantage linear, [sum|max|min|mean] pooling, value MLP, dueling combine), one workgroup per graph -----------
 // Same modes, saved layout (HeadSaved) and tie rules as head_fwd_kernel / head_bwd_kernel; generic in the width.
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ float bsum256(float v, float* s4) {
-    v = wsum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s4[0] + s4[1] + s4[2] + s4[3];
-}
-
 __global__ __launch_bounds__(256) void wide_head_fwd_kernel(
     int H, int hp, int mode, const int* __restrict__ gptr, const float* __restrict__ h, const float* __restrict__ lin_w,
     const float* __restrict__ lin_b, const float* __restrict__ v0_w, const float* __restrict__ v0_b,
@@ -628,7 +616,7 @@ __global__ __launch_bounds__(256) void wide_head_fwd_kernel(
     for (int row = r0 + wave; row < r1; row += 4) {           // one wave per row
         float a = 0.f;
         for (int c = lane; c < H; c += 64) a += h[(size_t)row * hp + c] * s_w[c];
-        a = wsum(a);
+        a = wave_sum(a);
         if (lane == 0) {
             a += lb;
             adv_raw[row] = a;
@@ -639,7 +627,7 @@ __global__ __launch_bounds__(256) void wide_head_fwd_kernel(
         }
     }
     if (mode == 2 || mode == 4) return;
-    const float adv_total = bsum256(tsum, s_red);
+    const float adv_total = block_sum_256(tsum, s_red);
     for (int c = tid; c < H; c += 256) {                      // pooling: a thread per column, rows in ascending order
         float sum = 0.f, mx = -INFINITY, mn = INFINITY;
         int ax = -1, an = -1;
@@ -661,7 +649,7 @@ __global__ __launch_bounds__(256) void wide_head_fwd_kernel(
     for (int k = wave; k < H2; k += 4) {                      // value MLP: one wave per hidden unit
         float p = 0.f;
         for (int c = lane; c < H4; c += 64) p += v0_w[(size_t)k * H4 + c] * s_pool[c];
-        p = wsum(p);
+        p = wave_sum(p);
         if (lane == 0) {
             const float zz = fmaxf(p + v0_b[k], 0.f);
             s_z[k] = zz;
@@ -671,7 +659,7 @@ __global__ __launch_bounds__(256) void wide_head_fwd_kernel(
     __syncthreads();
     float p = 0.f;
     for (int k = tid; k < H2; k += 256) p += v1_w[k] * s_z[k];
-    const float v = bsum256(p, s_red) + v1_b[0];
+    const float v = block_sum_256(p, s_red) + v1_b[0];
     if (tid == 0) vraw[g] = v;
     const float V = mode == 3 ? v : tanhf(v);
     if ((mode == 1 || mode == 3) && tid == 0) out_v[g] = V;
@@ -701,7 +689,7 @@ __global__ __launch_bounds__(256) void wide_head_bwd_kernel(
     if (has_value) {
         float ps = 0.f;
         for (int row = r0 + tid; row < r1; row += 256) ps += dq[row];
-        const float sdq = bsum256(ps, s_red);
+        const float sdq = block_sum_256(ps, s_red);
         mean_dq = raw ? 0.f : sdq * inv_cnt;
         for (int c = tid; c < H; c += 256) { s_ax[c] = amax[(size_t)g * H + c]; s_an[c] = amin[(size_t)g * H + c]; }
         const float dV = mode == 0 ? sdq : d_out_v[g];

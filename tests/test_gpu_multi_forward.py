@@ -209,6 +209,56 @@ def test_target_kernel_propagates_nan_like_torch():
     assert torch.equal(y.view(torch.int32)[[0, 2]], want.view(torch.int32)[[0, 2]])
 
 
+def _tie_cases():
+    """Q arrays over graphs of 3, 70, 2 and 140 nodes with exact ties for the maximum among the candidates (rows 2.. of a graph;
+    candidate c sits on lane c % 64 of pass c // 64 of the one wave that scans the graph).  The two terminal rows hold a larger
+    value still: they must never win."""
+    ptr = [0, 3, 73, 75, 215]
+    cases = {}
+
+    def make(name, ties70, ties140, base=None):
+        q = torch.linspace(-1.0, -0.5, ptr[-1]) if base is None else base.clone()
+        for g in range(4):
+            q[ptr[g]:ptr[g] + 2] = 9.0
+        for r0, ties in ((ptr[1], ties70), (ptr[3], ties140)):
+            for c in ties:
+                q[r0 + 2 + c] = 1.0
+        cases[name] = q
+
+    make("lanes i, i+1", [20, 21], [100, 101])
+    make("same lane, a later pass", [2, 66], [7, 71, 135])
+    make("the two halves of the wave", [40, 5], [64 + 33, 64 + 2])
+    make("a later pass on a lower lane", [67, 10], [130, 9, 70])
+    make("every candidate tied", range(68), range(138))
+    gen = torch.Generator().manual_seed(9)
+    make("few distinct values", [], [], base=torch.randint(0, 3, (ptr[-1],), generator=gen).float())
+    return ptr, cases
+
+
+def test_one_argmax_rule_for_acting_and_targets():
+    """ops.greedy_nodes (hexgnn_select_actions) and the a2 of hexgnn_dqn_targets against torch.argmax over each graph's candidates --
+    the first maximum -- and against each other; a two-node graph has no candidate: rank -1, i.e. ptr[g] - 1, from both."""
+    from gnn_hex_amd import _lib, ops
+    ptr_l, cases = _tie_cases()
+    ptr = torch.tensor(ptr_l, dtype=torch.int32, device="cuda")
+    b = len(ptr_l) - 1
+    r = torch.zeros(b, device="cuda")
+    d = torch.zeros(b, dtype=torch.uint8, device="cuda")
+    for name, q_cpu in cases.items():
+        want = [ptr_l[g] + 2 + int(torch.argmax(q_cpu[ptr_l[g] + 2:ptr_l[g + 1]])) if ptr_l[g + 1] - ptr_l[g] > 2 else ptr_l[g] - 1
+                for g in range(b)]
+        q = q_cpu.cuda()
+        y = torch.empty(b, device="cuda")
+        a2 = torch.empty(b, dtype=torch.int64, device="cuda")
+        _lib.check(_lib.lib().hexgnn_dqn_targets(b, ptr.data_ptr(), q.data_ptr(), q.data_ptr(), r.data_ptr(), d.data_ptr(),
+                                                 GAMMA_N, y.data_ptr(), a2.data_ptr(), ops._stream()))
+        greedy = ops.greedy_nodes(q, ptr)
+        assert greedy.tolist() == want, name
+        assert a2.tolist() == want, name
+        assert torch.equal(greedy, a2), name
+        assert want[2] == ptr_l[2] - 1
+
+
 def _targets_plain(online, target, dev, r, d):
     from gnn_hex_amd import ops
     q_on, q_tg = _plain([online, target], dev)

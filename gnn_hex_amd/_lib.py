@@ -100,6 +100,8 @@ _SIGS = {
                                           vp, vp, sz, vp, ci, ci, ci, vp, vp, vp]),
     "hexgnn_qnet_backward_flat_td_live": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp,
                                                vp, vp, vp, sz, vp, ci, ci, ci, vp, vp, vp, vp]),
+    "hexgnn_qnet_step_td": (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                 vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
     "hexgnn_qnet_jobs_bytes": (sz, [ci, ci]),
     "hexgnn_qnet_multi_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
     "hexgnn_qnet_forward_jobs": (ci, [ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),

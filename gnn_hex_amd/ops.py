@@ -908,6 +908,17 @@ def set_fused(enabled: bool) -> None:
     _FUSED_ENABLED = bool(enabled)
 
 
+_ONE_LAUNCH_STEP = True
+
+
+def set_one_launch_step(enabled: bool) -> None:
+    """``td_step``'s fused form as ONE launch for the forward, the TD loss and the backward's data chain
+    (``hexgnn_qnet_step_td``: a workgroup runs its graph's backward chain right behind its forward) instead of two.  Same
+    bits; taken in exact fp32 without ``defer_lower``, a grad-stage hook or ``x._hex_live_rows`` (tests and A/B switch it)."""
+    global _ONE_LAUNCH_STEP
+    _ONE_LAUNCH_STEP = bool(enabled)
+
+
 _GRAD_STAGE_HOOK = None
 
 
@@ -1054,7 +1065,7 @@ class _QNetCall:
     ``nonleaf``: a parameter of the call is computed per forward (no staging, see qnet_backward); ``live``: td_step() over
     capacity-sized buffers -- the 1-element int32 device tensor that holds the live row count (``x._hex_live_rows``)."""
     __slots__ = ("cache", "gs", "gptr", "dims", "x", "bufs", "math", "sink", "gp", "done", "layered", "td", "pending", "versions",
-                 "assign", "nonleaf", "live")
+                 "assign", "nonleaf", "live", "step_ws")
 
 
 def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
@@ -1117,7 +1128,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
               gptr.data_ptr(), gs.status.data_ptr())
     t = cache.tail
     stream = _stream()
-    td = live = None
+    td = live = step_ws = None
     if layered:
         fn, name, tbl = _stack_entry(L, gs, True)
         _lib.check(fn(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr, wpack, base, saved,
@@ -1133,13 +1144,24 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
             # one buffer: dq [n] | td [b] | loss terms [b] | loss [1]
             tb = torch.empty(n + 2 * b + 1, dtype=torch.float32, device=dev)
             tp = tb.data_ptr()
-            _lib.check(L.hexgnn_qnet_forward_td(
-                n, b, c_in, hidden, tot, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
-                t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, _MATH, q.data_ptr(), gp[6],
-                sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
-                tp + 4 * (n + b), stream), "hexgnn_qnet_forward_td")
-            td = (tb, n, b)
             live = getattr(_TD_STEP, "live", None)
+            if _ONE_LAUNCH_STEP and _MATH == 0 and live is None and getattr(_TD_STEP, "whole", False):
+                # the backward's data chain in the same launch: its workspace exists from here on (qnet_backward runs the rest)
+                # (and the gradient of the body's output, which the model's activations hook receives in qnet_backward)
+                step_ws = (torch.empty(bwd_bytes, dtype=torch.uint8, device=dev),
+                           torch.empty((n, hp), dtype=torch.float32, device=dev))
+                _lib.check(L.hexgnn_qnet_step_td(
+                    n, b, c_in, hidden, tot, body_layers, gp[5], gp[0], gp[1], gp[2], gp[3], gp[4], x.data_ptr(), x_stride,
+                    wl, bl, wr, t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, q.data_ptr(), gp[6],
+                    sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
+                    tp + 4 * (n + b), step_ws[1].data_ptr(), step_ws[0].data_ptr(), bwd_bytes, stream), "hexgnn_qnet_step_td")
+            else:
+                _lib.check(L.hexgnn_qnet_forward_td(
+                    n, b, c_in, hidden, tot, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
+                    t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, _MATH, q.data_ptr(), gp[6],
+                    sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
+                    tp + 4 * (n + b), stream), "hexgnn_qnet_forward_td")
+            td = (tb, n, b)
         else:
             _lib.check(L.hexgnn_qnet_forward(
                 n, b, c_in, hidden, tot, mode, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
@@ -1151,7 +1173,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
     call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, bwd_bytes)
     call.bufs, call.math, call.gp = buf, 0 if layered else _MATH, gp
     call.sink, call.done, call.layered, call.td, call.pending = None, False, layered, td, None
-    call.assign, call.nonleaf, call.live = assign, False, live
+    call.assign, call.nonleaf, call.live, call.step_ws = assign, False, live, step_ws
     # the backward reads the head tail's weights LIVE (the SAGE layers' from the pack made by this forward): an in-place update
     # between the two would mix old and new weights without autograd's saved-tensor version check to notice it
     call.versions = tuple(p._version for p in cache.params[-6:]) if need_bwd else None
@@ -1251,8 +1273,18 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
             *tbl, stream), name)
     else:
         ws_bytes = bwd_bytes
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if call.sink is not None else None
+        td = call.td
+        # hexgnn_qnet_step_td ran the data chain with the forward: the remaining stages work on its workspace
+        chained = call.step_ws is not None and td is not None and dq.data_ptr() == td[0].data_ptr() \
+            and not defer_lower and _GRAD_STAGE_HOOK is None
+        if chained:
+            ws, d_emb = call.step_ws
+            call.step_ws = True          # (the chain's results are taken; tests look at this)
+            if call.sink is None:
+                d_emb = None
+        else:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if call.sink is not None else None
         common = (n, b, c_in, hidden, tot, body_layers, mode, call.math, gp[5], gp[2], gp[3], gp[4], call.x.data_ptr(),
                   x_stride, base, base + a_bytes + w_bytes, base + a_bytes, t[0], t[2], t[4], dq.data_ptr(),
                   d_v.data_ptr() if d_v is not None else None, d_emb.data_ptr() if d_emb is not None else None,
@@ -1260,7 +1292,6 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
         hook = _GRAD_STAGE_HOOK
         split = tot >= 3 and mode != 2 and not call.nonleaf and (defer_lower or hook is not None)
         mid = 1 + tot // 2 if split else 1
-        td = call.td
         if td is not None and dq.data_ptr() == td[0].data_ptr():
             # td_step(): d loss / d Q came from the forward launch; the reduce launch also writes the loss (mean of the graphs' terms)
             tb, tn, tbb = td
@@ -1271,8 +1302,8 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
                 _lib.check(L.hexgnn_qnet_backward_flat_td_live(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
                                                                live.data_ptr(), _stream()), "hexgnn_qnet_backward_flat_td_live")
             else:
-                _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
-                                                          _stream()), "hexgnn_qnet_backward_flat_td")
+                _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 6 if chained else 7, mid, tot, tp + 4 * (tn + tbb),
+                                                          tp + 4 * (tn + 2 * tbb), _stream()), "hexgnn_qnet_backward_flat_td")
         else:
             _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, mid, tot, _stream()), "hexgnn_qnet_backward_flat")
         if split and defer_lower:
@@ -1504,7 +1535,8 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
     When the update selects ONE node per graph, ``sel[g]`` a node of graph g (the action of the sampled transition: what the
     RainbowDQN step gathers, README.md:5,7) and the batch runs on the fused per-graph kernels, the loss is graph-local and the
     forward kernel forms it in its tail: no launch between the network's forward and backward, ``loss`` is written by the
-    backward's reduce launch (``hexgnn_qnet_forward_td`` / ``hexgnn_qnet_backward_flat_td``).  A ``sel[g]`` outside graph g
+    backward's reduce launch (``hexgnn_qnet_forward_td`` / ``hexgnn_qnet_backward_flat_td``; in exact fp32 the forward and the
+    backward's data chain are one launch, ``hexgnn_qnet_step_td``, see ``set_one_launch_step``).  A ``sel[g]`` outside graph g
     makes ``loss`` / ``td[g]`` NaN and raises at the next ``GraphStructure.check()`` (status 16).  Anything else (several
     selections per graph, graphs above 128 nodes, frozen parameters, ``--noisy_dqn``) runs the three calls.
 
@@ -1529,11 +1561,13 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
     lfn = {"mse": 0, "huber": 1}[loss_fn]
     _TD_STEP.args = (sel, target, weights, lfn)
     _TD_STEP.live = live
+    _TD_STEP.whole = not defer_lower and _GRAD_STAGE_HOOK is None      # (the one-launch form: set_one_launch_step)
     try:
         q = model(x, edge_index, graph_indices, ptr)
     finally:
         _TD_STEP.args = None
         _TD_STEP.live = None
+        _TD_STEP.whole = False
     q = q.__dict__.get("_hex_plain", q)      # (td_step hands back the ordinary tensor, not the QValues wrapper)
     call = getattr(q, "_hex_call", None)
     td = call.td if call is not None else None

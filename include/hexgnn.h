@@ -497,6 +497,22 @@ int hexgnn_qnet_backward_flat_td_live(int n, int b, int c_in, int hidden, int to
                                       const float* loss_part /*[b]*/, float* loss /*[1]*/, const int* n_live /* device */,
                                       hexgnn_stream_t stream);
 
+/* The TD step's forward, loss and backward data chain in ONE launch (entry point added to ABI 6, nothing existing changes): what
+ * hexgnn_qnet_forward_td followed by the HEXGNN_QBWD_DATA stage of hexgnn_qnet_backward_flat_td does (math 0, mode 0), same
+ * arguments, same bits in every output and in everything the later stages read from saved / workspace.  One workgroup per graph
+ * runs the forward, the TD tail and then the backward chain of ITS graph; no workgroup waits for another.  The caller then runs
+ * hexgnn_qnet_backward_flat_td with stages = HEXGNN_QBWD_SMALL | HEXGNN_QBWD_HIDDEN on the same workspace.  Status bits as in
+ * the two launches (2: a graph above 128 rows, 16: a selection outside its graph).  n > 0 and b > 0.  While a profile class is
+ * enabled (hexgnn_profile_enable) the two kernels are launched one after the other, so that per-kernel times keep their meaning. */
+int hexgnn_qnet_step_td(int n, int b, int c_in, int hidden, int total_layers, int body_layers, const int* gptr,
+                        const int* rowptr, const int* col, const int* rowptr_t, const int* col_t, const float* invdeg,
+                        const float* x, int x_stride, const float* const* wl, const float* const* bl, const float* const* wr,
+                        const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b, const float* v1_w,
+                        const float* v1_b, void* wpack, float* acts, void* saved, float* q, int* status,
+                        const int64_t* sel /*[b]*/, const float* target /*[b]*/, const float* weights /*[b] or NULL*/, int loss_fn,
+                        float* dq /*[n]*/, float* td /*[b]*/, float* loss_part /*[b]*/, float* d_embeds /* or NULL */,
+                        void* workspace, size_t workspace_bytes, hexgnn_stream_t stream);
+
 /* ---- double-DQN targets: several weight sets over ONE batch in one load-balanced forward launch.  Entry points added to
  *      ABI 6 (nothing existing changes).  The RainbowDQN update (README.md:5,7: the double-DQN step) runs the
  *      online and the target network on the same next states, takes the per-graph argmax of the online Q over the non-terminal

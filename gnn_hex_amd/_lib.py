@@ -79,6 +79,7 @@ _SIGS = {
     "hexgnn_policy_log_softmax_forward": (ci, [ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     "hexgnn_policy_log_softmax_backward": (ci, [ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]),
     "hexgnn_qnet_supported": (ci, [ci, ci, ci]),
+    "hexgnn_qnet_csr_capacity": (ci, [ci]),
     "hexgnn_qnet_saved_bytes": (sz, [ci, ci, ci, ci, ci]),
     "hexgnn_qnet_forward": (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                  vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),

@@ -238,6 +238,13 @@ int hexgnn_qnet_supported(int c_in, int hidden, int max_nodes_per_graph) {
            max_nodes_per_graph <= kRows;
 }
 
+int hexgnn_qnet_csr_capacity(int hidden) {
+    const int hp = padded_width(hidden);
+    if (hp <= 0 || hp > 112 || hidden < 2) return HEXGNN_EUNSUPPORTED;
+    HEXGNN_NT_SWITCH7(hp / 16, return QLds<NT_>::col_cap);
+    return HEXGNN_EUNSUPPORTED;
+}
+
 size_t hexgnn_qnet_saved_bytes(int n, int b, int c_in, int hidden, int total_layers) {
     QPlan q;
     if (n < 0 || b < 0 || make_qplan(n, b, c_in, hidden, total_layers, &q) != HEXGNN_OK) return 0;

@@ -376,6 +376,11 @@ int hexgnn_sage_norm_stack_backward(int n, int c_in, int hidden, int num_layers,
  *                ~3*2^-22 of max|w| max|x|; same parity bar as math 0, see tests/test_gpu_model.py).  The backward
  *                call must use the math of its forward. ---- */
 int hexgnn_qnet_supported(int c_in, int hidden, int max_nodes_per_graph);
+/* Edges of ONE graph that the fused kernels keep in LDS at this width (host arithmetic; query added to ABI 6, nothing existing
+ * changes): a graph with more edges runs the same kernels with its neighbour ids read from the global CSR instead (same
+ * results, slower; a Hex board never comes near it).  8192 up to hidden 96, 2848 at 97..112; HEXGNN_EUNSUPPORTED for a width
+ * hexgnn_qnet_supported() refuses (hidden < 2 or > 112). */
+int hexgnn_qnet_csr_capacity(int hidden);
 size_t hexgnn_qnet_saved_bytes(int n, int b, int c_in, int hidden, int total_layers);
 int hexgnn_qnet_forward(int n, int b, int c_in, int hidden, int total_layers, int mode, const int* gptr,
                         const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,

@@ -747,3 +747,139 @@ def norm_model_margin(ref64, maker, run):
             h.remove()
     assert len(pre) >= len(mods) - 1              # advantages_only runs no value MLP
     return relu_margin_of(pre), out
+
+
+# ---- every tile count, kernel form and CSR home of the fused per-graph kernels (tests/test_gpu_fused_instantiations.py) ---------
+
+def csr_capacity(hidden):
+    """Edges of one graph the fused kernels keep in LDS at this width (hexgnn_qnet_csr_capacity)."""
+    from gnn_hex_amd import _lib
+    cap = _lib.lib().hexgnn_qnet_csr_capacity(int(hidden))
+    assert cap > 0, (hidden, cap)
+    return cap
+
+
+def model_relu_margin(ref64, maker, run):
+    """min |ReLU input| / rms over the SAGE layers of the body and of the playing head and the value MLP's first layer of an
+    oracle model without norms, during run()."""
+    store, hooks = {}, []
+    head = ref64.maker_head if maker else ref64.breaker_head
+    for conv in list(ref64.gnn.convs) + list(head.gnn.convs):
+        hooks.append(conv.register_forward_hook(lambda mod, inp, out: store.__setitem__(id(mod), out.detach())))
+    hooks.append(head.value_head.layers[0].register_forward_hook(lambda mod, inp, out: store.__setitem__("value", out.detach())))
+    try:
+        with torch.no_grad():
+            run()
+    finally:
+        for h in hooks:
+            h.remove()
+    return min((t.abs().min() / t.pow(2).mean().sqrt()).item() for t in store.values())
+
+
+def truncated_graphs(make, rows, edge_counts, seed, p_edge):
+    """One batch of len(edge_counts) graphs of ``rows`` nodes each: graph g is ``make([rows], seed + g, p_edge=p_edge)`` (an
+    edge list in random order) cut to exactly edge_counts[g] edges."""
+    xs, eis, bv, ptr = [], [], [], [0]
+    for g, k in enumerate(edge_counts):
+        x, ei, _, _ = make([rows], seed=seed + g, p_edge=p_edge)
+        assert ei.shape[1] >= k, "graph %d: %d edges, %d wanted" % (g, ei.shape[1], k)
+        xs.append(x)
+        eis.append(ei[:, :k] + ptr[-1])
+        bv.append(torch.full((rows,), g, dtype=torch.long))
+        ptr.append(ptr[-1] + rows)
+    return torch.cat(xs), torch.cat(eis, 1), torch.cat(bv), torch.tensor(ptr, dtype=torch.long)
+
+
+def graph_edge_counts(ei, ptr):
+    """Edges per graph, by the graph of the edge's target row."""
+    return torch.bincount(torch.bucketize(ei[1], ptr[1:], right=True), minlength=ptr.numel() - 1).tolist()
+
+
+def spread_selection(ptr, seed=1):
+    """(sel, tgt, w): ``one_row_per_graph``, every second graph's selection (graphs 0, 2, ..) moved to its LAST row, and weights
+    ~ U(0.5, 1.5)."""
+    sel, tgt = one_row_per_graph(ptr, seed)
+    sel = sel.clone()
+    sel[0::2] = ptr[1:][0::2] - 1
+    gen = torch.Generator().manual_seed(seed + 1000)
+    return sel, tgt, torch.rand(sel.numel(), generator=gen) + 0.5
+
+
+class TdCases:
+    """The TD step of ``modern_two_headed`` (``body`` + ``head`` layers, sharpened) on named batches: per (batch, hidden) the
+    float64 and fp32 oracle results of loss = mean(w (Q[sel] - tgt)^2) at the first weight seed below SEEDS at which the float64
+    oracle has no ReLU input within MARGIN of zero (relative to its tensor's rms), a Q spread >= 0.5 and |g|max >= 1e-2 in every
+    gradient tensor -- once per session, from the oracle alone.  ``recorded`` {(batch key, hidden): seed} holds what that search
+    found before (a float64 pass over these batches takes seconds, a search up to a minute): the conditions are evaluated at the
+    recorded seed as at any other, and the search runs where there is none or where it no longer meets them."""
+
+    def __init__(self, body, head, batches, recorded=None):
+        self.body, self.head, self.batches = body, head, batches       # batches(name, hidden) -> (builder, key)
+        self.recorded = dict(recorded or {})
+        self._batches, self._oracles = {}, {}
+
+    def args(self, hidden):
+        return model_args(self.body, hidden, self.head)
+
+    def ref(self, hidden, seed):
+        from oracle.model_ref import get_pre_defined_ref
+        torch.manual_seed(seed)
+        return sharpen_(get_pre_defined_ref("modern_two_headed", self.args(hidden)))
+
+    def hip(self, ref, hidden):
+        from gnn_hex_amd.models import get_pre_defined
+        hip = get_pre_defined("modern_two_headed", self.args(hidden))
+        res = hip.load_state_dict(ref.state_dict())
+        assert not res.missing_keys and not res.unexpected_keys
+        return hip.cuda()
+
+    def batch(self, name, hidden):
+        b, key = self.batches(name, hidden)
+        if key not in self._batches:
+            x, ei, bv, ptr = b()
+            self._batches[key] = (x, ei, bv, ptr) + spread_selection(ptr)
+        return key, self._batches[key]
+
+    @staticmethod
+    def ref_run(model, x, ei, bv, ptr, sel, tgt, w):
+        model.zero_grad(set_to_none=True)
+        q = model(x, ei, bv, ptr)
+        d = q[sel] - tgt
+        loss = (w * d * d).mean()
+        loss.backward()
+        return dict(loss=loss.detach(), td=d.detach(), q=q.detach(),
+                    grads=[None if p.grad is None else p.grad.detach().clone() for p in model.parameters()])
+
+    def conditions(self, ref64, inputs, search=False):
+        x, ei, bv, ptr, sel, tgt, w = inputs
+        x64 = x.double()
+        margin = model_relu_margin(ref64, bool(x[0, 2] == 1), lambda: ref64(x64, ei, bv, ptr))
+        if search and margin < MARGIN:
+            return False, "", None
+        r64 = self.ref_run(ref64, x64, ei, bv, ptr, sel, tgt.double(), w.double())
+        spread = (r64["q"].max() - r64["q"].min()).item()
+        gmax = min(g.abs().max().item() for g in r64["grads"] if g is not None)
+        ok = margin >= MARGIN and spread >= 0.5 and gmax >= 1e-2
+        return ok, "Q spread %.3g (>= 0.5), smallest |g|max %.3g (>= 1e-2), smallest |ReLU input| / rms %.3g (>= 2^-16)" \
+            % (spread, gmax, margin), r64
+
+    def oracle(self, name, hidden):
+        import copy
+        key, inputs = self.batch(name, hidden)
+        if (key, hidden) not in self._oracles:
+            known = self.recorded.get((key, hidden))
+            for seed in ([] if known is None else [known]) + list(range(SEEDS)):
+                ref = self.ref(hidden, seed)
+                ok, text, r64 = self.conditions(copy.deepcopy(ref).double(), inputs, search=True)
+                if ok:
+                    break
+            else:
+                raise AssertionError("%s hidden %d: no weight seed below %d meets the oracle conditions" % (key, hidden, SEEDS))
+            x, ei, bv, ptr, sel, tgt, w = inputs
+            print("oracle %s hidden %d: %d rows, weight seed %d; %s" % (key, hidden, x.shape[0], seed, text))
+            self._oracles[(key, hidden)] = dict(ref=ref, seed=seed, ok=ok, text=text, r64=r64, inputs=inputs,
+                                               r32=self.ref_run(ref, x, ei, bv, ptr, sel, tgt, w),
+                                               names=[k for k, _ in ref.named_parameters()])
+        o = self._oracles[(key, hidden)]
+        assert o["ok"], "%s hidden %d: %s" % (key, hidden, o["text"])
+        return o

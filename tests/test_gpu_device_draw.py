@@ -24,6 +24,7 @@ import pytest
 import torch
 
 from helpers import MARGIN, PoisonedTorch, batch_tensors, check_grads, dw_plan, model_args, sel_and_targets, sharpen_
+from helpers import model_relu_margin as _relu_margin      # (min |ReLU input| / rms over the SAGE layers and the value MLP)
 
 pytestmark = pytest.mark.gpu
 
@@ -219,21 +220,6 @@ CASES = ("one-slice-plan", "below-256", "below-32-per-slice", "multiple", "multi
 
 def _args(hidden):
     return model_args(LAYERS, hidden, HEAD)
-
-
-def _relu_margin(ref64, maker, run):
-    store, hooks = {}, []
-    head = ref64.maker_head if maker else ref64.breaker_head
-    for conv in list(ref64.gnn.convs) + list(head.gnn.convs):
-        hooks.append(conv.register_forward_hook(lambda mod, inp, out: store.__setitem__(id(mod), out.detach())))
-    hooks.append(head.value_head.layers[0].register_forward_hook(lambda mod, inp, out: store.__setitem__("value", out.detach())))
-    try:
-        with torch.no_grad():
-            run()
-    finally:
-        for h in hooks:
-            h.remove()
-    return min((t.abs().min() / t.pow(2).mean().sqrt()).item() for t in store.values())
 
 
 def _ref_model(hidden, maker):

@@ -411,7 +411,9 @@ def test_graph_size_boundary_128_129():
 
 
 def test_dense_graph_exceeds_lds_csr_capacity():
-    """A graph whose edge list does not fit the LDS CSR cache (u8 columns, ~3.8 KB at hidden 110) walks the global CSR."""
+    """A graph whose edge list does not fit the LDS CSR cache (u8 columns; 2848 edges at hidden 110, hexgnn_qnet_csr_capacity)
+    walks the global CSR: about 5 900 edges per graph here.  At a width of 96 or less the cache takes 8192 edges and these graphs
+    would stay in LDS; tests/test_gpu_fused_instantiations.py has graphs beyond that for every tile count."""
     hip, ref = make_pair(3, 110, seed=23)
     from gnn_hex_amd import ops
     x, ei, batch, ptr = _random_batch([100, 100], seed=7, directed=True, p_edge=0.6)

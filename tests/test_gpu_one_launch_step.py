@@ -103,8 +103,11 @@ def test_one_launch_has_the_bits_of_two(hidden, body, head):
 
 @pytest.mark.parametrize("hidden", [35, 110])
 def test_dense_graphs_walk_the_global_csr(hidden):
-    """The suite's degree-60 stress graphs (tests/test_gpu_model.py): rows above 16 neighbours, and an edge list beyond the LDS
-    arrays, so that both bodies take their global-CSR fallback; directed edges make the transposed CSR differ from the forward's."""
+    """The suite's degree-60 stress graphs (tests/test_gpu_model.py): rows above 16 neighbours and about 5 900 edges per graph;
+    directed edges make the transposed CSR differ from the forward's.  Only the 110-wide half walks the global CSR (2848 edges fit
+    the LDS arrays at NT = 7); at hidden 35 the arrays take 8192 edges (hexgnn_qnet_csr_capacity) and these graphs stay in LDS -- there
+    the case is the long-row gather of the LDS path.  The global-CSR fallback at every tile count:
+    tests/test_gpu_fused_instantiations.py."""
     from test_gpu_model import _random_batch
     hip, _ = _pair(3, 2, hidden, seed=23)
     x, ei, bv, ptr = _random_batch([100, 100], seed=7, directed=True, p_edge=0.6)

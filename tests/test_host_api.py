@@ -439,3 +439,24 @@ def test_raw_feature_count_bounds_are_refused_on_the_host():
                                      None, None, None, p, None, p, 0, -1, 0, None, None, p, None)
     assert forward(3, 2) == -1 and forward(8, 7) == -1 and forward(1, 0) == -1        # HEXGNN_EINVAL
     assert forward(9, 9) == -2 and forward(0, 3) == -2                                 # HEXGNN_EUNSUPPORTED comes first
+
+
+def test_csr_capacity_query():
+    """hexgnn_qnet_csr_capacity: the edges of one graph the fused kernels keep in LDS, per width (QLds<NT>::col_cap).  At least
+    1024 for every width hexgnn_qnet_supported takes, the same for every width of one tile count, non-increasing in the tile
+    count; refused (HEXGNN_EUNSUPPORTED) exactly where hexgnn_qnet_supported refuses the width.  Host arithmetic only."""
+    from gnn_hex_amd import _lib
+    L = _lib.lib()
+    caps = {}
+    for hidden in range(-1, 131):
+        cap = L.hexgnn_qnet_csr_capacity(hidden)
+        if L.hexgnn_qnet_supported(1 if hidden != 1 else 2, hidden, 128):
+            assert cap >= 1024, (hidden, cap)
+            caps.setdefault((hidden + 15) // 16, set()).add(cap)
+        else:
+            assert cap == -2, (hidden, cap)
+    assert sorted(caps) == [1, 2, 3, 4, 5, 6, 7] and all(len(v) == 1 for v in caps.values())
+    by_nt = [caps[nt].pop() for nt in range(1, 8)]
+    assert all(a >= b for a, b in zip(by_nt, by_nt[1:])), by_nt
+    assert by_nt[0] == 8192 and by_nt[6] == 2848          # the figures include/hexgnn.h and DESIGN.md 7.9 quote
+    assert max(by_nt) < 65536                              # row offsets in LDS are 16-bit

@@ -127,6 +127,8 @@ _SIGS = {
     "hexgnn_per_sample_dev": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
     "hexgnn_replay_offsets": (ci, [ci, vp, ci, ci, vp, vp, vp, vp, vp]),
     "hexgnn_select_actions": (ci, [ci, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
+    "hexgnn_sample_actions": (ci, [ci, vp, vp, vp, ci, C.c_float, vp, vp, vp, vp, vp]),
+    "hexgnn_arena_ply": (ci, [vp, vp, vp, vp, ci, C.c_float, vp, vp, ci, vp, vp, vp, vp, vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_forward_backward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

@@ -12,7 +12,7 @@
 // clique" / "find the twin" are per-lane tests combined with wave ballots.  Integer/bit work: no MFMA, bound by LDS
 // latency; results are bit-exact against oracle/env_ref.c (same canonical ascending order).
 #include <vector>
-#include "hexgnn_common.h"
+#include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
@@ -492,6 +492,83 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev d, const int* __res
     }
 }
 
+// One ply of a match (include/hexgnn.h: hexgnn_arena_ply): pick with graph_pick, play the vertex exactly as env_step_kernel does
+// with dead/captured removal and auto reset, and keep the game's record.  A decided game rests: only its side flag flips.
+template <int WT>
+__global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __restrict__ gptr, const float* __restrict__ q,
+                                                     const int64_t* __restrict__ backmap, int mode, float temperature,
+                                                     const float* __restrict__ u, int* __restrict__ forced,
+                                                     int reset_maker_turn, int* __restrict__ game, int* __restrict__ log_row,
+                                                     int* __restrict__ result, int* __restrict__ live) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int env = blockIdx.x, lane = threadIdx.x;
+    GameT<WT> g;
+    using Sets = typename GameT<WT>::Sets;
+    load_game(g, d, env, lds);
+    int* rec = game + 4 * env;
+    int* res = result + 5 * env;
+    int mt = d.maker_turn[env], moves = d.total_moves[env];
+    if (rec[0] >= 0 || rec[3] != 0) {                         // resting: nothing but the side flag and the sizes
+        int na, ne;
+        count_game(g, &na, &ne);
+        if (lane == 0) {
+            d.maker_turn[env] = !mt;
+            log_row[env] = -1;
+            res[0] = -1; res[1] = 0; res[2] = na; res[3] = ne; res[4] = 0;
+        }
+        return;
+    }
+    short* rm = d.resp_maker + (size_t)env * d.nv;
+    short* rb = d.resp_breaker + (size_t)env * d.nv;
+    int v = forced ? forced[env] : -1;
+    int err = 0;
+    if (v >= 2) {
+        __syncthreads();                                      // every lane has read the entry
+        if (lane == 0) forced[env] = -1;
+    } else {
+        const int r0 = gptr[env], r1 = gptr[env + 1];
+        bool bad;
+        const int rank = graph_pick(q, r0, r1, lane, mode, temperature, u ? u[env] : 0.f, bad);
+        v = rank >= 0 ? (int)backmap[r0 + rank] : -1;
+        if (bad) err = 2;
+    }
+    if (!err && (v < 2 || v >= d.nv || !g.alive[v])) err = 1;
+    int winner = -1;
+    if (!err) {
+        ++moves;
+        Sets consider;
+#pragma unroll
+        for (int w = 0; w < WT; ++w) consider.w[w] = 0ull;
+        if (mt) consider = g.maker_connect(v);
+        const Sets nbv = g.get_row(v);
+#pragma unroll
+        for (int w = 0; w < WT; ++w) consider.w[w] |= nbv.w[w];
+        g.remove_vertex(v);
+        mt = !mt;
+        if (!g.maker_won) g.dead_and_captured(consider, rm, rb);
+        winner = g.who_won();
+    }
+    const int length = moves;
+    if (winner >= 0) {
+        reset_game_lds(g, d);
+        for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
+        mt = reset_maker_turn;
+        moves = 0;
+    }
+    int na, ne;
+    count_game(g, &na, &ne);
+    store_game(g, d, env);
+    if (lane == 0) {
+        d.maker_turn[env] = mt; d.total_moves[env] = moves;
+        res[0] = winner; res[1] = length; res[2] = na; res[3] = ne; res[4] = err ? 1 : 0;
+        if (winner >= 0) { rec[0] = winner; rec[1] = length; }
+        if (!err) rec[2] += 1;
+        rec[3] = err;
+        log_row[env] = v;
+        if (winner < 0 && !err) atomicAdd(live, 1);
+    }
+}
+
 // Observation of every env into batched buffers (convert_graph.py:77-122, old_style=True; Batch.from_data_list):
 //   x [N][3] = (degree, is_terminal, maker_to_move);  backmap [N] rank -> vertex id (int64)
 //   edge_local [2][E]: per graph, first the E_g/2 edges (s > t, sorted by (s,t)) then the flipped copies, LOCAL ranks
@@ -655,6 +732,19 @@ static void launch_env_step(const EnvDev& d, const int* actions, int remove_dc, 
     env_step_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, actions, remove_dc, auto_reset, reset_maker_turn, result);
 }
 
+template <int WT>
+static void launch_arena_ply(const EnvDev& d, const int* gptr, const float* q, const int64_t* backmap, int mode, float temperature,
+                             const float* u, int* forced, int reset_maker_turn, int* game, int* log_row, int* result, int* live,
+                             hipStream_t st) {
+    static bool once = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&arena_ply_kernel<WT>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        return true;
+    }();
+    (void)once;
+    arena_ply_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, gptr, q, backmap, mode, temperature, u, forced,
+                                                                    reset_maker_turn, game, log_row, result, live);
+}
 
 }  // namespace hexgnn
 
@@ -769,6 +859,28 @@ int hexgnn_env_step(hexgnn_env* h, const int* actions, int remove_dead_and_captu
         case 3: launch_env_step<3>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
         case 4: launch_env_step<4>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
         default: launch_env_step<kMaxW>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
+    }
+    return check_launch();
+}
+
+int hexgnn_arena_ply(hexgnn_env* h, const int* gptr, const float* q, const int64_t* backmap, int mode, float temperature,
+                     const float* u, int* forced, int reset_maker_turn, int* game, int* log_row, int* result, int* live,
+                     hexgnn_stream_t stream_) {
+    if (!h || !gptr || !backmap || !game || !log_row || !result || !live) return HEXGNN_EINVAL;
+    if (mode < HEXGNN_PICK_GREEDY || mode > HEXGNN_PICK_SOFTMAX) return HEXGNN_EINVAL;
+    if ((!q && mode != HEXGNN_PICK_UNIFORM) || (!u && mode != HEXGNN_PICK_GREEDY)) return HEXGNN_EINVAL;
+    if (mode == HEXGNN_PICK_SOFTMAX && !(temperature > 0.f && temperature < INFINITY)) return HEXGNN_EINVAL;
+    Env* e = reinterpret_cast<Env*>(h);
+    hipStream_t st = (hipStream_t)stream_;
+    const hipError_t me = hipMemsetAsync(live, 0, sizeof(int), st);
+    if (me != hipSuccess) { g_last_hip_error = (int)me; return HEXGNN_EHIP; }
+    const int rm = reset_maker_turn ? 1 : 0;
+    switch (e->d.W) {          // as hexgnn_env_step: register-resident vertex sets for the common board sizes
+        case 1: launch_arena_ply<1>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
+        case 2: launch_arena_ply<2>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
+        case 3: launch_arena_ply<3>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
+        case 4: launch_arena_ply<4>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
+        default: launch_arena_ply<kMaxW>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
     }
     return check_launch();
 }

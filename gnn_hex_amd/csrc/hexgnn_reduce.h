@@ -50,6 +50,70 @@ __device__ __forceinline__ void graph_first_max(const float* q, int r0, int r1, 
     }
 }
 
+// One wave: pick a node of a graph from its non-terminal rows [r0 + 2, r1) of q (nact = r1 - r0 - 2 of them).  Returns the node's
+// rank inside the graph (>= 2) in every lane; -1 for a graph without such a row, 2 for a graph with exactly one (in every mode,
+// GN0/RainbowDQN/evaluate_elo.py:255-257).  HEXGNN_PICK_*:
+//   GREEDY   the first maximum, exactly graph_first_max (a NaN never compares greater: it is never picked).
+//   UNIFORM  2 + min(floor(u * nact), nact - 1), the exploration formula of select_actions_kernel; q is not read (may be null).
+//   SOFTMAX  one draw from Categorical(softmax(q / T)) (evaluate_elo.py:267-273) as an inverse-CDF lookup of the caller's uniform
+//            u in [0, 1), T > 0.  The contract, all in fp32: m = the maximum; w_j = expf((q_j - m) / T); inclusive prefix sums
+//            s_j in ascending row order, rows taken in chunks of 64 consecutive rows -- a wave inclusive scan (shift-and-add over
+//            distances 1, 2, .. 32) plus the running carry of the chunks before -- so the order of every addition depends on
+//            nothing but the row count; S = the last prefix; the pick is the smallest j with s_j > u * S, and where rounding
+//            leaves none the last j with w_j > 0.  Shift-invariant per graph: advantages sample the distribution of full Q.
+// bad is set when GREEDY or SOFTMAX meet a NaN among the rows, or SOFTMAX an infinite maximum (the weights are undefined): the
+// SOFTMAX pick is then rank 2, the GREEDY pick stays graph_first_max's.
+__device__ __forceinline__ int graph_pick(const float* q, int r0, int r1, int lane, int mode, float temperature, float u,
+                                          bool& bad) {
+    bad = false;
+    const int nact = r1 - r0 - 2;
+    if (nact <= 0) return -1;
+    if (mode == HEXGNN_PICK_UNIFORM) {
+        int k = (int)(u * (float)nact);
+        if (k >= nact) k = nact - 1;
+        return 2 + k;
+    }
+    float m;
+    int arg;
+    graph_first_max(q, r0, r1, lane, m, arg);
+    bool nan = false;
+    for (int i = r0 + 2 + lane; i < r1; i += 64) nan |= q[i] != q[i];
+    nan = __any(nan);
+    if (mode == HEXGNN_PICK_GREEDY) {
+        bad = nan;
+        if (nact == 1) return 2;
+        return arg == 0x7fffffff ? -1 : arg - r0;
+    }
+    bad = nan || m == INFINITY || m == -INFINITY;
+    if (bad || nact == 1) return 2;
+    // pass 1: the total S; pass 2 repeats the same additions, so its prefixes are the ones S was built from
+    float S = 0.f, thr = 0.f;
+    int pick = -1, last = -1;
+    for (int pass = 0; pass < 2; ++pass) {
+        float carry = 0.f;
+        for (int base = r0 + 2; base < r1; base += 64) {
+            const int i = base + lane;
+            const float w = i < r1 ? expf((q[i] - m) / temperature) : 0.f;
+            float s = w;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float t = __shfl_up(s, off);
+                if (lane >= off) s += t;
+            }
+            s += carry;
+            carry = __shfl(s, 63);
+            if (pass == 1) {
+                const uint64_t hit = __ballot(i < r1 && s > thr), pos = __ballot(w > 0.f);
+                if (pos) last = base + 63 - __builtin_clzll(pos);
+                if (hit) { pick = base + __builtin_ctzll(hit); break; }
+            }
+        }
+        if (pass == 0) { S = carry; thr = u * S; }
+    }
+    if (pick < 0) pick = last;
+    return pick - r0;
+}
+
 // ---- the head's small parameter-gradient sums over the graphs, one wave per output (lanes stride over the graphs) ------------
 // advantage Linear: column c in [0, H] (H == bias, kept at column hp) of the per-graph partials lin_part [b][hp + 1]
 __device__ __forceinline__ void lin_part_column_sum(int b, int hp, int H, const float* lin_part, int c, int lane,

@@ -522,10 +522,16 @@ class Env_manager:
             return states.backmap[base + idx].tolist()
         return [state.backmap[action].item() for state, action in zip(states, actions)]
 
-    def select_actions(self, q: torch.Tensor, states: "ObsList" = None, eps: float = 0.0, generator=None):
+    def select_actions(self, q: torch.Tensor, states: "ObsList" = None, eps: float = 0.0, generator=None,
+                       temperature: float = None):
         """Device-side acting: epsilon-greedy over each env's non-terminal nodes given the model output for the batched
         observation (``Q`` or ``advantages_only`` values).  Returns ``(vertex_actions int32 [num_envs] on the device --
-        ready for ``step`` --, node ranks, exploratory flags)``; nothing is copied to the host."""
+        ready for ``step`` --, node ranks, exploratory flags)``; nothing is copied to the host.
+
+        With a ``temperature`` every env's move is instead one draw from softmax(q / temperature) over its non-terminal nodes
+        (GN0/RainbowDQN/evaluate_elo.py:267-273; 0 = the first maximum), from one uniform per env out of ``generator``;
+        ``eps`` must then be 0, no move counts as exploratory, and ``self.sample_status`` (int32 [1] on the device) is
+        non-zero when some env's values held a NaN."""
         states = states if states is not None else self.last_obs
         dev = self.device
         k = len(states)
@@ -535,6 +541,18 @@ class Env_manager:
         qf = q.reshape(-1).float().contiguous()
         vert = torch.empty(k, dtype=torch.int32, device=dev)
         rank = torch.empty(k, dtype=torch.int32, device=dev)
+        if temperature is not None:
+            temperature = float(temperature)
+            if eps != 0 or not temperature >= 0.0 or temperature == float("inf"):
+                raise ValueError("temperature sampling takes eps == 0 and a finite temperature >= 0")
+            u = torch.rand(k, dtype=torch.float32, device=dev, generator=generator)
+            self.sample_status = torch.empty(1, dtype=torch.int32, device=dev)
+            _lib.check(_lib.lib().hexgnn_sample_actions(k, gptr.data_ptr(), qf.data_ptr(), states.backmap.data_ptr(),
+                                                        2 if temperature > 0 else 0, temperature if temperature > 0 else 1.0,
+                                                        u.data_ptr(), vert.data_ptr(), rank.data_ptr(),
+                                                        self.sample_status.data_ptr(), ops._stream()),
+                       "hexgnn_sample_actions")
+            return vert, rank, torch.zeros(k, dtype=torch.bool, device=dev)
         expl = torch.empty(k, dtype=torch.uint8, device=dev)
         u = torch.rand((k, 2), dtype=torch.float32, device=dev, generator=generator) if eps > 0 else None
         _lib.check(_lib.lib().hexgnn_select_actions(k, gptr.data_ptr(), qf.data_ptr(), states.backmap.data_ptr(),

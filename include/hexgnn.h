@@ -683,6 +683,40 @@ int hexgnn_select_actions(int b, const int* gptr, const float* q, const int64_t*
                           int* action_vertex /*[b]*/, int* action_rank /*[b]*/, uint8_t* exploratory /*[b] or NULL*/,
                           hexgnn_stream_t stream);
 
+/* ---- match play (entry points added to ABI 6, nothing existing changes): model-vs-model games as a closed device loop,
+ *      the evaluation side of the RainbowDQN loop (Elo_handler.play_some_games, GN0/RainbowDQN/evaluate_elo.py:185-345).
+ *      How a node of a graph is picked from q[gptr[g]+2 : gptr[g+1]]: */
+#define HEXGNN_PICK_GREEDY 0   /* the first maximum, hexgnn_select_actions' comparison */
+#define HEXGNN_PICK_UNIFORM 1  /* rank 2 + min(floor(u * n_act), n_act - 1), hexgnn_select_actions' exploration; q is not read */
+#define HEXGNN_PICK_SOFTMAX 2  /* one draw from Categorical(softmax(q / temperature)) (evaluate_elo.py:267-273) by inverse CDF
+                                  from the caller's uniform u in [0, 1); the fp32 summation order is fixed by the row count
+                                  alone (gnn_hex_amd/csrc/hexgnn_reduce.h states the contract), so a draw is reproducible */
+/* The selection alone, one uniform per graph: u [b] (may be NULL for GREEDY), temperature > 0 for SOFTMAX.  Outputs as
+ * hexgnn_select_actions (rank -1 / vertex -1 for a graph without a non-terminal node; a graph with exactly one gets rank 2);
+ * status (int32 on the device, may be NULL) is zeroed and then receives bit 0 when GREEDY or SOFTMAX met a NaN (or SOFTMAX an
+ * infinite maximum) in some graph: SOFTMAX picks rank 2 there, GREEDY keeps its comparison's result.  q may be NULL for UNIFORM. */
+int hexgnn_sample_actions(int b, const int* gptr, const float* q, const int64_t* backmap, int mode, float temperature,
+                          const float* u /*[b]*/, int* action_vertex /*[b] or NULL*/, int* action_rank /*[b]*/,
+                          int* status /*[1] or NULL*/, hexgnn_stream_t stream);
+/* One ply of a match in one launch, one workgroup per game (= env): pick a node as above from the batched observation's q
+ * (gptr = the node_off of hexgnn_env_observe; u [num_envs]; q may be NULL for UNIFORM, the built-in random player), play it
+ * as hexgnn_env_step does with dead/captured removal and auto reset, and record.
+ *   forced [num_envs] int32 (device, may be NULL): an entry >= 2 is a vertex to play instead of picking; it is overwritten
+ *          with -1 once used (fixed openings enter at ply 0 through the same launch).
+ *   game   [num_envs][4] int32 in/out = (winner -1 / 0 maker / 1 breaker, length, plies played, error).  A game whose record
+ *          holds a winner or an error RESTS: no pick, no move, log entry -1; only its env's side-to-move flag flips, so that
+ *          the batched observation keeps one side for all graphs.  A game that finishes in this ply records winner and length
+ *          once and its env restarts at the start position with reset_maker_turn to move.  error: 1 = the forced or picked
+ *          vertex is not a live non-terminal vertex, 2 = NaN (or, for SOFTMAX, an infinite maximum) in the game's q rows;
+ *          the env is left untouched and the game ends.
+ *   log_row [num_envs] int32: the vertex played in this ply (-1 for a resting game).
+ *   result [num_envs][5]: hexgnn_env_step's record for a game that moved; (-1, 0, nodes, edges, 0) for a resting one --
+ *          the sizes feed hexgnn_env_offsets either way.
+ *   live   [1] int32: zeroed, then the number of games still undecided after this ply. */
+int hexgnn_arena_ply(hexgnn_env* env, const int* gptr, const float* q, const int64_t* backmap, int mode, float temperature,
+                     const float* u, int* forced, int reset_maker_turn, int* game, int* log_row, int* result, int* live,
+                     hexgnn_stream_t stream);
+
 /* ---- layout helpers (host tensors <-> padded layout) ---------------------------------------- */
 /* dst[n][HP] <- src[n][hidden] (row stride src_stride floats), pad columns zeroed; and back. */
 int hexgnn_pad_rows(int n, int hidden, const float* src, int src_stride, float* dst, hexgnn_stream_t stream);

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib, ops
 from .multi_env_manager import Env_manager
+from .observation import ObsTarget, acting_forward, live_norm_of
 
 PICK_GREEDY, PICK_UNIFORM, PICK_SOFTMAX = 0, 1, 2      # HEXGNN_PICK_* of include/hexgnn.h
 
@@ -65,24 +66,13 @@ class DeviceArena:
         dev = self.device = mgr.device
         k, nv = num_games, mgr._nv
         e_max = int(mgr._base_sizes[0, 1])
-        N, E = k * nv, k * e_max
-        # capacity-sized observation buffers (every env at the start position), as DeviceRollout keeps them
-        self.x = torch.zeros((N, 3), dtype=torch.float32, device=dev)
-        self.backmap = torch.zeros(N, dtype=torch.long, device=dev)
-        self.batch_vec = torch.zeros(N, dtype=torch.long, device=dev)
-        self.edge_local = torch.zeros((2, E), dtype=torch.long, device=dev)
-        self.edge_global = torch.zeros((2, E), dtype=torch.long, device=dev)
-        rowptr = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-        col = torch.zeros(E, dtype=torch.int32, device=dev)
-        invdeg = torch.ones(N, dtype=torch.float32, device=dev)
-        self.gs = ops.GraphStructure.from_csr(N, E, rowptr, col, invdeg)
-        self.node_off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
-        self.edge_off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
+        # capacity-sized observation (every env at the start position), as DeviceRollout keeps it; the players are not known
+        # yet, so the tail clear is always there
+        self.obs = ObsTarget.capacity(k, nv, e_max, dev, zeroed=True, tail_clear=True)
         off = np.zeros((2, k + 1), dtype=np.int32)
         off[0] = np.arange(k + 1) * nv
         off[1] = np.arange(k + 1) * e_max
         self._start_off = torch.from_numpy(off).to(dev)
-        self._iota = torch.arange(N + 1, dtype=torch.int32, device=dev)
         self.max_plies = hex_size * hex_size + chunk
         rows = -(-self.max_plies // chunk) * chunk
         self.log = torch.zeros((rows, k), dtype=torch.int32, device=dev)
@@ -102,62 +92,39 @@ class DeviceArena:
             return False
         if not callable(player):
             raise TypeError("a player is a model from get_pre_defined or the string \"random\", not %r" % (player,))
-        norms = getattr(getattr(player, "gnn", None), "norms", None)
-        if norms is not None and any(type(m).__name__ != "LayerNorm" for m in norms):
-            raise NotImplementedError("DeviceRollout supports the whole-batch LayerNorm of --norm=True; per-channel "
-                                      "CachedGraphNorm statistics need exact-size batches: use Env_manager.observe()/step()")
-        return norms is not None
+        return live_norm_of(player)
 
     def _prepare(self, maker_first: bool, forced: Optional[torch.Tensor]):
         """All envs at the start position with ``first`` to move, every game undecided, the openings in place."""
         _lib.check(_lib.lib().hexgnn_env_reset(self.mgr._h, None, int(maker_first), None, ops._stream()), "hexgnn_env_reset")
-        self.node_off.copy_(self._start_off[0])
-        self.edge_off.copy_(self._start_off[1])
+        self.obs.node_off.copy_(self._start_off[0])
+        self.obs.edge_off.copy_(self._start_off[1])
         self.game.copy_(self._game0)
         if forced is None:
             self.forced.fill_(-1)
         else:
             self.forced.copy_(forced)
 
-    def _forward(self, model, maker: bool, live_norm: bool):
-        k = self.num_games
-        if self.mgr._nv > 128 or live_norm:
-            # layer-major kernels (boards above 128 nodes, --norm=True) walk ALL rows of the capacity-sized buffers: rows past
-            # the current total must be empty, not what an earlier, larger observation left there
-            torch.where(self._iota > self.node_off[k], self.edge_off[k], self.gs.rowptr, out=self.gs.rowptr)
-        x = self.x.view(self.x.shape)           # a fresh tensor object per ply: the hints differ per side
-        x._hex_is_maker = maker
-        x._hex_max_nodes = self.mgr._nv
-        x._hex_hint_version = x._version
-        ei = self.edge_global.view(self.edge_global.shape)
-        ei._hex_csr = self.gs
-        with torch.no_grad(), ops.live_rows(self.node_off[k:k + 1] if live_norm else None):
-            return model(x, ei, self.batch_vec, self.node_off, advantages_only=True)
-
     def _body(self, players, maker_first: bool, modes, temperature: float):
         """``chunk`` plies.  players / modes: (the maker's, the breaker's)."""
         L = _lib.lib()
-        h, k = self.mgr._h, self.num_games
-        E = int(self.edge_global.shape[1])
+        h, k, obs = self.mgr._h, self.num_games, self.obs
         maker = maker_first
         for t in range(self.chunk):
-            _lib.check(L.hexgnn_env_observe(h, self.node_off.data_ptr(), self.edge_off.data_ptr(), E, self.x.data_ptr(),
-                                            self.backmap.data_ptr(), self.edge_local.data_ptr(), self.edge_global.data_ptr(),
-                                            self.gs.rowptr.data_ptr(), self.gs.col.data_ptr(), self.gs.invdeg.data_ptr(),
-                                            self.batch_vec.data_ptr(), ops._stream()), "hexgnn_env_observe")
+            obs.observe_env(h)
             (player, live_norm), mode = players[0 if maker else 1], modes[0 if maker else 1]
             q = None
             if mode != PICK_UNIFORM:            # the built-in random player needs no forward
-                q = self._forward(player, maker, live_norm).reshape(-1)
+                q = acting_forward(player, obs, maker, self.mgr._nv, live_norm).reshape(-1)
                 if q.dtype != torch.float32 or not q.is_contiguous():
                     q = q.float().contiguous()
             # a game that ends restarts on the side everyone moves to next
-            _lib.check(L.hexgnn_arena_ply(h, self.node_off.data_ptr(), q.data_ptr() if q is not None else None,
-                                          self.backmap.data_ptr(), mode, float(temperature) if mode == PICK_SOFTMAX else 1.0,
+            _lib.check(L.hexgnn_arena_ply(h, obs.node_off.data_ptr(), q.data_ptr() if q is not None else None,
+                                          obs.backmap.data_ptr(), mode, float(temperature) if mode == PICK_SOFTMAX else 1.0,
                                           self.uni[t].data_ptr(), self.forced.data_ptr(), int(not maker),
                                           self.game.data_ptr(), self.log_chunk[t].data_ptr(), self.result.data_ptr(),
                                           self.live.data_ptr(), ops._stream()), "hexgnn_arena_ply")
-            _lib.check(L.hexgnn_env_offsets(k, self.result.data_ptr(), self.node_off.data_ptr(), self.edge_off.data_ptr(),
+            _lib.check(L.hexgnn_env_offsets(k, self.result.data_ptr(), obs.node_off.data_ptr(), obs.edge_off.data_ptr(),
                                             ops._stream()), "hexgnn_env_offsets")
             maker = not maker
 

@@ -13,6 +13,8 @@ from typing import List, Optional
 
 import torch
 
+from . import ops
+
 
 BLOCK_ROWS = 128         # rows of one workgroup of the layer-major kernels (gnn_hex_amd/csrc/sage_layer.hip, sage_stack.hip)
 MAX_TABLE_BLOCKS = 512   # blocks of one table (kStackFlagWords: the progress counters of a call, indexed by block)
@@ -261,7 +263,6 @@ class Batch(Data):
         sizes = [int(d.x.shape[0]) for d in data_list]
         if dev0.type == "cuda" and max(sizes) > BLOCK_ROWS:
             if max_blocks is None:
-                from . import ops
                 max_blocks = ops.stack_block_budget(dev0)
             # (groups: only where not even the default 128-row blocks can be resident at once)
             want_groups = want_groups and -(-sum(sizes) // BLOCK_ROWS) > max_blocks
@@ -305,10 +306,7 @@ class Batch(Data):
         out._num_graphs = len(sizes)
         # host-known batch metadata spares the model two device->host syncs (side to move, largest graph)
         sides = {getattr(d.x, "_hex_is_maker", None) for d in data_list}
-        if len(sides) == 1 and None not in sides:
-            out.x._hex_is_maker = sides.pop()
-        out.x._hex_max_nodes = max(sizes)
-        out.x._hex_hint_version = out.x._version
+        ops.attach_hints(out.x, sides.pop() if len(sides) == 1 else None, max(sizes))
         out.edge_index._hex_grouped = True      # collated graph by graph: the one-launch CSR build applies
         # ... and knows every graph's edge range without searching for it (torch_geometric keeps the same slices in _slice_dict)
         ecnt = torch.tensor([0] + [int(d.edge_index.shape[1]) for d in data_list], dtype=torch.long)

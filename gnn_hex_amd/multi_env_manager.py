@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, ops
 from .data import Batch, Data
+from .observation import ObsTarget, acting_forward, live_norm_of, prefix_offsets
 
 
 class ObsList:
@@ -47,9 +48,7 @@ class ObsList:
             n0, n1 = self.node_off[i], self.node_off[i + 1]
             e0, e1 = self.edge_off[i], self.edge_off[i + 1]
             d = Data(x=self.x[n0:n1], edge_index=self.edge_local[:, e0:e1], backmap=self.backmap[n0:n1])
-            d.x._hex_is_maker = self.is_maker
-            d.x._hex_max_nodes = n1 - n0
-            d.x._hex_hint_version = d.x._version
+            ops.attach_hints(d.x, self.is_maker, n1 - n0)
             d._hex_src = (self, i)
             self._items[i] = d
         return d
@@ -69,9 +68,7 @@ class ObsList:
             self._ptr = torch.tensor(self.node_off, dtype=torch.long, device=self.x.device)
         b.x, b.edge_index, b.batch, b.ptr, b.backmap = self.x, self.edge_global, self.batch_vec, self._ptr, self.backmap
         b._num_graphs = len(self)
-        b.x._hex_is_maker = self.is_maker
-        b.x._hex_max_nodes = self.max_nodes
-        b.x._hex_hint_version = b.x._version
+        ops.attach_hints(b.x, self.is_maker, self.max_nodes)
         b.edge_index._hex_csr = self.gs
         return b
 
@@ -97,10 +94,7 @@ class SnapObs(ObsList):
 
     def __init__(self, snap, sizes: np.ndarray, is_maker: bool, owner=None):
         self._owner = owner        # (DeviceRollout, run number): the snapshot is a view into that rollout's ring
-        node_off = np.zeros(sizes.shape[0] + 1, dtype=np.int64)
-        edge_off = np.zeros(sizes.shape[0] + 1, dtype=np.int64)
-        np.cumsum(sizes[:, 0], out=node_off[1:])
-        np.cumsum(sizes[:, 1], out=edge_off[1:])
+        node_off, edge_off = prefix_offsets(sizes[:, 0], sizes[:, 1])
         super().__init__(None, None, None, None, None, node_off.tolist(), edge_off.tolist(), None, is_maker,
                          int(sizes[:, 0].max()) if sizes.shape[0] else 0, snap)
 
@@ -149,31 +143,14 @@ class DeviceRollout:
     def __init__(self, mgr: "Env_manager", model, steps: int = 16, eps: float = 0.05, graph: bool = True):
         if steps < 2 or steps % 2:
             raise ValueError("steps must be a positive even number")
-        norms = getattr(getattr(model, "gnn", None), "norms", None)
-        # --norm=True normalises over the LIVE batch (all nodes of the current observation).  The rollout hands the model
-        # capacity-sized buffers (num_envs * nv rows) whose tail rows are stale once nodes have been removed: the norm kernels
-        # take the live node total from the device-side prefix sums instead (ops.live_rows).
-        self._live_norm = norms is not None
-        if norms is not None and any(type(m).__name__ != "LayerNorm" for m in norms):
-            raise NotImplementedError("DeviceRollout supports the whole-batch LayerNorm of --norm=True; per-channel "
-                                      "CachedGraphNorm statistics need exact-size batches: use Env_manager.observe()/step()")
+        self._live_norm = live_norm_of(model)
         self.mgr, self.model, self.T, self.eps = mgr, model, steps, float(eps)
         self.start_side = mgr.global_onturn
         dev = mgr.device
         k, nv, W = mgr.num_envs, mgr._nv, mgr._words
-        e_max = int(mgr._base_sizes[0, 1])
-        N, E = k * nv, k * e_max
-        self.x = torch.zeros((N, 3), dtype=torch.float32, device=dev)
-        self.backmap = torch.zeros(N, dtype=torch.long, device=dev)
-        self.batch_vec = torch.zeros(N, dtype=torch.long, device=dev)
-        self.edge_local = torch.zeros((2, E), dtype=torch.long, device=dev)
-        self.edge_global = torch.zeros((2, E), dtype=torch.long, device=dev)
-        rowptr = torch.zeros(N + 1, dtype=torch.int32, device=dev)
-        col = torch.zeros(E, dtype=torch.int32, device=dev)
-        invdeg = torch.ones(N, dtype=torch.float32, device=dev)
-        self.gs = ops.GraphStructure.from_csr(N, E, rowptr, col, invdeg)
-        self.node_off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
-        self.edge_off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
+        # capacity-sized observation (every env at the start position); the tail clear only where the forward needs it
+        self.obs = ObsTarget.capacity(k, nv, int(mgr._base_sizes[0, 1]), dev, zeroed=True,
+                                      tail_clear=nv > 128 or self._live_norm)
         T = steps
         self.vert = torch.zeros((T, k), dtype=torch.int32, device=dev)
         self.rank = torch.zeros((T, k), dtype=torch.int32, device=dev)
@@ -184,27 +161,16 @@ class DeviceRollout:
         self.alive = torch.zeros((T + 1, k, nv), dtype=torch.uint8, device=dev)
         self._mt = torch.zeros(k, dtype=torch.int32, device=dev)
         self._tm = torch.zeros(k, dtype=torch.int32, device=dev)
-        self._iota = torch.arange(N + 1, dtype=torch.int32, device=dev) if nv > 128 or self._live_norm else None
         self._run_no = 0           # bumped by every run(): results of earlier runs view overwritten snapshots
         self._graph = None
         if graph:
             from .graphs import GraphedStep
-            self._upload_offsets()
+            self.obs.set_offsets(mgr._sizes)
             state = self.mgr._state_tensors()
             self._graph = GraphedStep(self._body, warmup=1)
             self.mgr._restore_state_tensors(state)      # warm-up + capture played moves: put the boards back
 
     # -- pieces ----------------------------------------------------------------------------------------
-    def _upload_offsets(self):
-        sizes = self.mgr._sizes
-        k = self.mgr.num_envs
-        off = np.zeros(2 * (k + 1), dtype=np.int32)
-        np.cumsum(sizes[:, 0], out=off[1:k + 1])
-        np.cumsum(sizes[:, 1], out=off[k + 2:])
-        t = torch.from_numpy(off).to(self.mgr.device)
-        self.node_off.copy_(t[:k + 1])
-        self.edge_off.copy_(t[k + 1:])
-
     def _export(self, slot: int):
         _lib.check(_lib.lib().hexgnn_env_export(self.mgr._h, self.adj[slot].data_ptr(), self.alive[slot].data_ptr(),
                                                self._mt.data_ptr(), self._tm.data_ptr(), None, None, ops._stream()),
@@ -212,42 +178,25 @@ class DeviceRollout:
 
     def _body(self):
         L = _lib.lib()
-        mgr, k = self.mgr, self.mgr.num_envs
-        E = int(self.edge_global.shape[1])
+        mgr, k, obs = self.mgr, self.mgr.num_envs, self.obs
         self._export(0)
         maker = self.start_side == "m"
         for t in range(self.T):
-            _lib.check(L.hexgnn_env_observe(mgr._h, self.node_off.data_ptr(), self.edge_off.data_ptr(), E,
-                                            self.x.data_ptr(), self.backmap.data_ptr(), self.edge_local.data_ptr(),
-                                            self.edge_global.data_ptr(), self.gs.rowptr.data_ptr(), self.gs.col.data_ptr(),
-                                            self.gs.invdeg.data_ptr(), self.batch_vec.data_ptr(), ops._stream()),
-                       "hexgnn_env_observe")
-            if self._iota is not None:
-                # Boards above 128 nodes (and --norm=True models) run on the layer-major kernels, which walk ALL rows of the capacity-sized buffers:
-                # rows past the current total must be empty, not whatever an earlier, larger observation left there (the
-                # row right behind the end marker otherwise shows a bogus degree of thousands: 146 us per layer launch).
-                torch.where(self._iota > self.node_off[k], self.edge_off[k], self.gs.rowptr, out=self.gs.rowptr)
-            x = self.x.view(self.x.shape)       # fresh tensor object per step: the hints below differ per side
-            x._hex_is_maker = maker
-            x._hex_max_nodes = mgr._nv
-            x._hex_hint_version = x._version
-            ei = self.edge_global.view(self.edge_global.shape)
-            ei._hex_csr = self.gs
-            with torch.no_grad(), ops.live_rows(self.node_off[k:k + 1] if self._live_norm else None):
-                adv = self.model(x, ei, self.batch_vec, self.node_off, advantages_only=True)
+            obs.observe_env(mgr._h)
+            adv = acting_forward(self.model, obs, maker, mgr._nv, self._live_norm)
             u = None
             if self.eps > 0:
                 u = self.uni[t]
                 u.uniform_()
-            _lib.check(L.hexgnn_select_actions(k, self.node_off.data_ptr(), adv.reshape(-1).data_ptr(),
-                                               self.backmap.data_ptr(), self.eps, u.data_ptr() if u is not None else None,
+            _lib.check(L.hexgnn_select_actions(k, obs.node_off.data_ptr(), adv.reshape(-1).data_ptr(),
+                                               obs.backmap.data_ptr(), self.eps, u.data_ptr() if u is not None else None,
                                                self.vert[t].data_ptr(), self.rank[t].data_ptr(), self.expl[t].data_ptr(),
                                                ops._stream()), "hexgnn_select_actions")
             # finished envs restart on the side everyone moves to next (multi_env_manager.py:98-101)
             _lib.check(L.hexgnn_env_step(mgr._h, self.vert[t].data_ptr(), 1, 1, int(not maker), self.result[t].data_ptr(),
                                          ops._stream()), "hexgnn_env_step")
-            _lib.check(L.hexgnn_env_offsets(k, self.result[t].data_ptr(), self.node_off.data_ptr(),
-                                            self.edge_off.data_ptr(), ops._stream()), "hexgnn_env_offsets")
+            _lib.check(L.hexgnn_env_offsets(k, self.result[t].data_ptr(), obs.node_off.data_ptr(),
+                                            obs.edge_off.data_ptr(), ops._stream()), "hexgnn_env_offsets")
             self._export(t + 1)
             maker = not maker
 
@@ -267,7 +216,7 @@ class DeviceRollout:
             raise RuntimeError("run_begin() called twice without run_end()")
         sizes0 = mgr._sizes.copy()
         self._run_no += 1
-        self._upload_offsets()
+        self.obs.set_offsets(mgr._sizes)
         if self._graph is not None:
             self._graph.replay()
         else:
@@ -469,35 +418,12 @@ class Env_manager:
         return adj, alive
 
     def _observe_handle(self, h, sizes, is_maker) -> ObsList:
-        L = _lib.lib()
-        dev = self.device
         k = sizes.shape[0]
-        node_off = np.zeros(k + 1, dtype=np.int64)
-        edge_off = np.zeros(k + 1, dtype=np.int64)
-        np.cumsum(sizes[:, 0], out=node_off[1:])
-        np.cumsum(sizes[:, 1], out=edge_off[1:])
-        N, E = int(node_off[-1]), int(edge_off[-1])
-        offs = torch.from_numpy(np.concatenate([node_off, edge_off]).astype(np.int32)).to(dev, non_blocking=True)
-        x = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        backmap = torch.empty(N, dtype=torch.long, device=dev)
-        batch_vec = torch.empty(N, dtype=torch.long, device=dev)
-        edge_local = torch.empty((2, max(E, 1)), dtype=torch.long, device=dev)[:, :E]
-        edge_global = torch.empty((2, max(E, 1)), dtype=torch.long, device=dev)[:, :E]
-        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        col = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        invdeg = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
-        if E == 0:
-            edge_local = torch.empty((2, 0), dtype=torch.long, device=dev)
-            edge_global = torch.empty((2, 0), dtype=torch.long, device=dev)
-        el_base = edge_local.data_ptr() if E > 0 else x.data_ptr()
-        eg_base = edge_global.data_ptr() if E > 0 else x.data_ptr()
-        _lib.check(L.hexgnn_env_observe(h, offs.data_ptr(), offs[k + 1:].data_ptr(), E, x.data_ptr(), backmap.data_ptr(),
-                                        el_base, eg_base, rowptr.data_ptr(), col.data_ptr(), invdeg.data_ptr(),
-                                        batch_vec.data_ptr(), ops._stream()), "hexgnn_env_observe")
-        gs = ops.GraphStructure.from_csr(N, E, rowptr, col, invdeg)
+        t = ObsTarget.exact(sizes, self.device)
+        t.observe_env(h)
         snap = self._snapshot_handle(h, k) if self.record_snapshots else None
-        return ObsList(x, edge_local, edge_global, backmap, batch_vec, node_off.tolist(), edge_off.tolist(), gs,
-                       is_maker, int(sizes[:, 0].max()) if k else 0, snap)
+        return ObsList(t.x, t.edge_local, t.edge_global, t.backmap, t.batch_vec, t.node_off_host.tolist(),
+                       t.edge_off_host.tolist(), t.gs, is_maker, int(sizes[:, 0].max()) if k else 0, snap)
 
     @property
     def starting_obs(self) -> Data:
@@ -737,8 +663,7 @@ class Env_manager:
                     s_next = self.starting_obs
                     s_next.__delattr__("backmap")
                     s_next.x[:, 2] = 1.0 if blk.maker_side else 0.0
-                    s_next.x._hex_is_maker = blk.maker_side
-                    s_next.x._hex_hint_version = s_next.x._version
+                    ops.attach_hints(s_next.x, blk.maker_side)
                 else:
                     s_next = blk.obs_list[nxt][env]
                     if hasattr(s_next, "backmap"):

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, ops
 from .data import Batch, block_groups, blocks_for_order, pack_groups, pack_order
+from .observation import ObsTarget
 
 
 def _pow2_at_least(n: int) -> int:
@@ -228,37 +229,14 @@ class GraphReplayBuffer:
 
     # ---- sampling ----------------------------------------------------------------------------------------
     def _build_batch(self, slots_dev: torch.Tensor, slots_host: np.ndarray, starts=None) -> Batch:
-        L = _lib.lib()
         dev = self.device
         k = len(slots_host)
-        node_off = np.zeros(k + 1, dtype=np.int64)
-        edge_off = np.zeros(k + 1, dtype=np.int64)
-        np.cumsum(self.n_nodes[slots_host], out=node_off[1:])
-        np.cumsum(self.n_edges[slots_host], out=edge_off[1:])
-        N, E = int(node_off[-1]), int(edge_off[-1])
-        offs = torch.from_numpy(np.concatenate([node_off, edge_off]).astype(np.int32)).to(dev, non_blocking=True)
-        x = torch.empty((N, 3), dtype=torch.float32, device=dev)
-        backmap = torch.empty(N, dtype=torch.long, device=dev)
-        batch_vec = torch.empty(N, dtype=torch.long, device=dev)
-        edge_local = torch.empty((2, max(E, 1)), dtype=torch.long, device=dev)
-        edge_global = torch.empty((2, max(E, 1)), dtype=torch.long, device=dev)
-        rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
-        col = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-        invdeg = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
-        idx32 = slots_dev.to(torch.int32)
-        _lib.check(L.hexgnn_states_observe(self.hex_size, k, self.adj.data_ptr(), self.alive.data_ptr(),
-                                           self.side.data_ptr(), idx32.data_ptr(), offs.data_ptr(),
-                                           offs[k + 1:].data_ptr(), E, x.data_ptr(), backmap.data_ptr(),
-                                           edge_local.data_ptr(), edge_global.data_ptr(), rowptr.data_ptr(),
-                                           col.data_ptr(), invdeg.data_ptr(), batch_vec.data_ptr(), ops._stream()),
-                   "hexgnn_states_observe")
+        t = ObsTarget.exact(np.stack([self.n_nodes[slots_host], self.n_edges[slots_host]], axis=1), dev, with_ptr=True)
+        t.observe_states(self.hex_size, self.adj, self.alive, self.side, slots_dev.to(torch.int32))
+        N, gs = t.gs.n, t.gs
         b = Batch()
-        b.x, b.edge_index, b.batch = x, edge_global[:, :E], batch_vec
-        b.ptr = torch.from_numpy(node_off).to(dev, non_blocking=True)
+        b.x, b.edge_index, b.batch, b.ptr = t.x, t.edge_global, t.batch_vec, t.ptr
         b._num_graphs = k
-        b.x._hex_max_nodes = int(self.n_nodes[slots_host].max()) if k else 0
-        b.x._hex_hint_version = b.x._version
-        gs = ops.GraphStructure.from_csr(N, E, rowptr, col, invdeg)
         if starts is not None and len(starts) - 1 <= self._max_blocks:
             gs.blocks = (torch.tensor(starts, dtype=torch.int32).to(dev, non_blocking=True), len(starts) - 1)
         elif starts is not None and self.group_blocks and -(-N // 128) > self._max_blocks:
@@ -324,10 +302,9 @@ class GraphReplayBuffer:
         state = self._build_batch(idx, host, st_blocks)
         nxt = self._build_batch(idx + self.capacity, host + self.capacity, nx_blocks)
         # all stored states of one buffer share the mover's side (maker / breaker buffers are separate)
-        state.x._hex_is_maker = bool(self.side_host[int(host[0])]) if batch_size else True
-        state.x._hex_hint_version = state.x._version
-        nxt.x._hex_is_maker = bool(self.side_host[int(host[0]) + self.capacity]) if batch_size else True
-        nxt.x._hex_hint_version = nxt.x._version
+        for b, slots in ((state, host), (nxt, host + self.capacity)):
+            ops.attach_hints(b.x, bool(self.side_host[int(slots[0])]) if batch_size else True,
+                             int(self.n_nodes[slots].max()) if batch_size else 0)
         return idx, w, state, nxt, self.action[idx], self.reward[idx], self.done[idx]
 
     # ---- sampling with sizes that never leave the device ---------------------------------------------------
@@ -426,23 +403,12 @@ class GraphReplayBuffer:
         batches = []
         for half, slots in ((bufs.state, bufs.idx32), (bufs.next, bufs.idx32_next)):
             self.draw_offsets(bufs.idx32, C if half is bufs.next else 0, half.node_off, half.edge_off, half.ptr)
-            _lib.check(L.hexgnn_states_observe(self.hex_size, k, self.adj.data_ptr(), self.alive.data_ptr(),
-                                               self.side.data_ptr(), slots.data_ptr(), half.node_off.data_ptr(),
-                                               half.edge_off.data_ptr(), k * bufs.e_cap, half.x.data_ptr(),
-                                               half.backmap.data_ptr(), half.edge_local.data_ptr(),
-                                               half.edge_global.data_ptr(), half.gs.rowptr.data_ptr(), half.gs.col.data_ptr(),
-                                               half.gs.invdeg.data_ptr(), half.batch_vec.data_ptr(), ops._stream()),
-                       "hexgnn_states_observe")
+            half.observe_states(self.hex_size, self.adj, self.alive, self.side, slots)
             b = Batch()
-            x = half.x.view(half.x.shape)                 # fresh tensor objects per draw: the hints belong to this draw
-            ei = half.edge_global.view(half.edge_global.shape)
-            b.x, b.edge_index, b.batch, b.ptr = x, ei, half.batch_vec, half.ptr
+            # (the hints belong to this draw)
+            b.x, b.edge_index = half.inputs(sides[1] if half is bufs.next else sides[0], self.nv, live_rows=True)
+            b.batch, b.ptr = half.batch_vec, half.ptr
             b._num_graphs = k
-            x._hex_is_maker = sides[1] if half is bufs.next else sides[0]
-            x._hex_max_nodes = self.nv
-            x._hex_live_rows = half.node_off[k:k + 1]
-            x._hex_hint_version = x._version
-            ei._hex_csr = half.gs
             batches.append(b)
         torch.index_select(self.action, 0, bufs.idx, out=bufs.action)
         torch.index_select(self.reward, 0, bufs.idx, out=bufs.reward)
@@ -470,24 +436,6 @@ class GraphReplayBuffer:
                                                    self.min_tree.data_ptr(), ops._stream()), "hexgnn_per_update_td")
 
 
-class _HalfBuffers:
-    """Capacity-sized storage of one batch of a device-side draw (the states or the next states)."""
-
-    def __init__(self, k: int, nv: int, e_cap: int, dev):
-        N, E = k * nv, k * e_cap
-        e = lambda *shape, dtype: torch.empty(shape, dtype=dtype, device=dev)      # noqa: E731
-        self.x = e(N, 3, dtype=torch.float32)
-        self.backmap = e(N, dtype=torch.long)
-        self.batch_vec = e(N, dtype=torch.long)
-        self.edge_local = e(2, E, dtype=torch.long)
-        self.edge_global = e(2, E, dtype=torch.long)
-        self.node_off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
-        self.edge_off = torch.zeros(k + 1, dtype=torch.int32, device=dev)
-        self.ptr = torch.zeros(k + 1, dtype=torch.int64, device=dev)
-        self.gs = ops.GraphStructure.from_csr(N, E, e(N + 1, dtype=torch.int32), e(E, dtype=torch.int32),
-                                              e(N, dtype=torch.float32))
-
-
 class DrawBuffers:
     """Everything ``GraphReplayBuffer.sample_device`` writes, for one batch size (``GraphReplayBuffer.draw_buffers``)."""
 
@@ -501,8 +449,9 @@ class DrawBuffers:
         self.action = torch.empty(k, dtype=torch.long, device=dev)
         self.reward = torch.empty(k, dtype=torch.float32, device=dev)
         self.done = torch.empty(k, dtype=torch.bool, device=dev)
-        self.state = _HalfBuffers(k, nv, e_cap, dev)
-        self.next = _HalfBuffers(k, nv, e_cap, dev)
+        # capacity-sized storage of the two batches, left as allocated: a draw writes the live rows and nothing behind them
+        self.state = ObsTarget.capacity(k, nv, e_cap, dev, zeroed=False, with_ptr=True)
+        self.next = ObsTarget.capacity(k, nv, e_cap, dev, zeroed=False, with_ptr=True)
 
 
 class GraphedUpdate:

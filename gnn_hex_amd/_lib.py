@@ -15,11 +15,31 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhexgnn.so")
 _lib = None
-ABI_VERSION = 6          # HEXGNN_ABI_VERSION of include/hexgnn.h this binding was written against
+ABI_VERSION = 7          # HEXGNN_ABI_VERSION of include/hexgnn.h this binding was written against
 
 vp = C.c_void_p
 ci = C.c_int
 sz = C.c_size_t
+
+
+def _fields(kind, names):
+    return [(name, kind) for name in names.split()]
+
+
+class QNetCall(C.Structure):
+    """``hexgnn_qnet_call`` of include/hexgnn.h, field for field in its order (tests/test_qnet_call_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes")
+                + _fields(ci, "n b c_in hidden total_layers body_layers mode math x_stride need_backward acts_layer")
+                + _fields(vp, "gptr rowptr col rowptr_t col_t invdeg x")
+                + _fields(vp, "wl bl wr lin_w lin_b v0_w v0_b v1_w v1_b")
+                + _fields(vp, "wpack acts saved workspace") + _fields(sz, "workspace_bytes")
+                + _fields(vp, "q out_v status")
+                + _fields(vp, "td_sel td_target td_weights") + _fields(ci, "td_loss_fn")
+                + _fields(vp, "td_dq td_out td_loss_part td_loss")
+                + _fields(vp, "dq d_out_v d_embeds flat offsets n_live"))
+
+
+QNET_CALL_BYTES = C.sizeof(QNetCall)
 
 _SIGS = {
     "hexgnn_abi_version": (ci, []),
@@ -88,21 +108,13 @@ _SIGS = {
                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
     "hexgnn_qnet_backward_staged": (ci, [ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp,
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, ci, vp]),
-    "hexgnn_qnet_backward_flat": (ci, [ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp,
-                                       vp, vp, vp, vp, vp, sz, vp, ci, ci, ci, vp]),
+    "hexgnn_qnet_call_forward": (ci, [C.POINTER(QNetCall), ci, vp]),
+    "hexgnn_qnet_call_backward": (ci, [C.POINTER(QNetCall), ci, ci, ci, vp]),
     "hexgnn_stack_status": (ci, [ci]),
     "hexgnn_stack_reserve_cus": (ci, [ci]),
     "hexgnn_stack_block_budget": (ci, []),
     "hexgnn_debug_stack_mode": (ci, [ci, C.c_uint]),
     "hexgnn_debug_occupy": (ci, [ci, ci, vp, sz, vp, vp]),
-    "hexgnn_qnet_forward_td": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci,
-                                    vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
-    "hexgnn_qnet_backward_flat_td": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                          vp, vp, sz, vp, ci, ci, ci, vp, vp, vp]),
-    "hexgnn_qnet_backward_flat_td_live": (ci, [ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp,
-                                               vp, vp, vp, sz, vp, ci, ci, ci, vp, vp, vp, vp]),
-    "hexgnn_qnet_step_td": (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                 vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
     "hexgnn_qnet_jobs_bytes": (sz, [ci, ci]),
     "hexgnn_qnet_multi_workspace_bytes": (sz, [ci, ci, ci, ci, ci, ci]),
     "hexgnn_qnet_forward_jobs": (ci, [ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),

@@ -4,18 +4,6 @@
 
 namespace hexgnn {
 
-#define HEXGNN_NT_SWITCH7(nt, CALL)                     \
-    switch (nt) {                                      \
-        case 1: { constexpr int NT_ = 1; CALL; } break; \
-        case 2: { constexpr int NT_ = 2; CALL; } break; \
-        case 3: { constexpr int NT_ = 3; CALL; } break; \
-        case 4: { constexpr int NT_ = 4; CALL; } break; \
-        case 5: { constexpr int NT_ = 5; CALL; } break; \
-        case 6: { constexpr int NT_ = 6; CALL; } break; \
-        case 7: { constexpr int NT_ = 7; CALL; } break; \
-        default: return HEXGNN_EUNSUPPORTED;           \
-    }
-
 int launch_qfwd_math(int nt, int math, const QFwdArgs& a, hipStream_t st) {
     if (math == 1) return launch_qfwd_split(nt, a, st);
     HEXGNN_NT_SWITCH7(nt, (launch_qfwd_m<NT_, 0>(a, st)));
@@ -43,7 +31,7 @@ struct GradReduceArgs {
     const float* dz; const float* dvr; const float* pooled; const float* z;
     float* d_v0_w; float* d_v0_b; float* d_v1_w; float* d_v1_b;
     int n0, n1, n2, n3, nbx3;
-    // R4 (one block, hexgnn_qnet_backward_flat_td): loss = (sum over the b graphs of loss_part) / b, by tree_mean_256
+    // R4 (one block, a backward with td_loss): loss = (sum over the b graphs of loss_part) / b, by tree_mean_256
     const float* loss_part; float* loss;
 };
 
@@ -172,180 +160,111 @@ int make_qplan(int n, int b, int c_in, int hidden, int L, QPlan* q) {
 }
 }  // namespace
 
-// the forward kernel's arguments from the C ABI's (one copy: hexgnn_qnet_forward* and hexgnn_qnet_step_td)
-static void fill_qfwd_args(QFwdArgs& a, const QPlan& qp, int n, int b, int c_in, int hidden, int total_layers, int mode,
-                           const int* gptr, const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
-                           const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b, const float* v1_w,
-                           const float* v1_b, void* wpack, float* acts, void* saved, int need_backward, int acts_layer,
-                           unsigned* maxima, float* q, float* out_v, int* status, const int64_t* td_sel, const float* td_target,
-                           const float* td_weights, int td_loss_fn, float* td_dq, float* td_out, float* td_loss_part) {
-    a.n = n; a.b = b; a.c_in = c_in; a.H = hidden; a.L = total_layers; a.mode = mode; a.x_stride = x_stride;
-    a.need_backward = need_backward;
-    a.acts_layer = acts_layer;
-    a.gptr = gptr; a.rowptr = rowptr; a.col = col; a.invdeg = invdeg; a.x = x;
-    a.wpack = (const char*)wpack;
-    for (int l = 0; l < total_layers; ++l) {
+// math 1 + backward: the per-layer maxima (xmax | gmax) kept behind the saved tensors, zeroed by the pack's scale kernel
+static unsigned* qfwd_maxima(const hexgnn_qnet_call& c, const QPlan& qp) {
+    return (c.math == 1 && c.need_backward) ? (unsigned*)((char*)c.saved + qp.xmax_off) : nullptr;
+}
+
+// the forward kernel's arguments from the descriptor (one copy: every forward form and the chained step)
+static void fill_qfwd_args(QFwdArgs& a, const hexgnn_qnet_call& c, const QPlan& qp) {
+    a.n = c.n; a.b = c.b; a.c_in = c.c_in; a.H = c.hidden; a.L = c.total_layers; a.mode = c.mode; a.x_stride = c.x_stride;
+    a.need_backward = c.need_backward;
+    a.acts_layer = c.acts_layer;
+    a.gptr = c.gptr; a.rowptr = c.rowptr; a.col = c.col; a.invdeg = c.invdeg; a.x = c.x;
+    a.wpack = (const char*)c.wpack;
+    for (int l = 0; l < c.total_layers; ++l) {
         a.fwd_off[l] = qp.sp.fwd_off[l]; a.bias_off[l] = qp.sp.bias_off[l]; a.agg_off[l] = qp.sp.agg_off[l];
     }
-    a.acts = acts; a.saved = (char*)saved;
-    a.lin_w = lin_w; a.lin_b = lin_b; a.v0_w = v0_w; a.v0_b = v0_b; a.v1_w = v1_w; a.v1_b = v1_b;
-    char* hsv = (char*)saved + qp.head_saved_off;
+    a.acts = c.acts; a.saved = (char*)c.saved;
+    a.lin_w = c.lin_w; a.lin_b = c.lin_b; a.v0_w = c.v0_w; a.v0_b = c.v0_b; a.v1_w = c.v1_w; a.v1_b = c.v1_b;
+    char* hsv = (char*)c.saved + qp.head_saved_off;
     a.adv_raw = (float*)(hsv + qp.hs.adv_off); a.pooled = (float*)(hsv + qp.hs.pooled_off);
     a.amax = (int*)(hsv + qp.hs.amax_off); a.amin = (int*)(hsv + qp.hs.amin_off);
     a.z = (float*)(hsv + qp.hs.z_off); a.vraw = (float*)(hsv + qp.hs.v_off);
-    a.q = q; a.out_v = out_v; a.status = status;
-    a.xmax = maxima;
-    a.td_sel = (const long long*)td_sel; a.td_tgt = td_target; a.td_w = td_weights; a.td_loss_fn = td_loss_fn;
-    a.td_dq = td_dq; a.td_out = td_out; a.td_loss_part = td_loss_part;
+    a.q = c.q; a.out_v = c.out_v; a.status = c.status;
+    a.xmax = qfwd_maxima(c, qp);
+    a.td_sel = (const long long*)c.td_sel; a.td_tgt = c.td_target; a.td_w = c.td_weights; a.td_loss_fn = c.td_loss_fn;
+    a.td_dq = c.td_dq; a.td_out = c.td_out; a.td_loss_part = c.td_loss_part;
 }
 
-// the backward data chain's arguments from the C ABI's (one copy: hexgnn_qnet_backward* and hexgnn_qnet_step_td)
-static void fill_qbwd_args(QBwdArgs& a, const QPlan& qp, int n, int b, int c_in, int hidden, int total_layers, int body_layers,
-                           int mode, int math, const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                           const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                           const float* lin_w, const float* v0_w, const float* v1_w, const float* dq, const float* d_out_v,
-                           float* d_embeds, void* workspace, int* status) {
-    char* ws = (char*)workspace;
-    const char* sv = (const char*)saved;
+// the backward data chain's arguments from the descriptor (one copy: every backward form and the chained step)
+static void fill_qbwd_args(QBwdArgs& a, const hexgnn_qnet_call& c, const QPlan& qp) {
+    char* ws = (char*)c.workspace;
+    const char* sv = (const char*)c.saved;
     const char* hsv = sv + qp.head_saved_off;
-    float* G = (float*)(ws + qp.ws_g_off);
     char* hws = ws + qp.ws_head_off;
-    a.n = n; a.b = b; a.H = hidden; a.L = total_layers; a.mode = mode; a.body_layers = body_layers;
-    a.gptr = gptr; a.rowptr_t = rowptr_t; a.col_t = col_t; a.invdeg = invdeg;
-    a.wpack = (const char*)wpack;
-    for (int l = 0; l < total_layers; ++l) { a.bwd_off[l] = qp.sp.bwd_off[l]; a.bias_off[l] = qp.sp.bias_off[l]; }
-    a.acts = acts; a.lin_w = lin_w; a.v0_w = v0_w; a.v1_w = v1_w;
+    a.n = c.n; a.b = c.b; a.H = c.hidden; a.L = c.total_layers; a.mode = c.mode; a.body_layers = c.body_layers;
+    a.gptr = c.gptr; a.rowptr_t = c.rowptr_t; a.col_t = c.col_t; a.invdeg = c.invdeg;
+    a.wpack = (const char*)c.wpack;
+    for (int l = 0; l < c.total_layers; ++l) { a.bwd_off[l] = qp.sp.bwd_off[l]; a.bias_off[l] = qp.sp.bias_off[l]; }
+    a.acts = c.acts; a.lin_w = c.lin_w; a.v0_w = c.v0_w; a.v1_w = c.v1_w;
     a.adv_raw = (const float*)(hsv + qp.hs.adv_off); a.amax = (const int*)(hsv + qp.hs.amax_off);
     a.amin = (const int*)(hsv + qp.hs.amin_off); a.z = (const float*)(hsv + qp.hs.z_off);
     a.vraw = (const float*)(hsv + qp.hs.v_off);
-    a.dq = dq; a.d_out_v = d_out_v; a.G = G; a.d_embeds = d_embeds;
+    a.dq = c.dq; a.d_out_v = c.d_out_v; a.G = (float*)(ws + qp.ws_g_off); a.d_embeds = c.d_embeds;
     a.dadv = (float*)(hws + qp.hw.dadv_off); a.dz = (float*)(hws + qp.hw.dz_off);
     a.dvr = (float*)(hws + qp.hw.dvr_off); a.lin_part = (float*)(hws + qp.hw.part_off);
-    a.status = status;
-    a.x = x; a.x_stride = x_stride; a.c_in = c_in;
+    a.status = c.status;
+    a.x = c.x; a.x_stride = c.x_stride; a.c_in = c.c_in;
     a.agg0 = (const float*)(sv + qp.sp.agg_off[0]);
     a.first_part = (float*)(ws + qp.ws_first_off);
     // max |G_l| per layer (math 1): lives behind the forward's saved tensors, zeroed by the forward; a backward pass
     // repeated on the same saved state only re-maxes identical values
-    a.gmax = math == 1 ? (unsigned*)(const_cast<char*>(sv) + qp.xmax_off) + kMaxLayers : nullptr;
+    a.gmax = c.math == 1 ? (unsigned*)(const_cast<char*>(sv) + qp.xmax_off) + kMaxLayers : nullptr;
 }
 
-extern "C" {
-
-int hexgnn_qnet_supported(int c_in, int hidden, int max_nodes_per_graph) {
-    const int hp = padded_width(hidden);
-    return hp > 0 && hp <= 112 && hidden >= 2 && c_in >= 1 && c_in <= kSmallCin && c_in != hidden &&
-           max_nodes_per_graph <= kRows;
+// what the TD tail (td_sel set) wants besides td_sel: its buffers, a known loss, mode 0 with a backward to come
+static bool td_tail_ok(const hexgnn_qnet_call& c) {
+    return c.td_target && c.td_dq && c.td_out && c.td_loss_part && c.td_loss_fn >= 0 && c.td_loss_fn <= 1 && c.mode == 0 &&
+           c.need_backward;
 }
 
-int hexgnn_qnet_csr_capacity(int hidden) {
-    const int hp = padded_width(hidden);
-    if (hp <= 0 || hp > 112 || hidden < 2) return HEXGNN_EUNSUPPORTED;
-    HEXGNN_NT_SWITCH7(hp / 16, return QLds<NT_>::col_cap);
-    return HEXGNN_EUNSUPPORTED;
-}
-
-size_t hexgnn_qnet_saved_bytes(int n, int b, int c_in, int hidden, int total_layers) {
-    QPlan q;
-    if (n < 0 || b < 0 || make_qplan(n, b, c_in, hidden, total_layers, &q) != HEXGNN_OK) return 0;
-    return q.saved_total;
-}
-
-static int qnet_forward_impl(int n, int b, int c_in, int hidden, int total_layers, int mode, const int* gptr,
-                             const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
-                             const float* const* wl, const float* const* bl, const float* const* wr,
-                             const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b,
-                             const float* v1_w, const float* v1_b, void* wpack, float* acts, void* saved,
-                             int need_backward, int acts_layer, int math, float* q, float* out_v, int* status,
-                             const int64_t* td_sel, const float* td_target, const float* td_weights, int td_loss_fn,
-                             float* td_dq, float* td_out, float* td_loss_part, hexgnn_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    if (n < 0 || b < 0 || mode < 0 || mode > 2 || math < 0 || math > 1) return HEXGNN_EINVAL;
+static int qnet_forward_impl(const hexgnn_qnet_call& c, hipStream_t st) {
+    if (c.td_sel && !td_tail_ok(c)) return HEXGNN_EINVAL;
+    if (c.n < 0 || c.b < 0 || c.mode < 0 || c.mode > 2 || c.math < 0 || c.math > 1) return HEXGNN_EINVAL;
     QPlan qp;
-    int rc = make_qplan(n, b, c_in, hidden, total_layers, &qp);
+    int rc = make_qplan(c.n, c.b, c.c_in, c.hidden, c.total_layers, &qp);
     if (rc != HEXGNN_OK) return rc;
     // (wl = bl = wr = NULL: the weights were packed by hexgnn_csr_build_grouped_pack of this forward; exact fp32 only)
-    const bool packed = !wl && !bl && !wr && math == 0;
-    if (!gptr || (!packed && (!wl || !bl || !wr)) || !lin_w || !lin_b || !wpack || !saved || !status) return HEXGNN_EINVAL;
-    if (mode != 2 && (!v0_w || !v0_b || !v1_w || !v1_b)) return HEXGNN_EINVAL;
-    if (mode == 1 && !out_v) return HEXGNN_EINVAL;
-    if (n > 0 && (!rowptr || !col || !invdeg || !x || !acts || !q)) return HEXGNN_EINVAL;
-    if (x_stride < c_in) return HEXGNN_EINVAL;
-    // math 1 + backward: the pack's scale kernel also zeroes the per-layer maxima (xmax | gmax) kept behind the saved tensors
-    unsigned* maxima = (math == 1 && need_backward) ? (unsigned*)((char*)saved + qp.xmax_off) : nullptr;
-    rc = launch_pack(qp.sp, c_in, hidden, wl, bl, wr, wpack, st, math, maxima);
+    const bool packed = !c.wl && !c.bl && !c.wr && c.math == 0;
+    if (!c.gptr || (!packed && (!c.wl || !c.bl || !c.wr)) || !c.lin_w || !c.lin_b || !c.wpack || !c.saved || !c.status)
+        return HEXGNN_EINVAL;
+    if (c.mode != 2 && (!c.v0_w || !c.v0_b || !c.v1_w || !c.v1_b)) return HEXGNN_EINVAL;
+    if (c.mode == 1 && !c.out_v) return HEXGNN_EINVAL;
+    if (c.n > 0 && (!c.rowptr || !c.col || !c.invdeg || !c.x || !c.acts || !c.q)) return HEXGNN_EINVAL;
+    if (c.x_stride < c.c_in) return HEXGNN_EINVAL;
+    rc = launch_pack(qp.sp, c.c_in, c.hidden, c.wl, c.bl, c.wr, c.wpack, st, c.math, qfwd_maxima(c, qp));
     if (rc != HEXGNN_OK) return rc;
-    if (b == 0) return check_launch();
+    if (c.b == 0) return check_launch();
     QFwdArgs a;
-    fill_qfwd_args(a, qp, n, b, c_in, hidden, total_layers, mode, gptr, rowptr, col, invdeg, x, x_stride, lin_w, lin_b, v0_w, v0_b,
-                   v1_w, v1_b, wpack, acts, saved, need_backward, acts_layer, maxima, q, out_v, status, td_sel, td_target,
-                   td_weights, td_loss_fn, td_dq, td_out, td_loss_part);
+    fill_qfwd_args(a, c, qp);
     {
         KernelTimer kt(HEXGNN_K_QNET_FWD, st);
-        rc = launch_qfwd_math(qp.sp.nt, math, a, st);
+        rc = launch_qfwd_math(qp.sp.nt, c.math, a, st);
         if (rc != HEXGNN_OK) return rc;
     }
     return check_launch();
 }
 
-int hexgnn_qnet_forward(int n, int b, int c_in, int hidden, int total_layers, int mode, const int* gptr,
-                        const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
-                        const float* const* wl, const float* const* bl, const float* const* wr,
-                        const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b,
-                        const float* v1_w, const float* v1_b, void* wpack, float* acts, void* saved,
-                        int need_backward, int acts_layer, int math, float* q, float* out_v, int* status,
-                        hexgnn_stream_t stream_) {
-    return qnet_forward_impl(n, b, c_in, hidden, total_layers, mode, gptr, rowptr, col, invdeg, x, x_stride, wl, bl, wr, lin_w,
-                             lin_b, v0_w, v0_b, v1_w, v1_b, wpack, acts, saved, need_backward, acts_layer, math, q, out_v,
-                             status, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, stream_);
-}
-
-int hexgnn_qnet_forward_td(int n, int b, int c_in, int hidden, int total_layers, const int* gptr,
-                           const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
-                           const float* const* wl, const float* const* bl, const float* const* wr,
-                           const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b,
-                           const float* v1_w, const float* v1_b, void* wpack, float* acts, void* saved,
-                           int math, float* q, int* status, const int64_t* sel, const float* target,
-                           const float* weights, int loss_fn, float* dq, float* td, float* loss_part,
-                           hexgnn_stream_t stream_) {
-    if (!sel || !target || !dq || !td || !loss_part || loss_fn < 0 || loss_fn > 1) return HEXGNN_EINVAL;
-    return qnet_forward_impl(n, b, c_in, hidden, total_layers, 0, gptr, rowptr, col, invdeg, x, x_stride, wl, bl, wr, lin_w,
-                             lin_b, v0_w, v0_b, v1_w, v1_b, wpack, acts, saved, 1, -1, math, q, nullptr, status, sel, target,
-                             weights, loss_fn, dq, td, loss_part, stream_);
-}
-
-size_t hexgnn_qnet_backward_workspace_bytes(int n, int b, int c_in, int hidden, int total_layers) {
-    QPlan q;
-    if (n < 0 || b < 0 || make_qplan(n, b, c_in, hidden, total_layers, &q) != HEXGNN_OK) return 0;
-    return q.ws_total;
-}
-
-int hexgnn_qnet_step_td(int n, int b, int c_in, int hidden, int total_layers, int body_layers, const int* gptr,
-                        const int* rowptr, const int* col, const int* rowptr_t, const int* col_t, const float* invdeg,
-                        const float* x, int x_stride, const float* const* wl, const float* const* bl, const float* const* wr,
-                        const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b, const float* v1_w,
-                        const float* v1_b, void* wpack, float* acts, void* saved, float* q, int* status, const int64_t* sel,
-                        const float* target, const float* weights, int loss_fn, float* dq, float* td, float* loss_part,
-                        float* d_embeds, void* workspace, size_t workspace_bytes, hexgnn_stream_t stream_) {
-    hipStream_t st = (hipStream_t)stream_;
-    if (n <= 0 || b <= 0 || body_layers < 1 || body_layers > total_layers) return HEXGNN_EINVAL;
-    if (!sel || !target || !dq || !td || !loss_part || loss_fn < 0 || loss_fn > 1) return HEXGNN_EINVAL;
+// forward, TD tail and the backward's data chain (on the tail's own td_dq) in one launch
+static int qnet_step_impl(const hexgnn_qnet_call& c, hipStream_t st) {
+    if (c.n <= 0 || c.b <= 0 || c.body_layers < 1 || c.body_layers > c.total_layers) return HEXGNN_EINVAL;
+    if (!c.td_sel || !td_tail_ok(c) || c.math != 0) return HEXGNN_EINVAL;
     QPlan qp;
-    int rc = make_qplan(n, b, c_in, hidden, total_layers, &qp);
+    int rc = make_qplan(c.n, c.b, c.c_in, c.hidden, c.total_layers, &qp);
     if (rc != HEXGNN_OK) return rc;
-    if (!workspace || workspace_bytes < qp.ws_total) return HEXGNN_EWORKSPACE;
-    const bool packed = !wl && !bl && !wr;      // (packed by hexgnn_csr_build_grouped_pack of this step)
-    if (!gptr || (!packed && (!wl || !bl || !wr)) || !lin_w || !lin_b || !v0_w || !v0_b || !v1_w || !v1_b || !wpack || !saved ||
-        !status || !rowptr || !col || !rowptr_t || !col_t || !invdeg || !x || !acts || !q || x_stride < c_in)
+    if (!c.workspace || c.workspace_bytes < qp.ws_total) return HEXGNN_EWORKSPACE;
+    const bool packed = !c.wl && !c.bl && !c.wr;      // (packed by hexgnn_csr_build_grouped_pack of this step)
+    if (!c.gptr || (!packed && (!c.wl || !c.bl || !c.wr)) || !c.lin_w || !c.lin_b || !c.v0_w || !c.v0_b || !c.v1_w || !c.v1_b ||
+        !c.wpack || !c.saved || !c.status || !c.rowptr || !c.col || !c.rowptr_t || !c.col_t || !c.invdeg || !c.x || !c.acts ||
+        !c.q || c.x_stride < c.c_in)
         return HEXGNN_EINVAL;
-    rc = launch_pack(qp.sp, c_in, hidden, wl, bl, wr, wpack, st, 0, nullptr);
+    rc = launch_pack(qp.sp, c.c_in, c.hidden, c.wl, c.bl, c.wr, c.wpack, st, 0, nullptr);
     if (rc != HEXGNN_OK) return rc;
     QStepArgs a;
-    fill_qfwd_args(a.f, qp, n, b, c_in, hidden, total_layers, 0, gptr, rowptr, col, invdeg, x, x_stride, lin_w, lin_b, v0_w, v0_b,
-                   v1_w, v1_b, wpack, acts, saved, 1, -1, nullptr, q, nullptr, status, sel, target, weights, loss_fn, dq, td,
-                   loss_part);
-    fill_qbwd_args(a.b, qp, n, b, c_in, hidden, total_layers, body_layers, 0, 0, gptr, rowptr_t, col_t, invdeg, x, x_stride, acts,
-                   saved, wpack, lin_w, v0_w, v1_w, dq, nullptr, d_embeds, workspace, status);
+    fill_qfwd_args(a.f, c, qp);
+    fill_qbwd_args(a.b, c, qp);
+    a.b.dq = c.td_dq;
     if (g_prof_class >= 0) {
         // a profile class is being timed: the two launches, so that the per-kernel figures keep their meaning
         {
@@ -362,17 +281,33 @@ int hexgnn_qnet_step_td(int n, int b, int c_in, int hidden, int total_layers, in
     return check_launch();
 }
 
-static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int mode, int math,
-                                const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                                const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                                const float* lin_w, const float* v0_w, const float* v1_w, const float* dq,
-                                const float* d_out_v, float* d_embeds, float* const* d_wl, float* const* d_bl,
-                                float* const* d_wr, float* d_lin_w, float* d_lin_b, float* d_v0_w, float* d_v0_b,
-                                float* d_v1_w, float* d_v1_b, void* workspace, size_t workspace_bytes, int* status,
-                                int stages, int layer_lo, int layer_hi, const float* loss_part, float* loss,
-                                hexgnn_stream_t stream_, const int* n_live = nullptr) {
-    hipStream_t st = (hipStream_t)stream_;
-    if (n < 0 || b < 0 || mode < 0 || mode > 2 || math < 0 || math > 1 || body_layers < 1 || body_layers > total_layers)
+// Gradient destinations per layer, and the head tail's in the order (lin_w, lin_b, v0_w, v0_b, v1_w, v1_b).  QGradArrays: how
+// the positional entry points name them (HOST pointer arrays); the descriptor names them as flat + offsets.
+struct QGrads { float* wl[kMaxLayers]; float* bl[kMaxLayers]; float* wr[kMaxLayers]; float* tail[6]; };
+struct QGradArrays { float* const* d_wl; float* const* d_bl; float* const* d_wr; float* tail[6]; };
+
+// the one place where either form becomes per-layer pointers (total_layers is in 1 .. kMaxLayers: make_qplan has passed)
+static int resolve_grads(const hexgnn_qnet_call& c, const QGradArrays* arr, QGrads& g) {
+    const int L = c.total_layers;
+    if (arr) {
+        if (!arr->d_wl || !arr->d_bl || !arr->d_wr) return HEXGNN_EINVAL;
+        for (int l = 0; l < L; ++l) { g.wl[l] = arr->d_wl[l]; g.bl[l] = arr->d_bl[l]; g.wr[l] = arr->d_wr[l]; }
+        for (int k = 0; k < 6; ++k) g.tail[k] = arr->tail[k];
+    } else {      // (flat and offsets: checked by hexgnn_qnet_call_backward)
+        for (int l = 0; l < L; ++l) {
+            g.wl[l] = c.flat + c.offsets[3 * l]; g.bl[l] = c.flat + c.offsets[3 * l + 1]; g.wr[l] = c.flat + c.offsets[3 * l + 2];
+        }
+        const int64_t* t = c.offsets + 3 * L;
+        for (int k = 0; k < 6; ++k) g.tail[k] = (k < 2 || c.mode != 2) ? c.flat + t[k] : nullptr;      // (mode 2: no value head)
+    }
+    for (int l = 0; l < L; ++l) if (!g.wl[l] || !g.bl[l] || !g.wr[l]) return HEXGNN_EINVAL;
+    return HEXGNN_OK;
+}
+
+static int qnet_backward_staged_impl(const hexgnn_qnet_call& c, const QGradArrays* arr, int stages, int layer_lo, int layer_hi,
+                                     hipStream_t st) {
+    const int n = c.n, b = c.b, c_in = c.c_in, hidden = c.hidden, total_layers = c.total_layers, mode = c.mode, math = c.math;
+    if (n < 0 || b < 0 || mode < 0 || mode > 2 || math < 0 || math > 1 || c.body_layers < 1 || c.body_layers > total_layers)
         return HEXGNN_EINVAL;
     if (stages <= 0 || (stages & ~(HEXGNN_QBWD_DATA | HEXGNN_QBWD_SMALL | HEXGNN_QBWD_HIDDEN))) return HEXGNN_EINVAL;
     if ((stages & HEXGNN_QBWD_HIDDEN) && (layer_lo < 1 || layer_hi < layer_lo || layer_hi > total_layers)) return HEXGNN_EINVAL;
@@ -380,21 +315,22 @@ static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int tot
     QPlan qp;
     int rc = make_qplan(n, b, c_in, hidden, total_layers, &qp);
     if (rc != HEXGNN_OK) return rc;
-    if (!workspace || workspace_bytes < qp.ws_total) return HEXGNN_EWORKSPACE;
-    if (!gptr || !d_wl || !d_bl || !d_wr || !wpack || !saved || !lin_w || !d_lin_w || !d_lin_b || !status)
-        return HEXGNN_EINVAL;
-    for (int l = 0; l < total_layers; ++l) if (!d_wl[l] || !d_bl[l] || !d_wr[l]) return HEXGNN_EINVAL;
-    if (mode != 2 && (!v0_w || !v1_w || !d_v0_w || !d_v0_b || !d_v1_w || !d_v1_b)) return HEXGNN_EINVAL;
-    if (mode == 1 && !d_out_v) return HEXGNN_EINVAL;
-    if (n > 0 && (!rowptr_t || !col_t || !invdeg || !x || !acts || !dq)) return HEXGNN_EINVAL;
-    const char* sv = (const char*)saved;
+    if (!c.workspace || c.workspace_bytes < qp.ws_total) return HEXGNN_EWORKSPACE;
+    QGrads g;
+    rc = resolve_grads(c, arr, g);
+    if (rc != HEXGNN_OK) return rc;
+    float* const* d_wl = g.wl; float* const* d_bl = g.bl; float* const* d_wr = g.wr;
+    float *d_lin_w = g.tail[0], *d_lin_b = g.tail[1], *d_v0_w = g.tail[2], *d_v0_b = g.tail[3], *d_v1_w = g.tail[4], *d_v1_b = g.tail[5];
+    if (!c.gptr || !c.wpack || !c.saved || !c.lin_w || !d_lin_w || !d_lin_b || !c.status) return HEXGNN_EINVAL;
+    if (mode != 2 && (!c.v0_w || !c.v1_w || !d_v0_w || !d_v0_b || !d_v1_w || !d_v1_b)) return HEXGNN_EINVAL;
+    if (mode == 1 && !c.d_out_v) return HEXGNN_EINVAL;
+    if (n > 0 && (!c.rowptr_t || !c.col_t || !c.invdeg || !c.x || !c.acts || !c.dq)) return HEXGNN_EINVAL;
+    const char* sv = (const char*)c.saved;
     const char* hsv = sv + qp.head_saved_off;
-    float* G = (float*)((char*)workspace + qp.ws_g_off);
-    float* part = (float*)((char*)workspace + qp.ws_part_off);
-    float* part0 = (float*)((char*)workspace + qp.ws_part0_off);
+    float* part = (float*)((char*)c.workspace + qp.ws_part_off);
+    float* part0 = (float*)((char*)c.workspace + qp.ws_part0_off);
     QBwdArgs a;
-    fill_qbwd_args(a, qp, n, b, c_in, hidden, total_layers, body_layers, mode, math, gptr, rowptr_t, col_t, invdeg, x, x_stride,
-                   acts, saved, wpack, lin_w, v0_w, v1_w, dq, d_out_v, d_embeds, workspace, status);
+    fill_qbwd_args(a, c, qp);
     if (b > 0 && n > 0) {
         if (st_data) {
             KernelTimer kt(HEXGNN_K_QNET_BWD, st);
@@ -420,9 +356,9 @@ static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int tot
         const size_t slab_sz = (size_t)qp.sp.hp * (2 * qp.sp.hp + 1);
         float* spart = part + (size_t)(lo - 1) * kDwMaxSlices * slab_sz;
         if (nh > 0) {
-            rc = launch_weight_grads(n, c_in, hidden, qp.sp, qp.bp, x, x_stride, acts, sv, G, d_wl, d_bl, d_wr, spart,
+            rc = launch_weight_grads(n, c_in, hidden, qp.sp, qp.bp, c.x, c.x_stride, c.acts, sv, a.G, d_wl, d_bl, d_wr, spart,
                                      part0, st, math, (const unsigned*)(sv + qp.xmax_off), a.gmax,
-                                     /*hidden_only_no_reduce=*/true, lo, hi, n_live);
+                                     /*hidden_only_no_reduce=*/true, lo, hi, c.n_live);
             if (rc != HEXGNN_OK) return rc;
         }
         GradReduceArgs r;
@@ -445,8 +381,8 @@ static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int tot
         r.n2 = st_small ? (hidden + 1 + 3) / 4 : 0;
         r.nbx3 = (4 * hidden + 15) / 16;
         r.n3 = (st_small && mode != 2 && hidden / 2 > 0) ? r.nbx3 * (hidden / 2) : 0;
-        r.loss_part = loss_part; r.loss = loss;
-        const int n4 = (st_small && loss_part && loss) ? 1 : 0;      // (the block behind the last role: the TD loss's mean)
+        r.loss_part = c.td_loss ? c.td_loss_part : nullptr; r.loss = c.td_loss;
+        const int n4 = (st_small && r.loss_part && r.loss) ? 1 : 0;      // (the block behind the last role: the TD loss's mean)
         if (r.n0 + r.n1 + r.n2 + r.n3 + n4 > 0) qnet_grad_reduce_kernel<<<r.n0 + r.n1 + r.n2 + r.n3 + n4, 256, 0, st>>>(r);
     } else if (st_small) {
         launch_head_param_grads(b, hidden, mode, a.dz, a.dvr, (const float*)(hsv + qp.hs.pooled_off),
@@ -454,6 +390,69 @@ static int qnet_backward_staged_impl(int n, int b, int c_in, int hidden, int tot
                                 d_v1_b, st);
     }
     return check_launch();
+}
+
+extern "C" {
+
+int hexgnn_qnet_supported(int c_in, int hidden, int max_nodes_per_graph) {
+    const int hp = padded_width(hidden);
+    return hp > 0 && hp <= 112 && hidden >= 2 && c_in >= 1 && c_in <= kSmallCin && c_in != hidden &&
+           max_nodes_per_graph <= kRows;
+}
+
+int hexgnn_qnet_csr_capacity(int hidden) {
+    const int hp = padded_width(hidden);
+    if (hp <= 0 || hp > 112 || hidden < 2) return HEXGNN_EUNSUPPORTED;
+    HEXGNN_NT_SWITCH7(hp / 16, return QLds<NT_>::col_cap);
+    return HEXGNN_EUNSUPPORTED;
+}
+
+size_t hexgnn_qnet_saved_bytes(int n, int b, int c_in, int hidden, int total_layers) {
+    QPlan q;
+    if (n < 0 || b < 0 || make_qplan(n, b, c_in, hidden, total_layers, &q) != HEXGNN_OK) return 0;
+    return q.saved_total;
+}
+
+size_t hexgnn_qnet_backward_workspace_bytes(int n, int b, int c_in, int hidden, int total_layers) {
+    QPlan q;
+    if (n < 0 || b < 0 || make_qplan(n, b, c_in, hidden, total_layers, &q) != HEXGNN_OK) return 0;
+    return q.ws_total;
+}
+
+int hexgnn_qnet_call_forward(const hexgnn_qnet_call* c, int chain_backward, hexgnn_stream_t stream_) {
+    if (!c || c->struct_bytes != sizeof(hexgnn_qnet_call)) return HEXGNN_EINVAL;
+    return chain_backward ? qnet_step_impl(*c, (hipStream_t)stream_) : qnet_forward_impl(*c, (hipStream_t)stream_);
+}
+
+int hexgnn_qnet_call_backward(const hexgnn_qnet_call* c, int stages, int layer_lo, int layer_hi, hexgnn_stream_t stream_) {
+    if (!c || c->struct_bytes != sizeof(hexgnn_qnet_call)) return HEXGNN_EINVAL;
+    if (!c->flat || !c->offsets || c->total_layers < 1 || c->total_layers > kMaxLayers) return HEXGNN_EINVAL;
+    if (c->td_loss && (!c->td_loss_part || c->mode != 0)) return HEXGNN_EINVAL;
+    if (c->n_live) {
+        if (!c->td_loss || c->math < 0 || c->math > 1) return HEXGNN_EINVAL;
+        if (c->math == 1) return HEXGNN_EUNSUPPORTED;      // (the split-f16 GEMM walks rows by the host's count)
+    }
+    return qnet_backward_staged_impl(*c, nullptr, stages, layer_lo, layer_hi, (hipStream_t)stream_);
+}
+
+// ---- the positional forms: adapters that fill a descriptor ----
+int hexgnn_qnet_forward(int n, int b, int c_in, int hidden, int total_layers, int mode, const int* gptr,
+                        const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
+                        const float* const* wl, const float* const* bl, const float* const* wr,
+                        const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b,
+                        const float* v1_w, const float* v1_b, void* wpack, float* acts, void* saved,
+                        int need_backward, int acts_layer, int math, float* q, float* out_v, int* status,
+                        hexgnn_stream_t stream_) {
+    hexgnn_qnet_call c = {};
+    c.struct_bytes = sizeof c;
+    c.n = n; c.b = b; c.c_in = c_in; c.hidden = hidden; c.total_layers = total_layers; c.mode = mode; c.math = math;
+    c.x_stride = x_stride; c.need_backward = need_backward; c.acts_layer = acts_layer;
+    c.gptr = gptr; c.rowptr = rowptr; c.col = col; c.invdeg = invdeg; c.x = x;
+    c.wl = wl; c.bl = bl; c.wr = wr;
+    c.lin_w = lin_w; c.lin_b = lin_b; c.v0_w = v0_w; c.v0_b = v0_b; c.v1_w = v1_w; c.v1_b = v1_b;
+    c.wpack = wpack; c.acts = acts; c.saved = saved;
+    c.q = q; c.out_v = out_v; c.status = status;
+    return qnet_forward_impl(c, (hipStream_t)stream_);
 }
 
 int hexgnn_qnet_backward_staged(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int mode, int math,
@@ -464,10 +463,17 @@ int hexgnn_qnet_backward_staged(int n, int b, int c_in, int hidden, int total_la
                                 float* const* d_wr, float* d_lin_w, float* d_lin_b, float* d_v0_w, float* d_v0_b,
                                 float* d_v1_w, float* d_v1_b, void* workspace, size_t workspace_bytes, int* status,
                                 int stages, int layer_lo, int layer_hi, hexgnn_stream_t stream_) {
-    return qnet_backward_staged_impl(n, b, c_in, hidden, total_layers, body_layers, mode, math, gptr, rowptr_t, col_t, invdeg,
-                                     x, x_stride, acts, saved, wpack, lin_w, v0_w, v1_w, dq, d_out_v, d_embeds, d_wl, d_bl,
-                                     d_wr, d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b, workspace, workspace_bytes,
-                                     status, stages, layer_lo, layer_hi, nullptr, nullptr, stream_);
+    hexgnn_qnet_call c = {};
+    c.struct_bytes = sizeof c;
+    c.n = n; c.b = b; c.c_in = c_in; c.hidden = hidden; c.total_layers = total_layers; c.body_layers = body_layers;
+    c.mode = mode; c.math = math; c.x_stride = x_stride;
+    c.gptr = gptr; c.rowptr_t = rowptr_t; c.col_t = col_t; c.invdeg = invdeg; c.x = x;
+    c.lin_w = lin_w; c.v0_w = v0_w; c.v1_w = v1_w;
+    c.wpack = const_cast<void*>(wpack); c.acts = const_cast<float*>(acts); c.saved = const_cast<void*>(saved);
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.status = status;
+    c.dq = dq; c.d_out_v = d_out_v; c.d_embeds = d_embeds;
+    const QGradArrays arr = {d_wl, d_bl, d_wr, {d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b}};
+    return qnet_backward_staged_impl(c, &arr, stages, layer_lo, layer_hi, (hipStream_t)stream_);
 }
 
 int hexgnn_qnet_backward(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int mode, int math,
@@ -483,70 +489,6 @@ int hexgnn_qnet_backward(int n, int b, int c_in, int hidden, int total_layers, i
                                        d_wl, d_bl, d_wr, d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b, workspace,
                                        workspace_bytes, status, HEXGNN_QBWD_DATA | HEXGNN_QBWD_SMALL | HEXGNN_QBWD_HIDDEN,
                                        1, total_layers, stream_);
-}
-
-int hexgnn_qnet_backward_flat(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int mode, int math,
-                              const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                              const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                              const float* lin_w, const float* v0_w, const float* v1_w, const float* dq,
-                              const float* d_out_v, float* d_embeds, float* flat, const int64_t* offsets,
-                              void* workspace, size_t workspace_bytes, int* status, int stages, int layer_lo,
-                              int layer_hi, hexgnn_stream_t stream_) {
-    if (!flat || !offsets || total_layers < 1 || total_layers > kMaxLayers) return HEXGNN_EINVAL;
-    float* d_wl[kMaxLayers]; float* d_bl[kMaxLayers]; float* d_wr[kMaxLayers];
-    for (int l = 0; l < total_layers; ++l) {
-        d_wl[l] = flat + offsets[3 * l]; d_bl[l] = flat + offsets[3 * l + 1]; d_wr[l] = flat + offsets[3 * l + 2];
-    }
-    const int64_t* t = offsets + 3 * total_layers;      // lin_w, lin_b, v0_w, v0_b, v1_w, v1_b
-    const bool vh = mode != 2;
-    return hexgnn_qnet_backward_staged(n, b, c_in, hidden, total_layers, body_layers, mode, math, gptr, rowptr_t, col_t,
-                                       invdeg, x, x_stride, acts, saved, wpack, lin_w, v0_w, v1_w, dq, d_out_v, d_embeds,
-                                       d_wl, d_bl, d_wr, flat + t[0], flat + t[1], vh ? flat + t[2] : nullptr,
-                                       vh ? flat + t[3] : nullptr, vh ? flat + t[4] : nullptr, vh ? flat + t[5] : nullptr,
-                                       workspace, workspace_bytes, status, stages, layer_lo, layer_hi, stream_);
-}
-
-int hexgnn_qnet_backward_flat_td(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int math,
-                                 const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                                 const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                                 const float* lin_w, const float* v0_w, const float* v1_w, const float* dq,
-                                 float* d_embeds, float* flat, const int64_t* offsets, void* workspace,
-                                 size_t workspace_bytes, int* status, int stages, int layer_lo, int layer_hi,
-                                 const float* loss_part, float* loss, hexgnn_stream_t stream_) {
-    if (!flat || !offsets || total_layers < 1 || total_layers > kMaxLayers || !loss_part || !loss) return HEXGNN_EINVAL;
-    float* d_wl[kMaxLayers]; float* d_bl[kMaxLayers]; float* d_wr[kMaxLayers];
-    for (int l = 0; l < total_layers; ++l) {
-        d_wl[l] = flat + offsets[3 * l]; d_bl[l] = flat + offsets[3 * l + 1]; d_wr[l] = flat + offsets[3 * l + 2];
-    }
-    const int64_t* t = offsets + 3 * total_layers;      // lin_w, lin_b, v0_w, v0_b, v1_w, v1_b
-    return qnet_backward_staged_impl(n, b, c_in, hidden, total_layers, body_layers, 0, math, gptr, rowptr_t, col_t, invdeg, x,
-                                     x_stride, acts, saved, wpack, lin_w, v0_w, v1_w, dq, nullptr, d_embeds, d_wl, d_bl,
-                                     d_wr, flat + t[0], flat + t[1], flat + t[2], flat + t[3], flat + t[4], flat + t[5],
-                                     workspace, workspace_bytes, status, stages, layer_lo, layer_hi, loss_part, loss,
-                                     stream_);
-}
-
-int hexgnn_qnet_backward_flat_td_live(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int math,
-                                      const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                                      const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                                      const float* lin_w, const float* v0_w, const float* v1_w, const float* dq,
-                                      float* d_embeds, float* flat, const int64_t* offsets, void* workspace,
-                                      size_t workspace_bytes, int* status, int stages, int layer_lo, int layer_hi,
-                                      const float* loss_part, float* loss, const int* n_live, hexgnn_stream_t stream_) {
-    if (!flat || !offsets || total_layers < 1 || total_layers > kMaxLayers || !loss_part || !loss || !n_live || math < 0 ||
-        math > 1)
-        return HEXGNN_EINVAL;
-    if (math == 1) return HEXGNN_EUNSUPPORTED;      // (the split-f16 GEMM walks rows by the host's count)
-    float* d_wl[kMaxLayers]; float* d_bl[kMaxLayers]; float* d_wr[kMaxLayers];
-    for (int l = 0; l < total_layers; ++l) {
-        d_wl[l] = flat + offsets[3 * l]; d_bl[l] = flat + offsets[3 * l + 1]; d_wr[l] = flat + offsets[3 * l + 2];
-    }
-    const int64_t* t = offsets + 3 * total_layers;      // lin_w, lin_b, v0_w, v0_b, v1_w, v1_b
-    return qnet_backward_staged_impl(n, b, c_in, hidden, total_layers, body_layers, 0, math, gptr, rowptr_t, col_t, invdeg, x,
-                                     x_stride, acts, saved, wpack, lin_w, v0_w, v1_w, dq, nullptr, d_embeds, d_wl, d_bl,
-                                     d_wr, flat + t[0], flat + t[1], flat + t[2], flat + t[3], flat + t[4], flat + t[5],
-                                     workspace, workspace_bytes, status, stages, layer_lo, layer_hi, loss_part, loss,
-                                     stream_, n_live);
 }
 
 #ifdef HEXGNN_STAMPS

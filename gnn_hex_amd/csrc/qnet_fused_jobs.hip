@@ -6,18 +6,6 @@
 
 namespace hexgnn {
 
-#define HEXGNN_NT_SWITCH7J(nt, CALL)                    \
-    switch (nt) {                                      \
-        case 1: { constexpr int NT_ = 1; CALL; } break; \
-        case 2: { constexpr int NT_ = 2; CALL; } break; \
-        case 3: { constexpr int NT_ = 3; CALL; } break; \
-        case 4: { constexpr int NT_ = 4; CALL; } break; \
-        case 5: { constexpr int NT_ = 5; CALL; } break; \
-        case 6: { constexpr int NT_ = 6; CALL; } break; \
-        case 7: { constexpr int NT_ = 7; CALL; } break; \
-        default: return HEXGNN_EUNSUPPORTED;           \
-    }
-
 template <int NT>
 static int launch_qfwd_jobs_m(int njobs, const QFwdJobArgs& a, hipStream_t st) {
     static bool once = [] {
@@ -30,7 +18,7 @@ static int launch_qfwd_jobs_m(int njobs, const QFwdJobArgs& a, hipStream_t st) {
     return HEXGNN_OK;
 }
 int launch_qfwd_jobs(int nt, int njobs, const QFwdJobArgs& a, hipStream_t st) {
-    HEXGNN_NT_SWITCH7J(nt, (launch_qfwd_jobs_m<NT_>(njobs, a, st)));
+    HEXGNN_NT_SWITCH7(nt, (launch_qfwd_jobs_m<NT_>(njobs, a, st)));
     return HEXGNN_OK;
 }
 

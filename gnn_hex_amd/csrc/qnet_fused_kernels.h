@@ -48,7 +48,7 @@ struct QFwdArgs {
     float* q; float* out_v; int* status;
     unsigned* xmax;   // [L] bit patterns of max |[agg|x]| per layer (math 1 + need_backward: feeds the f16 dW scales)
     int acts_layer;   // inference (need_backward == 0): store only this layer's activations (-1: every layer's)
-    // TD loss of the DQN update folded into the tail (mode 0, hexgnn_qnet_forward_td): graph g's selected node td_sel[g] (a
+    // TD loss of the DQN update folded into the tail (mode 0, hexgnn_qnet_call's td_sel): graph g's selected node td_sel[g] (a
     // global row of THAT graph), target and importance weight -> td error, the graph's loss term, d loss / d Q of its rows
     const long long* td_sel; const float* td_tgt; const float* td_w; int td_loss_fn;
     float* td_dq; float* td_out; float* td_loss_part;
@@ -669,6 +669,19 @@ static int launch_qbwd_m(const QBwdArgs& a, hipStream_t st) {
     qnet_bwd_kernel<NT, MATH><<<a.b, 512, QLds<NT>::total, st>>>(a);
     return HEXGNN_OK;
 }
+
+// CALL with NT_ = nt as a constant, for the tile counts the fused kernels are compiled for; returns from the caller otherwise
+#define HEXGNN_NT_SWITCH7(nt, CALL)                     \
+    switch (nt) {                                      \
+        case 1: { constexpr int NT_ = 1; CALL; } break; \
+        case 2: { constexpr int NT_ = 2; CALL; } break; \
+        case 3: { constexpr int NT_ = 3; CALL; } break; \
+        case 4: { constexpr int NT_ = 4; CALL; } break; \
+        case 5: { constexpr int NT_ = 5; CALL; } break; \
+        case 6: { constexpr int NT_ = 6; CALL; } break; \
+        case 7: { constexpr int NT_ = 7; CALL; } break; \
+        default: return HEXGNN_EUNSUPPORTED;           \
+    }
 
 // one translation unit per math mode and one for the job-table form (co-compiled template variants perturb each other's
 // register allocation)

@@ -913,8 +913,9 @@ _ONE_LAUNCH_STEP = True
 
 def set_one_launch_step(enabled: bool) -> None:
     """``td_step``'s fused form as ONE launch for the forward, the TD loss and the backward's data chain
-    (``hexgnn_qnet_step_td``: a workgroup runs its graph's backward chain right behind its forward) instead of two.  Same
-    bits; taken in exact fp32 without ``defer_lower``, a grad-stage hook or ``x._hex_live_rows`` (tests and A/B switch it)."""
+    (``hexgnn_qnet_call_forward`` with ``chain_backward``: a workgroup runs its graph's backward chain right behind its forward)
+    instead of two.  Same bits; taken in exact fp32 without ``defer_lower``, a grad-stage hook or ``x._hex_live_rows`` (tests
+    and A/B switch it)."""
     global _ONE_LAUNCH_STEP
     _ONE_LAUNCH_STEP = bool(enabled)
 
@@ -954,7 +955,7 @@ def qnet_fused_supported(c_in: int, hidden: int, max_nodes: int) -> bool:
 # step (66 AccumulateGrad nodes), which left GNN-S host-bound at 0.8 M graphs/s against 2 M replayed.  The function has ONE
 # differentiable input (a per-model anchor), the forward call uses pointer arrays cached per (model, head) -- re-validated by
 # data_ptr every call, 57 C-level calls -- and the backward writes every gradient into ONE flat buffer
-# (``hexgnn_qnet_backward_flat``: base pointer + cached offset table) and assigns the views to ``p.grad`` itself
+# (``hexgnn_qnet_call_backward``: base pointer + cached offset table) and assigns the views to ``p.grad`` itself
 # (accumulating when a gradient is already there, like AccumulateGrad).  Not usable with ``torch.autograd.grad(loss,
 # parameters)`` or hooks on parameters: the model takes the autograd form (QNetFusedFn: parameters are inputs, the same flat
 # buffer's views are returned) when it finds hooks, frozen or non-leaf parameters, or after ``set_direct_grads(False)``.
@@ -983,8 +984,8 @@ def _free_refcount() -> int:
 
 class QNetParamCache:
     """Per (model, head): the parameter list of the fused call, its cached pointer arrays and the flat gradient layout."""
-    __slots__ = ("params", "ptrs", "wl", "bl", "wr", "tail", "flat_params", "offsets", "total", "direct_ok", "tot",
-                 "sizes", "cut", "grad_ring")
+    __slots__ = ("params", "ptrs", "wl", "bl", "wr", "wlp", "tail", "flat_params", "offsets", "offsets_p", "total", "direct_ok",
+                 "tot", "sizes", "cut", "grad_ring")
 
     def __init__(self, params, tot):
         self.params = params
@@ -1033,6 +1034,7 @@ class QNetParamCache:
         vp = C.c_void_p * tot
         pt = self.ptrs
         self.wl, self.bl, self.wr = vp(*pt[0:3 * tot:3]), vp(*pt[1:3 * tot:3]), vp(*pt[2:3 * tot:3])
+        self.wlp = (C.addressof(self.wl), C.addressof(self.bl), C.addressof(self.wr))      # (what a descriptor holds of them)
         self.tail = tuple(pt[3 * tot:])
         nconv = 3 * tot
         order = list(range(nconv)) + [nconv + 2, nconv + 3, nconv + 4, nconv + 5, nconv + 0, nconv + 1]   # parameters() order
@@ -1042,6 +1044,7 @@ class QNetParamCache:
             o += params[i].numel()
         self.flat_params = [params[i] for i in order]
         self.offsets = (C.c_int64 * len(params))(*offs)
+        self.offsets_p = C.addressof(self.offsets)
         self.total = o
         self.grad_ring = []
         self.cut = offs[3 * (1 + tot // 2)] if tot >= 3 else 0      # flat position where the staged backward splits
@@ -1063,9 +1066,19 @@ class _QNetCall:
     """Everything one fused forward leaves behind for its backward (plain attributes: cheaper than ctx.save_for_backward).
     ``assign``: the direct form (the backward assigns ``p.grad``) rather than the autograd form (it returns the gradients);
     ``nonleaf``: a parameter of the call is computed per forward (no staging, see qnet_backward); ``live``: td_step() over
-    capacity-sized buffers -- the 1-element int32 device tensor that holds the live row count (``x._hex_live_rows``)."""
+    capacity-sized buffers -- the 1-element int32 device tensor that holds the live row count (``x._hex_live_rows``).
+
+    ``desc`` (fused kernels): the call's ``hexgnn_qnet_call``, filled by the forward; the backward sets its backward group.  It
+    holds raw addresses, and these attributes keep what they point at alive for as long as it can be used: ``x``: x; ``gs`` and
+    ``gptr``: the graph arrays and the status word; ``bufs``: acts | wpack | saved; ``cache``: the parameters (``cache.params``);
+    ``keep``: the pointer arrays wl / bl / wr the forward was given (``cache.refresh()`` replaces the cache's own); ``td``: td_dq |
+    td_out | td_loss_part | td_loss; ``live``: n_live; ``step_ws``: workspace and d_embeds of a chained forward until the backward
+    takes them.  td_sel / td_target / td_weights and q / out_v are read and written by the forward launch only, which is
+    enqueued before ``qnet_forward`` returns.  What the backward adds (dq, d_out_v, d_embeds, flat, workspace, ``cache.offsets``)
+    lives through ``qnet_backward``, which issues every launch that reads it -- except a deferred lower half, for which
+    ``pending`` holds flat, the workspace, d_embeds and the offsets table until ``finish_backward``."""
     __slots__ = ("cache", "gs", "gptr", "dims", "x", "bufs", "math", "sink", "gp", "done", "layered", "td", "pending", "versions",
-                 "assign", "nonleaf", "live", "step_ws")
+                 "assign", "nonleaf", "live", "step_ws", "desc", "keep")
 
 
 def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_in: int, hidden: int, body_layers: int,
@@ -1138,36 +1151,37 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
                                          saved + bwd_bytes[0], stream), "hexgnn_head_forward")
     else:
         tda = getattr(_TD_STEP, "args", None) if assign else None
+        # the differences between the three forms, as field values: the TD tail, the chained backward's workspace and d_embeds
+        tdf = (None, None, None, 0, None, None, None)
+        acts_layer, ws_p, demb_p = body_layers - 1, None, None
         if tda is not None and mode == 0 and need_bwd and b > 0 and n > 0 and tda[0].numel() == b:
             # td_step(): the update's loss is formed in the forward kernel's tail (one selected node per graph)
             sel, tgt, w, lfn = tda
             # one buffer: dq [n] | td [b] | loss terms [b] | loss [1]
             tb = torch.empty(n + 2 * b + 1, dtype=torch.float32, device=dev)
             tp = tb.data_ptr()
+            tdf = (sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n, tp + 4 * (n + b))
+            acts_layer = -1
             live = getattr(_TD_STEP, "live", None)
             if _ONE_LAUNCH_STEP and _MATH == 0 and live is None and getattr(_TD_STEP, "whole", False):
                 # the backward's data chain in the same launch: its workspace exists from here on (qnet_backward runs the rest)
                 # (and the gradient of the body's output, which the model's activations hook receives in qnet_backward)
                 step_ws = (torch.empty(bwd_bytes, dtype=torch.uint8, device=dev),
                            torch.empty((n, hp), dtype=torch.float32, device=dev))
-                _lib.check(L.hexgnn_qnet_step_td(
-                    n, b, c_in, hidden, tot, body_layers, gp[5], gp[0], gp[1], gp[2], gp[3], gp[4], x.data_ptr(), x_stride,
-                    wl, bl, wr, t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, q.data_ptr(), gp[6],
-                    sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
-                    tp + 4 * (n + b), step_ws[1].data_ptr(), step_ws[0].data_ptr(), bwd_bytes, stream), "hexgnn_qnet_step_td")
-            else:
-                _lib.check(L.hexgnn_qnet_forward_td(
-                    n, b, c_in, hidden, tot, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
-                    t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, _MATH, q.data_ptr(), gp[6],
-                    sel.data_ptr(), tgt.data_ptr(), w.data_ptr() if w is not None else None, lfn, tp, tp + 4 * n,
-                    tp + 4 * (n + b), stream), "hexgnn_qnet_forward_td")
+                ws_p, demb_p = step_ws[0].data_ptr(), step_ws[1].data_ptr()
             td = (tb, n, b)
-        else:
-            _lib.check(L.hexgnn_qnet_forward(
-                n, b, c_in, hidden, tot, mode, gp[5], gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr,
-                t[0], t[1], t[2], t[3], t[4], t[5], wpack, base, saved, int(need_bwd), body_layers - 1,
-                _MATH, q.data_ptr(), out_v.data_ptr() if out_v is not None else None, gp[6], stream), "hexgnn_qnet_forward")
+        wlp = cache.wlp if wl is not None else (None, None, None)
+        desc = _lib.QNetCall(
+            _lib.QNET_CALL_BYTES, n, b, c_in, hidden, tot, body_layers, mode, _MATH, x_stride, int(need_bwd), acts_layer,
+            gp[5], gp[0], gp[1], gp[2], gp[3], gp[4], x.data_ptr(),
+            wlp[0], wlp[1], wlp[2], t[0], t[1], t[2], t[3], t[4], t[5],
+            wpack, base, saved, ws_p, bwd_bytes,
+            q.data_ptr(), out_v.data_ptr() if out_v is not None else None, gp[6],
+            tdf[0], tdf[1], tdf[2], tdf[3], tdf[4], tdf[5], tdf[6], None,
+            None, None, demb_p, None, None, None)
+        _lib.check(L.hexgnn_qnet_call_forward(desc, int(step_ws is not None), stream), "hexgnn_qnet_call_forward")
     call = _QNetCall()
+    call.desc, call.keep = (None, None) if layered else (desc, (wl, bl, wr))
     call.cache, call.gs, call.gptr, call.x = cache, gs, gptr, x
     # (bwd_bytes: the fused backward's workspace bytes; layered: (stack saved, stack workspace, head workspace) bytes)
     call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, bwd_bytes)
@@ -1274,7 +1288,7 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
     else:
         ws_bytes = bwd_bytes
         td = call.td
-        # hexgnn_qnet_step_td ran the data chain with the forward: the remaining stages work on its workspace
+        # the chained forward ran the data chain: the remaining stages work on its workspace
         chained = call.step_ws is not None and td is not None and dq.data_ptr() == td[0].data_ptr() \
             and not defer_lower and _GRAD_STAGE_HOOK is None
         if chained:
@@ -1285,32 +1299,25 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
         else:
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             d_emb = torch.empty((n, hp), dtype=torch.float32, device=dev) if call.sink is not None else None
-        common = (n, b, c_in, hidden, tot, body_layers, mode, call.math, gp[5], gp[2], gp[3], gp[4], call.x.data_ptr(),
-                  x_stride, base, base + a_bytes + w_bytes, base + a_bytes, t[0], t[2], t[4], dq.data_ptr(),
-                  d_v.data_ptr() if d_v is not None else None, d_emb.data_ptr() if d_emb is not None else None,
-                  fb, cache.offsets, ws.data_ptr(), ws_bytes, gp[6])
+        offsets = cache.offsets
+        desc = call.desc
+        desc.dq, desc.d_out_v = dq.data_ptr(), d_v.data_ptr() if d_v is not None else None
+        desc.d_embeds = d_emb.data_ptr() if d_emb is not None else None
+        desc.flat, desc.offsets, desc.workspace = fb, cache.offsets_p, ws.data_ptr()
+        # td_step(): d loss / d Q came from the forward launch, and the reduce launch also writes the loss (mean of the graphs'
+        # terms); over capacity-sized buffers the weight-gradient GEMM takes the live row count from the device
+        td_bwd = td is not None and dq.data_ptr() == td[0].data_ptr()
+        desc.td_loss = td[0].data_ptr() + 4 * (td[1] + 2 * td[2]) if td_bwd else None
+        desc.n_live = live.data_ptr() if (td_bwd and live is not None) else None
         hook = _GRAD_STAGE_HOOK
         split = tot >= 3 and mode != 2 and not call.nonleaf and (defer_lower or hook is not None)
         mid = 1 + tot // 2 if split else 1
-        if td is not None and dq.data_ptr() == td[0].data_ptr():
-            # td_step(): d loss / d Q came from the forward launch; the reduce launch also writes the loss (mean of the graphs' terms)
-            tb, tn, tbb = td
-            tp = tb.data_ptr()
-            ctd = common[:6] + common[7:21] + common[22:]          # (no mode, no d_out_v: mode 0)
-            if live is not None:
-                # capacity-sized buffers: the weight-gradient GEMM takes the live row count from the device
-                _lib.check(L.hexgnn_qnet_backward_flat_td_live(*ctd, 7, mid, tot, tp + 4 * (tn + tbb), tp + 4 * (tn + 2 * tbb),
-                                                               live.data_ptr(), _stream()), "hexgnn_qnet_backward_flat_td_live")
-            else:
-                _lib.check(L.hexgnn_qnet_backward_flat_td(*ctd, 6 if chained else 7, mid, tot, tp + 4 * (tn + tbb),
-                                                          tp + 4 * (tn + 2 * tbb), _stream()), "hexgnn_qnet_backward_flat_td")
-        else:
-            _lib.check(L.hexgnn_qnet_backward_flat(*common, 7, mid, tot, _stream()), "hexgnn_qnet_backward_flat")
+        _lib.check(L.hexgnn_qnet_call_backward(desc, 6 if chained else 7, mid, tot, _stream()), "hexgnn_qnet_call_backward")
         if split and defer_lower:
-            call.pending = (common, mid, flat, cache.cut, ws, d_emb)
+            call.pending = (desc, mid, flat, cache.cut, ws, d_emb, offsets)
         elif split:
             hook(flat, cache.cut, cache.total)
-            _lib.check(L.hexgnn_qnet_backward_flat(*common, 4, 1, mid, _stream()), "hexgnn_qnet_backward_flat")
+            _lib.check(L.hexgnn_qnet_call_backward(desc, 4, 1, mid, _stream()), "hexgnn_qnet_call_backward")
             hook(flat, 0, cache.cut)
     grads = None
     if call.assign:
@@ -1389,8 +1396,8 @@ def finish_backward(call: "_QNetCall"):
     pend = call.pending
     if pend is None:
         return None, 0
-    common, mid, flat, cut, _ws, _d_emb = pend
-    _lib.check(_lib.lib().hexgnn_qnet_backward_flat(*common, 4, 1, mid, _stream()), "hexgnn_qnet_backward_flat")
+    desc, mid, flat, cut, _ws, _d_emb, _offsets = pend
+    _lib.check(_lib.lib().hexgnn_qnet_call_backward(desc, 4, 1, mid, _stream()), "hexgnn_qnet_call_backward")
     return flat, cut
 
 
@@ -1535,10 +1542,11 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
     When the update selects ONE node per graph, ``sel[g]`` a node of graph g (the action of the sampled transition: what the
     RainbowDQN step gathers, README.md:5,7) and the batch runs on the fused per-graph kernels, the loss is graph-local and the
     forward kernel forms it in its tail: no launch between the network's forward and backward, ``loss`` is written by the
-    backward's reduce launch (``hexgnn_qnet_forward_td`` / ``hexgnn_qnet_backward_flat_td``; in exact fp32 the forward and the
-    backward's data chain are one launch, ``hexgnn_qnet_step_td``, see ``set_one_launch_step``).  A ``sel[g]`` outside graph g
-    makes ``loss`` / ``td[g]`` NaN and raises at the next ``GraphStructure.check()`` (status 16).  Anything else (several
-    selections per graph, graphs above 128 nodes, frozen parameters, ``--noisy_dqn``) runs the three calls.
+    backward's reduce launch (the ``td_*`` fields of the call's ``hexgnn_qnet_call``; in exact fp32 the forward and the backward's
+    data chain are one launch, ``hexgnn_qnet_call_forward`` with ``chain_backward``, see ``set_one_launch_step``).
+    A ``sel[g]`` outside graph g makes ``loss`` / ``td[g]`` NaN and raises at the next ``GraphStructure.check()`` (status 16).
+    Anything else (several selections per graph, graphs above 128 nodes, frozen parameters, ``--noisy_dqn``) runs the three
+    calls.
 
     ``defer_lower=True`` returns ``(loss, td, q, call)`` with only the first stage of the staged backward issued (see
     ``qnet_backward``); ``finish_backward(call)`` issues the rest (a no-op returning (None, 0) where the step did not
@@ -1546,7 +1554,7 @@ def td_step(model, x: torch.Tensor, edge_index, graph_indices=None, ptr=None, *,
 
     Capacity-sized batches (``GraphReplayBuffer.sample_device``): ``x._hex_live_rows``, a 1-element int32 device tensor, says
     how many of the rows hold graphs (``ptr[-1]``); rows at or behind it are never read -- the per-graph kernels work from
-    ``ptr``, the batched weight-gradient GEMM takes the count from the device (``hexgnn_qnet_backward_flat_td_live``).  Only the
+    ``ptr``, the batched weight-gradient GEMM takes the count from the device (the descriptor's ``n_live``).  Only the
     fused form above in exact fp32 takes such a batch: anything else raises ``NotImplementedError``."""
     if not x.is_cuda:
         raise _lib.HexGnnError("td_step runs only on the MI355X HIP path (no CPU fallback)")

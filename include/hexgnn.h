@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define HEXGNN_ABI_VERSION 6
+#define HEXGNN_ABI_VERSION 7
 
 #define HEXGNN_OK 0
 #define HEXGNN_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -426,19 +426,68 @@ int hexgnn_qnet_backward_staged(int n, int b, int c_in, int hidden, int total_la
                                 void* workspace, size_t workspace_bytes, int* status,
                                 int stages, int layer_lo, int layer_hi, hexgnn_stream_t stream);
 
-/* The staged call with ALL parameter gradients in ONE flat fp32 buffer (the layout the single RCCL all-reduce uses):
- * gradient k lives at flat + offsets[k], offsets = HOST array of 3 * total_layers + 6 element offsets in the order
- * (d_wl[l], d_bl[l], d_wr[l]) for l = 0 .. total_layers-1, then d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b.  One base
- * pointer + a table the host caches per model instead of 3 * total_layers + 6 pointers rebuilt per step (the eager path
- * of the Python mirror: GN0/models.py:537-584 driven by `loss.backward()`). */
-int hexgnn_qnet_backward_flat(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int mode, int math,
-                              const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                              const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                              const float* lin_w, const float* v0_w, const float* v1_w,
-                              const float* dq, const float* d_out_v, float* d_embeds,
-                              float* flat, const int64_t* offsets /* HOST */,
-                              void* workspace, size_t workspace_bytes, int* status,
-                              int stages, int layer_lo, int layer_hi, hexgnn_stream_t stream);
+/* ---- The fused call as ONE descriptor (ABI 7): everything a fused forward and its backward need, written once.  A caller
+ *      fills it for the forward, hands the SAME object to the backward after setting the backward group, and selects a
+ *      capability by a field value instead of by another entry point.  It replaces hexgnn_qnet_forward_td, _step_td,
+ *      _backward_flat, _backward_flat_td and _backward_flat_td_live of ABI 6; hexgnn_qnet_forward / _backward / _backward_staged
+ *      above stay as positional adapters onto the same implementation.  Plain pointers and sizes; device pointers unless marked
+ *      HOST.  Fields a call does not read may hold anything. ---- */
+typedef struct hexgnn_qnet_call {
+    /* sizeof(hexgnn_qnet_call), else HEXGNN_EINVAL before anything else is looked at */
+    size_t struct_bytes;
+    /* shape: as hexgnn_qnet_forward / hexgnn_qnet_backward.  body_layers is read by the backward (and the chained forward) only;
+     * need_backward and acts_layer by the forward only */
+    int n, b, c_in, hidden, total_layers, body_layers, mode, math, x_stride, need_backward, acts_layer;
+    /* graph: gptr [b+1], the CSR (forward) and its transpose (backward), invdeg [n], x [n][x_stride] */
+    const int* gptr; const int* rowptr; const int* col; const int* rowptr_t; const int* col_t; const float* invdeg;
+    const float* x;
+    /* parameters: wl / bl / wr = HOST arrays of total_layers device pointers; all three NULL = packed into wpack by the
+     * hexgnn_csr_build_grouped_pack of this call (exact fp32 only).  Then the head tail's */
+    const float* const* wl; const float* const* bl; const float* const* wr;
+    const float* lin_w; const float* lin_b; const float* v0_w; const float* v0_b; const float* v1_w; const float* v1_b;
+    /* buffers: wpack (hexgnn_sage_stack_pack_bytes), acts [total_layers][n][HP] and saved (hexgnn_qnet_saved_bytes) go from the
+     * forward to the backward; workspace (hexgnn_qnet_backward_workspace_bytes) is the backward's, shared by all its stages */
+    void* wpack; float* acts; void* saved; void* workspace; size_t workspace_bytes;
+    /* outputs: q [n], out_v [b] (mode 1) or NULL, status [1] (OR-ed into, see above) */
+    float* q; float* out_v; int* status;
+    /* TD tail: `loss = loss_fn(Q[sel], target)` of the RainbowDQN training step (README.md:5,7: --loss_fn=mse,
+     * --prioritized_er=True importance weights; the step of SURVEY.md 8d) is graph-local when the update selects ONE node per
+     * graph, td_sel[g] a row of graph g (the action taken in the sampled transition), so the forward kernel's tail forms it for
+     * its own graph: td_out[g] = Q[td_sel[g]] - td_target[g], td_loss_part[g] = td_weights[g] * l(td_out[g]) and td_dq =
+     * d loss / d Q ([n], zero except at the selected rows) -- no hexgnn_td_loss_forward_backward launch between the two network
+     * launches, same per-entry expressions (bit-identical td and dq).  A td_sel[g] outside graph g sets status |= 16 and
+     * poisons td_out[g] / td_loss_part[g] with NaN.  td_sel == NULL: no tail.  Otherwise mode 0 and need_backward 1 are
+     * required; td_weights may be NULL; td_loss_fn 0 = mse, 1 = Huber(1).  td_loss [1] is the BACKWARD's switch: when set (with
+     * td_loss_part, mode 0) the reduce launch of HEXGNN_QBWD_SMALL also writes td_loss[0] = sum(td_loss_part) / b in
+     * hexgnn_td_loss_forward's reduction shape (its bits) */
+    const int64_t* td_sel; const float* td_target; const float* td_weights; int td_loss_fn;
+    float* td_dq; float* td_out; float* td_loss_part; float* td_loss;
+    /* backward: dq [n], d_out_v [b] (mode 1), d_embeds optional [n][HP] (final_conv_grads).  ALL parameter gradients go into ONE
+     * flat fp32 buffer (the layout the single RCCL all-reduce uses): gradient k lives at flat + offsets[k], offsets = HOST array
+     * of 3 * total_layers + 6 element offsets in the order (d_wl[l], d_bl[l], d_wr[l]) for l = 0 .. total_layers-1, then
+     * d_lin_w, d_lin_b, d_v0_w, d_v0_b, d_v1_w, d_v1_b (mode 2 writes no value-head gradient) -- one base pointer + a table the
+     * host caches per model (the eager path of the Python mirror: GN0/models.py:537-584 driven by `loss.backward()`).
+     * n_live (device, or NULL = the host's n): CAPACITY-sized buffers whose live row count is known on the device only.  n is
+     * then the row count the buffers, the workspace and the launch shapes are planned for, *n_live (0 <= *n_live <= n; larger
+     * values are clamped to n) the rows that hold graphs -- gptr[b] == *n_live.  Replaces the exact-size call of a replay draw
+     * whose sizes the host had to read back first.  The per-graph kernels work from gptr; the batched weight-gradient GEMM, the
+     * one kernel that walks rows by n, keeps the slice COUNT of n and spreads the live rows over those slices on the device
+     * (rows per slice = ceil(*n_live / slices) rounded up to 32; slices behind the live rows write zero slabs), so rows at or
+     * behind *n_live are never read.  *n_live == n gives the bits of n_live == NULL.  Needs td_loss; exact fp32 only (math 1
+     * returns HEXGNN_EUNSUPPORTED before any launch) */
+    const float* dq; const float* d_out_v; float* d_embeds; float* flat; const int64_t* offsets /* HOST */; const int* n_live;
+} hexgnn_qnet_call;
+/* The forward: hexgnn_qnet_forward's launch, with the TD tail when td_sel is set.  chain_backward != 0 (needs the TD tail, math 0,
+ * n > 0, b > 0, and every field the HEXGNN_QBWD_DATA stage reads: rowptr_t, col_t, workspace, body_layers; d_embeds optional):
+ * the forward, the loss and the backward's data chain in ONE launch -- one workgroup per graph runs the forward, the TD tail and
+ * then the backward chain of ITS graph on td_dq; no workgroup waits for another.  Same bits in every output and in everything
+ * the later stages read from saved / workspace as the two launches; the caller then runs hexgnn_qnet_call_backward with
+ * stages = HEXGNN_QBWD_SMALL | HEXGNN_QBWD_HIDDEN on the same descriptor.  Status bits as in the two launches (2: a graph above
+ * 128 rows, 16: a selection outside its graph).  While a profile class is enabled (hexgnn_profile_enable) the two kernels are
+ * launched one after the other, so that per-kernel times keep their meaning. */
+int hexgnn_qnet_call_forward(const hexgnn_qnet_call* call, int chain_backward, hexgnn_stream_t stream);
+/* The backward in stages (hexgnn_qnet_backward_staged's stages, layer_lo, layer_hi) into flat + offsets. */
+int hexgnn_qnet_call_backward(const hexgnn_qnet_call* call, int stages, int layer_lo, int layer_hi, hexgnn_stream_t stream);
 
 /* One-launch SAGE stack kernels behind hexgnn_sage_stack_* (all hidden layers of a stack in one launch when every workgroup can be
  * resident; GN0/models.py:261-294's layer loop).  Their waits have a poll budget: a launch that exhausts it writes NaN rows
@@ -457,66 +506,6 @@ int hexgnn_stack_block_budget(void);
 int hexgnn_debug_stack_mode(int persist, unsigned skew_seed);
 int hexgnn_debug_occupy(int blocks, int usec, const void* buffer, size_t buffer_bytes, void* sink /* >= 16 B */,
                         hexgnn_stream_t stream);
-
-/* The DQN update's loss folded into the network calls (ABI 6): `loss = loss_fn(Q[sel], target)` of the RainbowDQN training step
- * (README.md:5,7: --loss_fn=mse, --prioritized_er=True importance weights; the step of SURVEY.md 8d) is graph-local when the
- * update selects ONE node per graph, sel[g] a row of graph g (the action taken in the sampled transition), so the forward
- * kernel's tail forms it for its own graph: td[g] = Q[sel[g]] - target[g], loss_part[g] = weights[g] * l(td[g]) and
- * dq = d loss / d Q ([n], zero except at the selected rows) -- no hexgnn_td_loss_forward_backward launch between the two
- * network launches.  Same per-entry expressions as that launch (bit-identical td and dq).  A sel[g] outside graph g sets
- * status |= 16 and poisons td[g] / loss_part[g] with NaN.  mode 0, need_backward 1; loss_fn 0 = mse, 1 = Huber(1).
- * hexgnn_qnet_backward_flat_td is hexgnn_qnet_backward_flat (mode 0) whose reduce launch also writes
- * loss[0] = sum(loss_part) / b in hexgnn_td_loss_forward's reduction shape (its bits), when stages has HEXGNN_QBWD_SMALL. */
-int hexgnn_qnet_forward_td(int n, int b, int c_in, int hidden, int total_layers, const int* gptr,
-                           const int* rowptr, const int* col, const float* invdeg, const float* x, int x_stride,
-                           const float* const* wl, const float* const* bl, const float* const* wr,
-                           const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b,
-                           const float* v1_w, const float* v1_b, void* wpack, float* acts, void* saved,
-                           int math, float* q /*[n]*/, int* status,
-                           const int64_t* sel /*[b]*/, const float* target /*[b]*/, const float* weights /*[b] or NULL*/,
-                           int loss_fn, float* dq /*[n]*/, float* td /*[b]*/, float* loss_part /*[b]*/,
-                           hexgnn_stream_t stream);
-int hexgnn_qnet_backward_flat_td(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int math,
-                                 const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                                 const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                                 const float* lin_w, const float* v0_w, const float* v1_w,
-                                 const float* dq, float* d_embeds, float* flat, const int64_t* offsets /* HOST */,
-                                 void* workspace, size_t workspace_bytes, int* status,
-                                 int stages, int layer_lo, int layer_hi,
-                                 const float* loss_part /*[b]*/, float* loss /*[1]*/, hexgnn_stream_t stream);
-/* hexgnn_qnet_backward_flat_td over CAPACITY-sized buffers whose live row count is known on the device only (entry point added
- * to ABI 6, nothing existing changes): n is the row count the buffers, the workspace and the launch shapes are planned for,
- * *n_live (device, 0 <= *n_live <= n; larger values are clamped to n) the rows that hold graphs -- gptr[b] == *n_live.  Replaces
- * the exact-size call of a replay draw whose sizes the host had to read back first.  The per-graph kernels work from gptr; the
- * batched weight-gradient GEMM, the one kernel that walks rows by n, keeps the slice COUNT of n and spreads the live rows over
- * those slices on the device (rows per slice = ceil(*n_live / slices) rounded up to 32; slices behind the live rows write zero
- * slabs), so rows at or behind *n_live are never read.  *n_live == n gives the bits of hexgnn_qnet_backward_flat_td.
- * Exact fp32 only: math 1 returns HEXGNN_EUNSUPPORTED, n_live == NULL HEXGNN_EINVAL, before any launch. */
-int hexgnn_qnet_backward_flat_td_live(int n, int b, int c_in, int hidden, int total_layers, int body_layers, int math,
-                                      const int* gptr, const int* rowptr_t, const int* col_t, const float* invdeg,
-                                      const float* x, int x_stride, const float* acts, const void* saved, const void* wpack,
-                                      const float* lin_w, const float* v0_w, const float* v1_w,
-                                      const float* dq, float* d_embeds, float* flat, const int64_t* offsets /* HOST */,
-                                      void* workspace, size_t workspace_bytes, int* status,
-                                      int stages, int layer_lo, int layer_hi,
-                                      const float* loss_part /*[b]*/, float* loss /*[1]*/, const int* n_live /* device */,
-                                      hexgnn_stream_t stream);
-
-/* The TD step's forward, loss and backward data chain in ONE launch (entry point added to ABI 6, nothing existing changes): what
- * hexgnn_qnet_forward_td followed by the HEXGNN_QBWD_DATA stage of hexgnn_qnet_backward_flat_td does (math 0, mode 0), same
- * arguments, same bits in every output and in everything the later stages read from saved / workspace.  One workgroup per graph
- * runs the forward, the TD tail and then the backward chain of ITS graph; no workgroup waits for another.  The caller then runs
- * hexgnn_qnet_backward_flat_td with stages = HEXGNN_QBWD_SMALL | HEXGNN_QBWD_HIDDEN on the same workspace.  Status bits as in
- * the two launches (2: a graph above 128 rows, 16: a selection outside its graph).  n > 0 and b > 0.  While a profile class is
- * enabled (hexgnn_profile_enable) the two kernels are launched one after the other, so that per-kernel times keep their meaning. */
-int hexgnn_qnet_step_td(int n, int b, int c_in, int hidden, int total_layers, int body_layers, const int* gptr,
-                        const int* rowptr, const int* col, const int* rowptr_t, const int* col_t, const float* invdeg,
-                        const float* x, int x_stride, const float* const* wl, const float* const* bl, const float* const* wr,
-                        const float* lin_w, const float* lin_b, const float* v0_w, const float* v0_b, const float* v1_w,
-                        const float* v1_b, void* wpack, float* acts, void* saved, float* q, int* status,
-                        const int64_t* sel /*[b]*/, const float* target /*[b]*/, const float* weights /*[b] or NULL*/, int loss_fn,
-                        float* dq /*[n]*/, float* td /*[b]*/, float* loss_part /*[b]*/, float* d_embeds /* or NULL */,
-                        void* workspace, size_t workspace_bytes, hexgnn_stream_t stream);
 
 /* ---- double-DQN targets: several weight sets over ONE batch in one load-balanced forward launch.  Entry points added to
  *      ABI 6 (nothing existing changes).  The RainbowDQN update (README.md:5,7: the double-DQN step) runs the

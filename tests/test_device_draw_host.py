@@ -1,12 +1,12 @@
-"""CPU: the entry points of the replay draw that is sized on the device (hexgnn_replay_offsets, hexgnn_per_sample_dev,
-hexgnn_qnet_backward_flat_td_live) refuse bad arguments before anything is launched, and the header, the library and the ctypes
-table agree on them -- name, and number of parameters."""
+"""CPU: the entry points of the replay draw that is sized on the device (hexgnn_replay_offsets, hexgnn_per_sample_dev) refuse bad
+arguments before anything is launched, and the header, the library and the ctypes table agree on them -- name, and number of
+parameters.  (The backward over such a draw -- the n_live field of hexgnn_qnet_call -- is in test_qnet_call_host.py.)"""
 import ctypes
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("hexgnn_replay_offsets", "hexgnn_per_sample_dev", "hexgnn_qnet_backward_flat_td_live")
+NEW = ("hexgnn_replay_offsets", "hexgnn_per_sample_dev")
 
 
 def _host_ptr():
@@ -36,8 +36,7 @@ def test_header_library_and_ctypes_table_agree_on_the_new_entry_points():
                 assert a is ctypes.c_size_t, (name, p)
             else:
                 assert a is ctypes.c_int, (name, p)
-    # the plain forms are still there, unchanged in length
-    assert len(_lib._SIGS["hexgnn_qnet_backward_flat_td_live"][1]) == len(_lib._SIGS["hexgnn_qnet_backward_flat_td"][1]) + 1
+    # the plain form is still there, unchanged in length
     assert len(_lib._SIGS["hexgnn_per_sample_dev"][1]) == len(_lib._SIGS["hexgnn_per_sample"][1])
 
 
@@ -67,24 +66,4 @@ def test_per_sample_dev_refuses_bad_arguments():
     assert f(64, p, 8, p, None, p, p, p, p, None) == -1          # no uniforms
     assert f(64, p, 8, p, p, None, p, p, p, None) == -1 and f(64, p, 8, p, p, p, None, p, p, None) == -1
     assert f(64, p, 8, p, p, p, p, None, p, None) == -1 and f(64, p, 8, p, p, p, p, p, None, None) == -1
-    del keep
-
-
-def test_live_backward_refuses_bad_arguments():
-    """A live row count with math 1 (f16x3) is unsupported; a missing one, a missing gradient buffer or loss is a bad argument.
-    Every pointer the checks want is given (host memory, never dereferenced): the answers come before any launch."""
-    from gnn_hex_amd import _lib
-    L = _lib.lib()
-    keep, p = _host_ptr()
-
-    def call(math=0, flat=p, offsets=p, loss_part=p, loss=p, n_live=p, total_layers=5):
-        return L.hexgnn_qnet_backward_flat_td_live(204, 4, 2, 35, total_layers, 3, math, p, p, p, p, p, 2, p, p, p, p, p, p, p,
-                                                   None, flat, offsets, p, 1 << 20, p, 7, 1, total_layers, loss_part, loss,
-                                                   n_live, None)
-    assert call(math=1) == -2                                    # HEXGNN_EUNSUPPORTED: the split-f16 GEMM takes no live count
-    assert call(n_live=None) == -1                               # HEXGNN_EINVAL
-    assert call(flat=None) == -1 and call(offsets=None) == -1
-    assert call(loss_part=None) == -1 and call(loss=None) == -1
-    assert call(math=2) == -1 and call(math=-1) == -1
-    assert call(total_layers=0) == -1 and call(total_layers=65) == -1
     del keep

@@ -2,7 +2,9 @@
 """A complete RainbowDQN-style self-play loop on the HIP path (what GN0/RainbowDQN's train.py does with the reference
 pieces, README.md:5,7 flags): 128 parallel Hex-11 envs, eps-greedy acting with the online network, n-step (2) transitions
 into two prioritized replay rings (maker / breaker), double-DQN targets from a target network, importance-weighted MSE,
-Adam, priority updates.  Everything between two prints stays on the GPU except one read-back per 16-move rollout.
+Adam, priority updates.  Everything between two prints stays on the GPU except one read-back per 16-move rollout -- and with
+--device-store not even that: the transitions are assembled and stored on the device, and the host reads one small pinned
+record per iteration, an iteration late.
 
     python examples/selfplay_train.py --iters 50
 
@@ -21,7 +23,7 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gnn_hex_amd import ops  # noqa: E402
 from gnn_hex_amd.models import get_pre_defined  # noqa: E402
-from gnn_hex_amd.multi_env_manager import DeviceRollout, Env_manager, RolloutStitcher  # noqa: E402
+from gnn_hex_amd.multi_env_manager import DeviceRollout, DeviceTransitionFeed, Env_manager, RolloutStitcher  # noqa: E402
 from gnn_hex_amd.replay import GraphedUpdate, GraphReplayBuffer  # noqa: E402
 
 
@@ -45,7 +47,16 @@ def main():
                     help="every update as ONE HIP graph per side (replay.GraphedUpdate): the draw is sized on the device, so "
                          "the host neither waits for the drawn slots nor issues the update's launches one by one "
                          "(fp32 only; with --no-graph the same sequence is issued eagerly, still without a host wait)")
+    ap.add_argument("--device-store", action="store_true",
+                    help="assemble the n-step transitions and store them in the replay rings on the device "
+                         "(multi_env_manager.DeviceTransitionFeed): no run_end, no host assembly, no put_block; every run "
+                         "continues the previous one on the device.  Implies --graph-updates")
     args = ap.parse_args()
+    if args.device_store:
+        if args.async_rollout:
+            ap.error("--device-store issues rollout, store and updates in stream order: there is no host work to hide "
+                     "behind --async-rollout")
+        args.graph_updates = True
     ops.set_math(args.math)
     gamma, n_step = 0.97, 2
     margs = Namespace(num_layers=args.layers, hidden_channels=args.hidden, norm=False, noisy_dqn=False, noisy_sigma0=0.5,
@@ -63,7 +74,8 @@ def main():
             False: GraphReplayBuffer(cap, args.hex_size, prioritized=True, alpha=0.5)}
     rollout = DeviceRollout(mgr, q_net, steps=args.rollout, eps=0.12, graph=not args.no_graph)
     stitch = RolloutStitcher(mgr)      # carries the last 2 * n_step moves of a rollout into the next assembly
-    frames = updates = games = 0
+    feed = DeviceTransitionFeed(rollout, bufs[True], bufs[False]) if args.device_store else None
+    frames = updates = games = games0 = 0
     last_loss = float("nan")
     t0 = time.perf_counter()
     ahead = None
@@ -71,17 +83,30 @@ def main():
         if it == 0:       # start of the timed part
             torch.cuda.synchronize()
             frames = updates = games = 0
+            if feed is not None:
+                feed.settle()         # (outside the timed part: the games of the untimed iterations are all counted now)
+                games0 = feed.games
             t0 = time.perf_counter()
-        res = rollout.run_end(ahead) if ahead is not None else rollout.run()
         frames += args.envs * args.rollout
-        games += int(res.dones.sum())
-        mb, bb = stitch.assemble(res)
-        bufs[True].put_block(mb)
-        bufs[False].put_block(bb)
+        if feed is not None:
+            # rollout, assembly, store: issued, never waited for.  push() consumes the PREVIOUS push's record (pinned, long
+            # complete), which is what the sizes below are: the host runs at most one iteration ahead of the GPU
+            if it == -args.warm:
+                rollout.run_begin()
+            else:
+                rollout.run_continue()
+            feed.push()
+        else:
+            res = rollout.run_end(ahead) if ahead is not None else rollout.run()
+            games += int(res.dones.sum())
+            mb, bb = stitch.assemble(res)
+            bufs[True].put_block(mb)
+            bufs[False].put_block(bb)
         # Updates alternate between the two buffers, and a buffer's next draw (stream-ordered behind its own priority
         # update) is started right after its update is issued: while the host waits for those indices and builds that
         # batch, the GPU runs the OTHER buffer's update.
-        sides = [sd for sd in (True, False) if len(bufs[sd]) >= args.batch]
+        # (device store: the settled size, one push old, once a side's update exists -- len() would wait for this push's record)
+        sides = [sd for sd in (True, False) if (bufs[sd].size if feed is not None and sd in graphed else len(bufs[sd])) >= args.batch]
         pending = {} if args.graph_updates else {sd: bufs[sd].sample_begin(args.batch, beta=0.6) for sd in sides}
         # (after put_block: the run overwrites the snapshot ring; after the first draws: they need not wait for the rollout)
         ahead = rollout.run_begin() if args.async_rollout else None
@@ -115,9 +140,12 @@ def main():
         rollout.run_end(ahead)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if feed is not None:
+        feed.settle()
+        games = feed.games - games0
     print("hex %d, %d envs, GNN %dx%d, math %s%s%s: %.0f env frames/s, %.1f updates/s (batch %d), %d games finished, last loss %.4f"
           % (args.hex_size, args.envs, args.layers, args.hidden, args.math, ", rollout one iteration ahead" if args.async_rollout else "",
-             ", graphed updates" if args.graph_updates else "", frames / dt, updates / dt, args.batch, games,
+             (", device store" if args.device_store else ", graphed updates") if args.graph_updates else "", frames / dt, updates / dt, args.batch, games,
              float(last_loss)))
 
 

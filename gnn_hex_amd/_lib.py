@@ -41,6 +41,22 @@ class QNetCall(C.Structure):
 
 QNET_CALL_BYTES = C.sizeof(QNetCall)
 
+
+class TransitionsCall(C.Structure):
+    """``hexgnn_transitions_call`` of include/hexgnn.h, field for field (tests/test_device_store_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes")
+                + _fields(ci, "H P k n_count prune_exploratories side0_maker list_len coef_stride")
+                + _fields(vp, "n_steps result rank expl coef src_step env action reward next_step done count"))
+
+
+class StoreCall(C.Structure):
+    """``hexgnn_store_call`` of include/hexgnn.h, field for field."""
+    _fields_ = (_fields(sz, "struct_bytes")
+                + _fields(ci, "capacity nv words list_len side edge_limit H P k start_nodes start_edges")
+                + _fields(vp, "count src_step env action reward next_step done")
+                + _fields(vp, "hist_adj hist_alive result sizes0 start_adj start_alive")
+                + _fields(vp, "adj alive side_bytes ring_action ring_reward ring_done sizes ring_words leaves record env_done"))
+
 _SIGS = {
     "hexgnn_abi_version": (ci, []),
     "hexgnn_strerror": (C.c_char_p, [ci]),
@@ -138,6 +154,8 @@ _SIGS = {
     "hexgnn_per_sample": (ci, [ci, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]),
     "hexgnn_per_sample_dev": (ci, [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]),
     "hexgnn_replay_offsets": (ci, [ci, vp, ci, ci, vp, vp, vp, vp, vp]),
+    "hexgnn_transitions_assemble": (ci, [C.POINTER(TransitionsCall), vp]),
+    "hexgnn_replay_store_dev": (ci, [C.POINTER(StoreCall), vp]),
     "hexgnn_select_actions": (ci, [ci, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     "hexgnn_sample_actions": (ci, [ci, vp, vp, vp, ci, C.c_float, vp, vp, vp, vp, vp]),
     "hexgnn_arena_ply": (ci, [vp, vp, vp, vp, ci, C.c_float, vp, vp, ci, vp, vp, vp, vp, vp]),

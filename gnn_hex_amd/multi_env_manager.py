@@ -138,7 +138,8 @@ class DeviceRollout:
     whole sequence is ONE HIP graph (``gnn_hex_amd.graphs``), so a rollout costs one launch + one read-back.  The
     reference does this with a Python loop over envs per move (graph_game/multi_env_manager.py:76-103 +
     GN0/RainbowDQN/evaluate_elo.py:253-275).  ``steps`` must be even so the side to move is the same before and after;
-    the model's weights are read at run time (training between runs is fine, ``grow_*`` needs a new rollout)."""
+    the model's weights are read at run time (training between runs is fine, ``grow_*`` needs a new rollout).
+    ``run_continue()`` issues a run without the host's sizes and without a read-back; ``DeviceTransitionFeed`` consumes it."""
 
     def __init__(self, mgr: "Env_manager", model, steps: int = 16, eps: float = 0.05, graph: bool = True):
         if steps < 2 or steps % 2:
@@ -162,6 +163,9 @@ class DeviceRollout:
         self._mt = torch.zeros(k, dtype=torch.int32, device=dev)
         self._tm = torch.zeros(k, dtype=torch.int32, device=dev)
         self._run_no = 0           # bumped by every run(): results of earlier runs view overwritten snapshots
+        self._settled_run = 0      # the run up to which mgr._sizes is current (run_end, or DeviceTransitionFeed.settle)
+        self.sizes0_dev = torch.zeros((k, 2), dtype=torch.int32, device=dev)     # run_continue: graph sizes at the run's start
+        self._sizes0_host = None   # the same for a run issued by run_begin (host-known)
         self._graph = None
         if graph:
             from .graphs import GraphedStep
@@ -169,6 +173,7 @@ class DeviceRollout:
             state = self.mgr._state_tensors()
             self._graph = GraphedStep(self._body, warmup=1)
             self.mgr._restore_state_tensors(state)      # warm-up + capture played moves: put the boards back
+        self._mgr_touch = mgr._touch
 
     # -- pieces ----------------------------------------------------------------------------------------
     def _export(self, slot: int):
@@ -214,7 +219,11 @@ class DeviceRollout:
             raise RuntimeError("this rollout was built with %r to move" % self.start_side)
         if getattr(self, "_open", False):
             raise RuntimeError("run_begin() called twice without run_end()")
+        if self._settled_run != self._run_no and self._mgr_touch == mgr._touch:
+            raise RuntimeError("the last run was issued by run_continue() and its graph sizes have not reached the host yet: "
+                               "DeviceTransitionFeed.settle() first")
         sizes0 = mgr._sizes.copy()
+        self._sizes0_host, self._mgr_touch = sizes0, mgr._touch
         self._run_no += 1
         self.obs.set_offsets(mgr._sizes)
         if self._graph is not None:
@@ -224,12 +233,33 @@ class DeviceRollout:
         self._open = True
         return (self._run_no, sizes0)
 
+    def run_continue(self) -> None:
+        """Issue a run that continues the previous one with nothing from the host: the observation offsets are the ones the
+        previous run's last ``hexgnn_env_offsets`` left on the device, so the previous run needs no ``run_end`` and
+        ``mgr._sizes`` may lag (``DeviceTransitionFeed.settle`` refreshes it).  The run's histories are consumed on the device
+        (``DeviceTransitionFeed.push``).  ``RuntimeError`` before the first run and when the manager was reset, resized or
+        stepped by hand since the previous run was issued: the device-side offsets then describe other boards."""
+        mgr = self.mgr
+        if self._run_no == 0:
+            raise RuntimeError("run_continue() continues a previous run: issue the first one with run_begin()")
+        if self._mgr_touch != mgr._touch or mgr.global_onturn != self.start_side:
+            raise RuntimeError("the manager was reset, resized or stepped since the previous run: start again with run_begin()")
+        self.sizes0_dev.copy_(self.result[self.T - 1, :, 2:4])     # (before the run overwrites its result words)
+        self._sizes0_host = None
+        self._run_no += 1
+        if self._graph is not None:
+            self._graph.replay()
+        else:
+            self._body()
+        self._open = False
+
     def run_end(self, handle) -> RolloutResult:
         mgr = self.mgr
         run_no, sizes0 = handle
         if not getattr(self, "_open", False) or run_no != self._run_no:
             raise RuntimeError("run_end() needs the handle of the rollout issued last")
         self._open = False
+        self._settled_run = run_no
         owner = (self, run_no)
         res = self.result.cpu().numpy()                      # the only read-back (also the synchronisation point)
         if res[:, :, 4].any():
@@ -319,6 +349,205 @@ class RolloutStitcher:
         return blocks
 
 
+def transition_coef(gamma, n_steps) -> np.ndarray:
+    """The reward factors of ``Env_manager.assemble_transitions`` as a table ``[len(n_steps), 2 * max(n_steps)]`` (fp64, zero
+    behind a window's end): row ``ni`` holds, for ``j`` in the window of ``n_steps[ni]``, sign * gamma^(j // 2) computed by
+    the very expression used there, so the device assembly multiplies by the same bits."""
+    n_steps = [int(n) for n in n_steps]
+    out = np.zeros((len(n_steps), 2 * max(n_steps)), dtype=np.float64)
+    for ni, n_step in enumerate(n_steps):
+        w = 2 * n_step
+        jj = np.arange(w)
+        out[ni, :w] = ((-(jj % 2)) * 2 + 1) * (float(gamma) ** (jj // 2))
+    return out
+
+
+class DeviceTransitionFeed:
+    """Rollout -> replay rings without the host: what ``run_end`` -> ``RolloutStitcher.assemble`` -> ``put_block`` do, on the
+    device (``hexgnn_transitions_assemble`` + ``hexgnn_replay_store_dev``), with the same transitions, ring slots and bits.
+
+        feed = DeviceTransitionFeed(rollout, maker_buffer, breaker_buffer)
+        rollout.run_begin()                  # the first run; later ones: rollout.run_continue()
+        feed.push()                          # issued behind the run; nothing is waited for
+        ... GraphedUpdate.step() ...
+        feed.settle()                        # (push() does it for the previous push) -> episode counters
+
+    The feed keeps the history on the device: the last ``keep = 2 max(n_steps) - 1`` moves of the previous push in front of
+    the run's ``T`` new ones (``keep + T + 1`` board snapshots), the per-side transition lists and the reward factors.
+    ``push()`` copies the run's arrays behind the carried prefix, assembles, stores each side's list into its buffer (a
+    graph with more directed edges than the buffer's draw buffers hold is never stored: such a transition is dropped and
+    reported), raises the new leaves to the running maximum priority, moves the last ``keep`` moves to the front and starts a
+    non-blocking copy of a small record to pinned memory.  ``settle()`` waits for that record and refreshes what the host
+    mirrors: ``mgr._sizes`` / ``last_obs`` / creation times as ``run_end`` does, and the buffers' ``pos``, ``size``, graph
+    sizes and sides.  At most one record is outstanding: ``push()`` settles the previous one first (its event completed an
+    iteration ago), so the host runs at most one iteration ahead of the GPU.  A buffer's own host-side methods settle too."""
+
+    def __init__(self, rollout: DeviceRollout, maker_buffer, breaker_buffer, edge_limit: int = None):
+        """``edge_limit``: a tighter bound on the directed edges of a stored graph than the buffers' own (tests)."""
+        mgr = rollout.mgr
+        self.edge_limit = edge_limit
+        self.rollout, self.mgr, self.bufs = rollout, mgr, (maker_buffer, breaker_buffer)
+        self.n_steps = [int(n) for n in mgr.n_steps]
+        if not self.n_steps or len(self.n_steps) > 8 or min(self.n_steps) < 1:
+            raise ValueError("n_steps: 1 to 8 positive window lengths")
+        self.keep = 2 * max(self.n_steps) - 1
+        T, k, nv, W = rollout.T, mgr.num_envs, mgr._nv, mgr._words
+        if T < self.keep:
+            raise ValueError("a rollout must be at least 2 * n_step - 1 = %d moves long" % self.keep)
+        # per push and side: T / 2 start moves, each with one window per n_step and env
+        self.list_len = L = (T // 2) * len(self.n_steps) * k
+        dev = mgr.device
+        here = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        if maker_buffer is breaker_buffer:
+            raise ValueError("maker and breaker transitions go to two buffers")
+        for buf in self.bufs:
+            if not buf.prioritized:
+                raise ValueError("the device store raises new transitions to the running maximum priority: prioritized=True")
+            bd = buf.device
+            if torch.device("cuda", bd.index if bd.index is not None else torch.cuda.current_device()) != here:
+                raise ValueError("buffer on another device than the env manager")
+            if buf.hex_size != mgr.hex_size:
+                raise ValueError("buffer of hex_size %d, manager of hex_size %d" % (buf.hex_size, mgr.hex_size))
+            if buf.capacity < L:
+                raise ValueError("buffer capacity %d is below the %d transitions one push can store" % (buf.capacity, L))
+        H = self.keep + T
+        z = lambda *shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)     # noqa: E731
+        self.result, self.rank, self.expl = z(H, k, 5, dtype=torch.int32), z(H, k, dtype=torch.int32), z(H, k, dtype=torch.uint8)
+        self.adj, self.alive = z(H + 1, k, nv, W, dtype=torch.int64), z(H + 1, k, nv, dtype=torch.uint8)
+        kp = self.keep
+        self._tail = (z(kp, k, 5, dtype=torch.int32), z(kp, k, dtype=torch.int32), z(kp, k, dtype=torch.uint8),
+                      z(kp + 1, k, nv, W, dtype=torch.int64), z(kp + 1, k, nv, dtype=torch.uint8))
+        self.sizes0 = z(k, 2, dtype=torch.int32)
+        self.src_step, self.env, self.action = (z(2, L, dtype=torch.int32) for _ in range(3))
+        self.next_step, self.reward, self.done = z(2, L, dtype=torch.int32), z(2, L, dtype=torch.float32), z(2, L, dtype=torch.uint8)
+        self.count = z(2, dtype=torch.int32)
+        self.leaves = torch.full((2, L), -1, dtype=torch.int32, device=dev)
+        self._rec_len = 16 + 5 * L
+        self.record = z(2 * self._rec_len + 3 * k, dtype=torch.int32)       # two store records | last sizes [k][2] | env_done [k]
+        self._pinned = torch.zeros(self.record.numel(), dtype=torch.int32, pin_memory=True)
+        self.coef_host = transition_coef(mgr.gamma, self.n_steps)
+        self.coef = torch.from_numpy(self.coef_host).to(dev)
+        self._n_steps_c = (C.c_int * len(self.n_steps))(*self.n_steps)
+        self._start = mgr._snapshot_handle(mgr._base, 1)
+        self._prefix, self._pending = False, None
+        self._pushed_run, self._touch = 0, mgr._touch
+        self.games = self.maker_wins = self.length_sum = 0      # episode counters over every settled push
+
+    def reset(self):
+        """Forget the carried moves (after ``mgr.reset()`` / a fresh ``run_begin``: the stream is no longer continuous).
+        An outstanding record is settled first."""
+        self.settle()
+        self._prefix = False
+
+    def push(self) -> None:
+        ro, mgr, L = self.rollout, self.mgr, _lib.lib()
+        if ro._run_no == 0 or ro._run_no == self._pushed_run:
+            raise RuntimeError("push() stores the run issued last: issue one first (run_begin / run_continue)")
+        if ro._mgr_touch != mgr._touch:
+            raise RuntimeError("the manager was reset, resized or stepped after the run was issued")
+        if self._prefix and (self._touch != mgr._touch or ro._run_no != self._pushed_run + 1):
+            raise RuntimeError("the carried moves belong to another stream of play (the manager was reset, or a run was not "
+                               "pushed): feed.reset() first")
+        self.settle()
+        limits = [buf._device_store_begin(self) for buf in self.bufs]
+        if self.edge_limit is not None:
+            limits = [min(int(self.edge_limit), v) for v in limits]
+        T, k, kp = ro.T, mgr.num_envs, self.keep
+        P = kp if self._prefix else 0
+        H = P + T
+        self.result[P:H].copy_(ro.result)
+        self.rank[P:H].copy_(ro.rank)
+        self.expl[P:H].copy_(ro.expl)
+        self.adj[P:H + 1].copy_(ro.adj)
+        self.alive[P:H + 1].copy_(ro.alive)
+        start_maker = ro.start_side == "m"
+        if P == 0:
+            if ro._sizes0_host is not None:
+                self.sizes0.copy_(torch.from_numpy(ro._sizes0_host.astype(np.int32)))
+            else:
+                self.sizes0.copy_(ro.sizes0_dev)
+        side0 = start_maker if P % 2 == 0 else not start_maker
+        st = ops._stream()
+        call = _lib.TransitionsCall(
+            struct_bytes=C.sizeof(_lib.TransitionsCall), H=H, P=P, k=k, n_count=len(self.n_steps),
+            prune_exploratories=int(bool(mgr.prune_exploratories)), side0_maker=int(side0), list_len=self.list_len,
+            coef_stride=self.coef_host.shape[1], n_steps=C.cast(self._n_steps_c, C.c_void_p), result=self.result.data_ptr(),
+            rank=self.rank.data_ptr(), expl=self.expl.data_ptr(), coef=self.coef.data_ptr(), src_step=self.src_step.data_ptr(),
+            env=self.env.data_ptr(), action=self.action.data_ptr(), reward=self.reward.data_ptr(),
+            next_step=self.next_step.data_ptr(), done=self.done.data_ptr(), count=self.count.data_ptr())
+        _lib.check(L.hexgnn_transitions_assemble(C.byref(call), st), "hexgnn_transitions_assemble")
+        rl = self._rec_len
+        for s, buf in enumerate(self.bufs):
+            rec = self.record[s * rl:(s + 1) * rl]
+            sc = _lib.StoreCall(
+                struct_bytes=C.sizeof(_lib.StoreCall), capacity=buf.capacity, nv=buf.nv, words=buf.words, list_len=self.list_len,
+                side=1 - s, edge_limit=limits[s], H=H, P=P, k=k, start_nodes=int(mgr._base_sizes[0, 0]),
+                start_edges=int(mgr._base_sizes[0, 1]), count=self.count[s:].data_ptr(), src_step=self.src_step[s].data_ptr(),
+                env=self.env[s].data_ptr(), action=self.action[s].data_ptr(), reward=self.reward[s].data_ptr(),
+                next_step=self.next_step[s].data_ptr(), done=self.done[s].data_ptr(), hist_adj=self.adj.data_ptr(),
+                hist_alive=self.alive.data_ptr(), result=self.result.data_ptr(), sizes0=self.sizes0.data_ptr(),
+                start_adj=self._start[0].data_ptr(), start_alive=self._start[1].data_ptr(), adj=buf.adj.data_ptr(),
+                alive=buf.alive.data_ptr(), side_bytes=buf.side.data_ptr(), ring_action=buf.action.data_ptr(),
+                ring_reward=buf.reward.data_ptr(), ring_done=buf.done.data_ptr(), sizes=buf.sizes_dev.data_ptr(),
+                ring_words=buf._ring_words.data_ptr(), leaves=self.leaves[s].data_ptr(), record=rec.data_ptr(),
+                env_done=self.record[2 * rl + 2 * k:].data_ptr() if s == 0 else None)
+            _lib.check(L.hexgnn_replay_store_dev(C.byref(sc), st), "hexgnn_replay_store_dev")
+            buf._tree_update_td(self.leaves[s], None)          # new transitions enter at the running maximum priority
+        self.record[2 * rl:2 * rl + 2 * k].view(k, 2).copy_(self.result[H - 1, :, 2:4])
+        # next prefix: the last `keep` moves with their keep + 1 observations (through scratch: the ranges may overlap)
+        self.sizes0.copy_(self.result[H - kp - 1, :, 2:4])
+        for hist, tail, n in zip((self.result, self.rank, self.expl, self.adj, self.alive), self._tail, (kp, kp, kp, kp + 1, kp + 1)):
+            lo = H - kp
+            tail.copy_(hist[lo:lo + n])
+            hist[:n].copy_(tail)
+        self._pinned.copy_(self.record, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._prefix, self._pushed_run, self._touch, ro._open = True, ro._run_no, mgr._touch, False
+        self._pending = (ev, ro._run_no, mgr._touch, P)
+        for buf in self.bufs:
+            buf._device_stores.append(self)
+
+    def settle(self):
+        """Consume the outstanding record, if any: refresh the manager's and the buffers' host mirrors, raise ``ValueError``
+        for an illegal action (as ``run_end``) and ``RuntimeError`` when transitions were dropped by the edge limit, and
+        return the push's episode counters ``{"games", "maker_wins", "length_sum"}`` (None without an outstanding push)."""
+        if self._pending is None:
+            return None
+        ev, run_no, touch, P = self._pending
+        ev.synchronize()
+        rec = self._pinned.numpy().copy()
+        self._pending = None
+        mgr, ro, k, rl, L = self.mgr, self.rollout, self.mgr.num_envs, self._rec_len, self.list_len
+        dropped = 0
+        for s, buf in enumerate(self.bufs):
+            buf._device_stores.remove(self)
+            r = rec[s * rl:(s + 1) * rl]
+            buf._device_store_settle(r[:16], r[16:16 + L], r[16 + L:].reshape(L, 4), 1 - s)
+            dropped += int(r[2])
+        head = rec[:16]
+        # (not when the host has reset / stepped the boards since, or run_end has read this run or a later one: its sizes are newer)
+        if touch == mgr._touch and ro._settled_run < run_no:
+            mgr._sizes = rec[2 * rl:2 * rl + 2 * k].reshape(k, 2).astype(np.int64)
+            mgr.last_obs = None
+            now = time.perf_counter()
+            for i in np.nonzero(rec[2 * rl + 2 * k:2 * rl + 3 * k])[0]:
+                mgr._creation_time[i] = now
+            ro._settled_run = run_no
+        out = {"games": int(head[5]), "maker_wins": int(head[6]), "length_sum": int(head[7])}
+        self.games += out["games"]
+        self.maker_wins += out["maker_wins"]
+        self.length_sum += out["length_sum"]
+        if head[8]:
+            t, i = divmod(int(head[8]) - 1, k)
+            raise ValueError("illegal action at step %d for env %d" % (t, i))
+        if dropped:
+            raise RuntimeError("%d transitions were dropped: a graph of %d directed edges exceeds what the replay buffers' draw "
+                               "buffers hold per graph (the sizes are recorded: GraphedUpdate makes larger ones on its next step)"
+                               % (dropped, max(int(rec[4]), int(rec[rl + 4]))))
+        return out
+
+
 class _EnvView:
     """Read-only stand-in for the per-env ``Hex_game`` objects of the reference's ``Env_manager.envs``."""
 
@@ -387,6 +616,7 @@ class Env_manager:
     def change_hex_size(self, new_size):
         L = _lib.lib()
         self._destroy()
+        self._touch = getattr(self, "_touch", 0) + 1      # the boards changed under any rollout in flight (DeviceRollout.run_continue)
         self.hex_size = new_size
         self.global_onturn = "m"
         with torch.cuda.device(self.device):
@@ -506,6 +736,7 @@ class Env_manager:
             raise ValueError("expected %d actions" % self.num_envs)
         result = torch.empty((self.num_envs, 5), dtype=torch.int32, device=self.device)
         reset_maker = self.global_onturn == "b"      # finished envs restart on the side everyone moves to next
+        self._touch += 1
         _lib.check(L.hexgnn_env_step(self._h, act.data_ptr(), 1, 1, int(reset_maker), result.data_ptr(), ops._stream()),
                    "hexgnn_env_step")
         res = result.cpu().numpy()
@@ -536,6 +767,7 @@ class Env_manager:
     def reset(self) -> ObsList:
         L = _lib.lib()
         self.global_onturn = "m"
+        self._touch += 1
         _lib.check(L.hexgnn_env_reset(self._h, None, 1, None, ops._stream()), "hexgnn_env_reset")
         self._sizes = np.tile(self._base_sizes, (self.num_envs, 1))
         self._creation_time = [time.perf_counter()] * self.num_envs
@@ -561,6 +793,7 @@ class Env_manager:
                                                t["tm"].data_ptr(), t["rm"].data_ptr(), t["rb"].data_ptr(), ops._stream()),
                    "hexgnn_env_import")
         self._sizes, self.global_onturn = t["sizes"].copy(), t["onturn"]
+        self._touch += 1
         self.last_obs = None
 
     # ---- raw state (tests, debugging) ------------------------------------------------------------------

@@ -12,6 +12,7 @@ against that oracle; method names follow the upstream buffer (``put`` / ``sample
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import List, Optional
 
 import numpy as np
@@ -82,13 +83,59 @@ class GraphReplayBuffer:
         self._max_edges, self._max_nodes = 0, 0           # largest graph ever stored (host-known: bounds of sample_device)
         self._draw_size = z(1, dtype=torch.int32)         # fill level and beta of the next device-side draw
         self._draw_beta = z(1, dtype=torch.float64)
+        # device stores (multi_env_manager.DeviceTransitionFeed): the ring's (position, fill level) as device words once a feed
+        # has stored here, the feeds whose record the host has not consumed yet, and the draw buffers handed out (weakly held:
+        # the store's edge limit is the smallest of them)
+        self._ring_words = None
+        self._device_stores = []
+        self._draw_ecaps = weakref.WeakSet()
 
     def __len__(self):
+        self._settle()
         return self.size
 
     @property
     def burnedin(self) -> bool:
+        self._settle()
         return self.size >= self.burnin
+
+    # ---- stores issued on the device -----------------------------------------------------------------------
+    def _settle(self) -> None:
+        """Bring the host mirrors up to date with every device store issued so far (waits for their records).  Nothing to do
+        for a buffer that never saw one."""
+        while self._device_stores:
+            self._device_stores[0].settle()
+
+    def _sync_ring_words(self) -> None:
+        """The host moved the ring (put / put_block): tell the device words.  The values travel as kernel arguments."""
+        if self._ring_words is not None:
+            self._ring_words[0:1].fill_(int(self.pos))
+            self._ring_words[1:2].fill_(int(self.size))
+
+    def _device_store_begin(self, feed) -> int:
+        """A feed is about to store here: make the device words and return the edge limit of this store -- no slot may hold a
+        graph with more directed edges than ANY draw buffer in use has columns per graph (``hexgnn_states_observe`` does not
+        check), whatever the host's lagging ``_max_edges`` says."""
+        self._settle()
+        if self._ring_words is None:
+            self._ring_words = torch.zeros(2, dtype=torch.int32, device=self.device)
+            self._sync_ring_words()
+        return min([self.edge_capacity()] + [b.e_cap for b in self._draw_ecaps])
+
+    def _device_store_settle(self, head: np.ndarray, slots: np.ndarray, sizes: np.ndarray, side: int) -> None:
+        """Host mirrors after one device store, from its record (``hexgnn_replay_store_dev``)."""
+        C = self.capacity
+        kept = slots >= 0
+        sl = slots[kept].astype(np.int64)
+        if len(sl):
+            self.n_nodes[sl], self.n_edges[sl] = sizes[kept, 0], sizes[kept, 1]
+            self.n_nodes[sl + C], self.n_edges[sl + C] = sizes[kept, 2], sizes[kept, 3]
+            self.side_host[sl] = side
+            self.side_host[sl + C] = side
+            self._sides[0].add(int(side))
+            self._sides[1].add(int(side))
+        self.pos, self.size = int(head[10]), int(head[11])
+        self._max_nodes, self._max_edges = max(self._max_nodes, int(head[3])), max(self._max_edges, int(head[4]))
 
     # ---- insertion ---------------------------------------------------------------------------------------
     @staticmethod
@@ -134,6 +181,7 @@ class GraphReplayBuffer:
     def put(self, transitions: List[tuple]) -> None:
         """Append transitions ``(state, action, reward, next_state, done)`` as returned by
         ``Env_manager.get_transitions``; new entries get the running maximum priority."""
+        self._settle()
         k = len(transitions)
         if k == 0:
             return
@@ -154,6 +202,7 @@ class GraphReplayBuffer:
         self.done[st] = torch.as_tensor([bool(t[4]) for t in transitions], dtype=torch.bool, device=dev)
         self.pos = int((self.pos + k) % C)
         self.size = min(C, self.size + k)
+        self._sync_ring_words()
         if self.prioritized:
             self._tree_update_td(st, None)         # new transitions enter at the running maximum priority
 
@@ -190,6 +239,7 @@ class GraphReplayBuffer:
 
     def put_block(self, block) -> None:
         """Append a ``TransitionBlock`` from ``Env_manager.assemble_transitions`` (array form of ``put``)."""
+        self._settle()
         k = len(block)
         if k == 0:
             return
@@ -224,6 +274,7 @@ class GraphReplayBuffer:
         self.reward.index_copy_(0, st, sd[3].int().view(torch.float32))
         self.pos = int((self.pos + k) % C)
         self.size = min(C, self.size + k)
+        self._sync_ring_words()
         if self.prioritized:
             self._tree_update_td(st, None)         # new transitions enter at the running maximum priority
 
@@ -259,6 +310,7 @@ class GraphReplayBuffer:
         so far) and starts their copy to pinned host memory; returns a handle for ``sample_end``.  A loop with several
         buffers can begin the next buffer's draw before it waits for this one, so that the host builds one batch while
         the GPU still runs the previous update (examples/selfplay_train.py)."""
+        self._settle()
         if self.size == 0:
             raise ValueError("empty buffer")
         dev = self.device
@@ -324,6 +376,7 @@ class GraphReplayBuffer:
         least the start position's).  A maker move joins the removed node's neighbours, so a mid-game graph can have MORE
         edges than the start position; the host knows every stored graph's size, checks it against the buffers before every
         draw, and ``GraphedUpdate`` makes larger ones when a stored graph outgrows them."""
+        self._settle()
         return -(-3 * max(self._e_start, self._max_edges) // 2)
 
     def draw_buffers(self, batch_size: int) -> "DrawBuffers":
@@ -332,7 +385,9 @@ class GraphReplayBuffer:
         if self.nv > 128:
             raise NotImplementedError("sample_device: boards above 128 nodes (Hex-12 and larger) run on the layer-major kernels, "
                                       "which walk every row of their buffers; use sample()")
-        return DrawBuffers(int(batch_size), self.nv, self.edge_capacity(), self.device)
+        bufs = DrawBuffers(int(batch_size), self.nv, self.edge_capacity(), self.device)
+        self._draw_ecaps.add(bufs)                 # (a device store keeps every graph within the smallest of these)
+        return bufs
 
     def set_draw_params(self, beta: Optional[float] = None) -> None:
         """Refresh the two device words the next ``sample_device`` draws with -- the fill level and beta -- without a host
@@ -340,7 +395,10 @@ class GraphReplayBuffer:
         GPU cannot overwrite a staging buffer the copy has not read yet.  ``sample_device`` calls this itself unless the
         stream is being captured (a captured draw must not bake the values in: ``GraphedUpdate.step`` calls it before every
         replay)."""
-        self._draw_size.fill_(int(self.size))
+        if self._ring_words is not None:           # device stores: the fill level the store kernels left, not the host's (it lags)
+            self._draw_size.copy_(self._ring_words[1:2])
+        else:
+            self._draw_size.fill_(int(self.size))
         self._draw_beta.fill_(float(beta if beta is not None else 0.4))
 
     def draw_offsets(self, slots32: torch.Tensor, shift: int, node_off: torch.Tensor, edge_off: torch.Tensor,
@@ -469,8 +527,10 @@ class GraphedUpdate:
     still no host wait, the graph then ends with the priority update.  Everything the graph reads is read at replay time from
     storage that stays where it is: the weight packs are made from the parameters' own storage by every forward, so an
     in-place optimizer step, ``target.load_state_dict(online.state_dict())`` and ``put`` / ``put_block`` between steps are all
-    seen by the next replay.  What moves storage -- ``grow_*``, ``.to()``, ``load_state_dict(assign=True)`` -- needs a new
-    ``GraphedUpdate``, as it needs a new ``DeviceRollout``.
+    seen by the next replay, and so are stores issued on the device (``multi_env_manager.DeviceTransitionFeed``: the draw then
+    takes its fill level from the ring's device word, not from the host's ``size``, which lags until the store is settled).
+    What moves storage -- ``grow_*``, ``.to()``, ``load_state_dict(assign=True)`` -- needs a new ``GraphedUpdate``, as it needs a
+    new ``DeviceRollout``.
 
     The static buffers hold ``edge_capacity()`` edge columns per graph; when a stored graph outgrows them (the host knows
     every stored size) the next ``step`` makes larger buffers and captures again -- rare, the sizes are bounded by the board.

@@ -629,6 +629,91 @@ int hexgnn_per_sample_dev(int capacity_pow2, const int* size, int b, const doubl
 int hexgnn_replay_offsets(int k, const int* slots, int shift, int n_slots, const int* sizes, int* node_off, int* edge_off,
                           int64_t* ptr, hexgnn_stream_t stream);
 
+/* ---- rollout -> replay without the host (entry points added to ABI 7, nothing existing changes).
+ *      Replaces, on the device, Env_manager.get_transitions (graph_game/multi_env_manager.py:113-165) as
+ *      gnn_hex_amd.Env_manager.assemble_transitions restates it over arrays, the window-skip rule of RolloutStitcher, and the
+ *      ring bookkeeping of GraphReplayBuffer.put_block.  Both calls are stream-ordered, non-allocating, of static launch shape
+ *      (capturable), read nothing back, and return HEXGNN_EINVAL for bad arguments before anything is launched.
+ *
+ * hexgnn_transitions_assemble: a history of H = P + T moves of k envs, as DeviceRollout records them: result [H][k][5] int32
+ * (hexgnn_env_step's words), rank [H][k] int32 (the action = node rank in the observation the move was chosen from), expl
+ * [H][k] u8.  side0_maker: the side to move at observation 0.  P: moves carried over from the previous call (0 = none; else a
+ * window with start move i < P + 1 - 2 n was emitted by that call and is skipped).  n_steps: HOST array [n_count] (1..8
+ * entries, the manager's order); coef [n_count][coef_stride] fp64 (device): coef[ni][j] = sign * gamma^(j / 2), the host's own
+ * factors, coef_stride >= 2 max(n_steps).  For start move i, every n (list order) and env e, with w = 2 n: the window exists
+ * if i + w <= H; R[j] = 0 unless result[j][e][0] >= 0, then +1 if that winner is the side that moved at j, else -1; csum = the
+ * running fp64 sum of R[i + j'] coef[j'] in ascending j'; first_done = first j' with a finished game, first_expl = first
+ * j' >= 1 with an exploratory move (only with prune_exploratories); terminal = first_done < w && first_done <= first_expl;
+ * pruned = first_expl < w && first_expl < first_done; emitted if terminal or not pruned; reward = (float) csum[first_done] if
+ * terminal else csum[w - 1]; next_step = -1 (the start position) if terminal else i + w; action = rank[i][e].
+ * Output: per side the compact lists src_step / env / action / next_step (int32), reward (f32), done (u8), each [2][list_len]
+ * (list 0: maker to move at observation i, list 1: breaker), and count [2] (int32), in the host's order: i ascending, then n
+ * in list order, then e ascending.  Entries behind a count are left untouched.  One workgroup, an integer scan: deterministic. */
+typedef struct hexgnn_transitions_call {
+    size_t struct_bytes;                 /* sizeof(hexgnn_transitions_call), else HEXGNN_EINVAL */
+    int H, P, k, n_count, prune_exploratories, side0_maker, list_len, coef_stride;
+    const int* n_steps;                  /* HOST */
+    const int* result;
+    const int* rank;
+    const uint8_t* expl;
+    const double* coef;
+    int* src_step;
+    int* env;
+    int* action;
+    float* reward;
+    int* next_step;
+    uint8_t* done;
+    int* count;
+} hexgnn_transitions_call;
+int hexgnn_transitions_assemble(const hexgnn_transitions_call* call, hexgnn_stream_t stream);
+
+/* hexgnn_replay_store_dev: ONE side's list (count [1] and the six arrays [list_len] of that side) into one ring of `capacity`
+ * transitions laid out as GraphReplayBuffer keeps it: adj [2 capacity][nv][words] u64, alive [2 capacity][nv] u8, side_bytes
+ * [2 capacity] u8, sizes [2 capacity][2] int32 (slot s = the state, s + capacity = the next state), ring_action [capacity]
+ * int64, ring_reward f32, ring_done u8.  ring_words [2] int32 (device) = (position, fill level), read and advanced here.
+ * The snapshots are hist_adj [H + 1][k][nv][words] / hist_alive [H + 1][k][nv] (observation s = the board after move s - 1),
+ * next_step -1 = start_adj / start_alive with (start_nodes, start_edges).  The (nodes, edges) of observation s > 0 are
+ * result[s - 1][e][2:4], those of observation 0 sizes0 [k][2] int32.
+ * An entry is stored only if its indices are in range and neither graph has more than edge_limit directed edges (no slot may
+ * hold a graph that hexgnn_states_observe would write beyond a draw buffer's edge columns); the others count as dropped.
+ * Stored entries take the slots (position + 0, 1, ...) mod capacity in list order.  leaves [list_len] int32: the slot of every
+ * entry, -1 for the dropped ones and for entries at and behind count (hexgnn_per_update_td ignores them).
+ * record [16 + 5 list_len] int32: [0] position before, [1] count, [2] dropped, [3] / [4] most nodes / edges seen (dropped
+ * entries included), [5] games finished in moves [P, H), [6] maker wins, [7] sum of their lengths, [8] 0 or 1 + the flat index
+ * (move - P) k + env of the first illegal action, [9] stored, [10] position after, [11] fill level after; [16 + p] = leaves[p];
+ * [16 + list_len + 4 p ..] = (nodes, edges) of entry p's state and next state.  env_done [k] int32 (may be NULL): 1 where the
+ * env finished a game in moves [P, H).  capacity >= list_len is required (the host's "keep the last capacity" rule is not
+ * rebuilt).  Two launches: the plan (one workgroup) and the copies (one workgroup per transition half). */
+typedef struct hexgnn_store_call {
+    size_t struct_bytes;                 /* sizeof(hexgnn_store_call), else HEXGNN_EINVAL */
+    int capacity, nv, words, list_len, side, edge_limit, H, P, k, start_nodes, start_edges;
+    const int* count;
+    const int* src_step;
+    const int* env;
+    const int* action;
+    const float* reward;
+    const int* next_step;
+    const uint8_t* done;
+    const uint64_t* hist_adj;
+    const uint8_t* hist_alive;
+    const int* result;
+    const int* sizes0;
+    const uint64_t* start_adj;
+    const uint8_t* start_alive;
+    uint64_t* adj;
+    uint8_t* alive;
+    uint8_t* side_bytes;
+    int64_t* ring_action;
+    float* ring_reward;
+    uint8_t* ring_done;
+    int* sizes;
+    int* ring_words;
+    int* leaves;
+    int* record;
+    int* env_done;
+} hexgnn_store_call;
+int hexgnn_replay_store_dev(const hexgnn_store_call* call, hexgnn_stream_t stream);
+
 /* ---- in-library kernel timing: HIP events recorded on the launch stream around every launch of ONE
  *      kernel class (bench.py's live roofline measurement; torch.cuda.Event would only see torch's current
  *      stream and whole calls).  Not for use under graph capture. --------------------------------------- */

@@ -23,7 +23,8 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gnn_hex_amd import ops  # noqa: E402
 from gnn_hex_amd.models import get_pre_defined  # noqa: E402
-from gnn_hex_amd.multi_env_manager import DeviceRollout, DeviceTransitionFeed, Env_manager, RolloutStitcher  # noqa: E402
+from gnn_hex_amd.multi_env_manager import (DeviceRollout, DeviceTransitionFeed, Env_manager, EpsSchedule,  # noqa: E402
+                                           RolloutStitcher)
 from gnn_hex_amd.replay import GraphedUpdate, GraphReplayBuffer  # noqa: E402
 
 
@@ -51,7 +52,18 @@ def main():
                     help="assemble the n-step transitions and store them in the replay rings on the device "
                          "(multi_env_manager.DeviceTransitionFeed): no run_end, no host assembly, no put_block; every run "
                          "continues the previous one on the device.  Implies --graph-updates")
+    ap.add_argument("--eps-schedule", metavar="INIT,FINAL,DECAY_FRAMES", default=None,
+                    help="the recipe's exploration schedule (--init_eps=0.12 --final_eps=0.05 --eps_decay_frames=100000 is "
+                         "0.12,0.05,100000): epsilon is computed on the device per ply (multi_env_manager.EpsSchedule), so it "
+                         "decays under the one captured rollout and with --device-store.  Default: a fixed epsilon of 0.12")
     args = ap.parse_args()
+    schedule = None
+    if args.eps_schedule is not None:
+        try:
+            e0, e1, decay = args.eps_schedule.split(",")
+            schedule = EpsSchedule(float(e0), float(e1), int(decay))
+        except ValueError as err:
+            ap.error("--eps-schedule INIT,FINAL,DECAY_FRAMES: %s" % err)
     if args.device_store:
         if args.async_rollout:
             ap.error("--device-store issues rollout, store and updates in stream order: there is no host work to hide "
@@ -72,7 +84,7 @@ def main():
     cap = 65536
     bufs = {True: GraphReplayBuffer(cap, args.hex_size, prioritized=True, alpha=0.5),
             False: GraphReplayBuffer(cap, args.hex_size, prioritized=True, alpha=0.5)}
-    rollout = DeviceRollout(mgr, q_net, steps=args.rollout, eps=0.12, graph=not args.no_graph)
+    rollout = DeviceRollout(mgr, q_net, steps=args.rollout, eps=schedule if schedule is not None else 0.12, graph=not args.no_graph)
     stitch = RolloutStitcher(mgr)      # carries the last 2 * n_step moves of a rollout into the next assembly
     feed = DeviceTransitionFeed(rollout, bufs[True], bufs[False]) if args.device_store else None
     frames = updates = games = games0 = 0
@@ -136,6 +148,9 @@ def main():
                 last_loss = loss.detach()
         if (it + 1) % 10 == 0 and it >= 0:
             target_net.load_state_dict(q_net.state_dict())
+            if schedule is not None:      # the host's own frame count: nothing is read back
+                print("iteration %d: %d env frames issued, epsilon %.5f"
+                      % (it + 1, rollout.frames_issued, schedule.value(rollout.frames_issued)))
     if ahead is not None:
         rollout.run_end(ahead)
     torch.cuda.synchronize()
@@ -143,9 +158,10 @@ def main():
     if feed is not None:
         feed.settle()
         games = feed.games - games0
-    print("hex %d, %d envs, GNN %dx%d, math %s%s%s: %.0f env frames/s, %.1f updates/s (batch %d), %d games finished, last loss %.4f"
+    print("hex %d, %d envs, GNN %dx%d, math %s%s%s%s: %.0f env frames/s, %.1f updates/s (batch %d), %d games finished, last loss %.4f"
           % (args.hex_size, args.envs, args.layers, args.hidden, args.math, ", rollout one iteration ahead" if args.async_rollout else "",
-             (", device store" if args.device_store else ", graphed updates") if args.graph_updates else "", frames / dt, updates / dt, args.batch, games,
+             (", device store" if args.device_store else ", graphed updates") if args.graph_updates else "",
+             ", eps schedule %s" % args.eps_schedule if schedule is not None else "", frames / dt, updates / dt, args.batch, games,
              float(last_loss)))
 
 

@@ -57,6 +57,13 @@ class StoreCall(C.Structure):
                 + _fields(vp, "hist_adj hist_alive result sizes0 start_adj start_alive")
                 + _fields(vp, "adj alive side_bytes ring_action ring_reward ring_done sizes ring_words leaves record env_done"))
 
+
+class RolloutCall(C.Structure):
+    """``hexgnn_rollout_call`` of include/hexgnn.h, field for field (tests/test_eps_schedule_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(C.c_int64, "frame_add") + _fields(ci, "reset_maker_turn")
+                + _fields(vp, "gptr q backmap u sched frames action_vertex action_rank exploratory result adj_out alive_out eps_out"))
+
+
 _SIGS = {
     "hexgnn_abi_version": (ci, []),
     "hexgnn_strerror": (C.c_char_p, [ci]),
@@ -159,6 +166,8 @@ _SIGS = {
     "hexgnn_select_actions": (ci, [ci, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp]),
     "hexgnn_sample_actions": (ci, [ci, vp, vp, vp, ci, C.c_float, vp, vp, vp, vp, vp]),
     "hexgnn_arena_ply": (ci, [vp, vp, vp, vp, ci, C.c_float, vp, vp, ci, vp, vp, vp, vp, vp]),
+    "hexgnn_rollout_ply": (ci, [vp, C.POINTER(RolloutCall), vp]),
+    "hexgnn_frames_add": (ci, [vp, C.c_int64, vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_forward_backward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

@@ -61,23 +61,28 @@ struct GameT {
         for (int w = 0; w < WT; ++w) s.w[w] = w < Wr() ? adj[v * Wr() + w] : 0ull;
         return s;
     }
-    // word selection by compare chains: a dynamically indexed register array would be demoted to scratch memory
+    // word selection by AND masks: a dynamically indexed register array is demoted to scratch memory, and from three words on the
+    // compiler turns a chain of `i == w ? s.w[w] : r` selects back into exactly that index.  (Word 0 for an i outside [1, WT).)
     __device__ __forceinline__ static uint64_t word(const Sets& s, int i) {
-        uint64_t r = s.w[0];
+        uint64_t r = 0ull, other = 0ull;
 #pragma unroll
-        for (int w = 1; w < WT; ++w) r = (i == w) ? s.w[w] : r;
-        return r;
+        for (int w = 1; w < WT; ++w) {
+            const uint64_t m = 0ull - (uint64_t)(i == w);
+            r |= s.w[w] & m;
+            other |= m;
+        }
+        return r | (s.w[0] & ~other);
     }
     __device__ __forceinline__ static bool has(const Sets& s, int v) { return (word(s, v >> 6) >> (v & 63)) & 1ull; }
     __device__ __forceinline__ static void clr(Sets& s, int v) {
         const uint64_t m = ~(1ull << (v & 63));
 #pragma unroll
-        for (int w = 0; w < WT; ++w) if ((v >> 6) == w) s.w[w] &= m;
+        for (int w = 0; w < WT; ++w) s.w[w] &= m | (0ull - (uint64_t)((v >> 6) != w));
     }
     __device__ __forceinline__ static void set(Sets& s, int v) {
         const uint64_t m = 1ull << (v & 63);
 #pragma unroll
-        for (int w = 0; w < WT; ++w) if ((v >> 6) == w) s.w[w] |= m;
+        for (int w = 0; w < WT; ++w) s.w[w] |= m & (0ull - (uint64_t)((v >> 6) == w));
     }
     __device__ __forceinline__ bool empty(const Sets& s) const {
         uint64_t o = 0;
@@ -421,6 +426,24 @@ __device__ __forceinline__ void count_game(const G& g, int* n_alive, int* n_dir_
     *n_alive = a; *n_dir_edges = e;
 }
 
+// make_move(v) of the side `mt` on the LDS-resident game (the maker's rewiring, v's removal, dead/captured removal over what the
+// move touched), the side flag flipped, who_won returned.  The one copy behind env_step_kernel, arena_ply_kernel and
+// rollout_ply_kernel, which promise each other's bits.
+template <int WT>
+__device__ __forceinline__ int play_vertex(GameT<WT>& g, int v, int& mt, bool remove_dc, short* rm, short* rb) {
+    typename GameT<WT>::Sets consider;
+#pragma unroll
+    for (int w = 0; w < WT; ++w) consider.w[w] = 0ull;
+    if (mt) consider = g.maker_connect(v);
+    const typename GameT<WT>::Sets nbv = g.get_row(v);
+#pragma unroll
+    for (int w = 0; w < WT; ++w) consider.w[w] |= nbv.w[w];
+    g.remove_vertex(v);
+    mt = !mt;
+    if (remove_dc && !g.maker_won) g.dead_and_captured(consider, rm, rb);
+    return g.who_won();
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // kernels: one 64-thread workgroup per env
 // ------------------------------------------------------------------------------------------------------------
@@ -452,7 +475,6 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev d, const int* __res
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int env = blockIdx.x;
     GameT<WT> g;
-    using Sets = typename GameT<WT>::Sets;
     load_game(g, d, env, lds);
     short* rm = d.resp_maker + (size_t)env * d.nv;
     short* rb = d.resp_breaker + (size_t)env * d.nv;
@@ -464,17 +486,7 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev d, const int* __res
     int winner = -1;
     if (!err) {
         ++moves;
-        Sets consider;
-#pragma unroll
-        for (int w = 0; w < WT; ++w) consider.w[w] = 0ull;
-        if (mt) consider = g.maker_connect(v);
-        const Sets nbv = g.get_row(v);
-#pragma unroll
-        for (int w = 0; w < WT; ++w) consider.w[w] |= nbv.w[w];
-        g.remove_vertex(v);
-        mt = !mt;
-        if (remove_dc && !g.maker_won) g.dead_and_captured(consider, rm, rb);
-        winner = g.who_won();
+        winner = play_vertex(g, v, mt, remove_dc != 0, rm, rb);
     }
     int length = moves;
     if (winner >= 0 && auto_reset) {
@@ -503,7 +515,6 @@ __global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __re
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int env = blockIdx.x, lane = threadIdx.x;
     GameT<WT> g;
-    using Sets = typename GameT<WT>::Sets;
     load_game(g, d, env, lds);
     int* rec = game + 4 * env;
     int* res = result + 5 * env;
@@ -536,17 +547,7 @@ __global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __re
     int winner = -1;
     if (!err) {
         ++moves;
-        Sets consider;
-#pragma unroll
-        for (int w = 0; w < WT; ++w) consider.w[w] = 0ull;
-        if (mt) consider = g.maker_connect(v);
-        const Sets nbv = g.get_row(v);
-#pragma unroll
-        for (int w = 0; w < WT; ++w) consider.w[w] |= nbv.w[w];
-        g.remove_vertex(v);
-        mt = !mt;
-        if (!g.maker_won) g.dead_and_captured(consider, rm, rb);
-        winner = g.who_won();
+        winner = play_vertex(g, v, mt, true, rm, rb);
     }
     const int length = moves;
     if (winner >= 0) {
@@ -568,6 +569,101 @@ __global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __re
         if (winner < 0 && !err) atomicAdd(live, 1);
     }
 }
+
+// One ply of self-play (include/hexgnn.h: hexgnn_rollout_ply): select_actions_kernel's pick with epsilon read from the device,
+// env_step_kernel's move with dead/captured removal and auto reset, and the board snapshot of env_export_kernel, per env.
+struct RolloutPly {
+    const int* gptr;
+    const float* q;
+    const int64_t* backmap;
+    const float* u;              // [num_envs][2]
+    const double* sched;         // double init, double final, int64 burnin, int64 decay
+    const long long* frames;     // [1]: frames played before this run
+    long long frame_add;         // frames played earlier in this run
+    int reset_maker_turn;
+    int* act_vertex;
+    int* act_rank;
+    unsigned char* expl;
+    int* result;                 // [num_envs][5]
+    uint64_t* adj_out;           // [num_envs][nv][W]
+    uint8_t* alive_out;          // [num_envs][nv]
+    float* eps_out;              // [1] or null
+};
+
+// Linear decay from init to final over `decay` frames behind `burnin`.  PARITY UNPINNED: the reference's schedule is in its
+// absent Rainbow submodule; include/hexgnn.h fixes this formula.  Every fp64 operation is rounded on its own
+// (the intrinsics keep the compiler from contracting the product into the sum), so EpsSchedule.value gives the same bits.
+__device__ __forceinline__ float schedule_eps(const double* __restrict__ sched, long long f) {
+    const double init = sched[0], fin = sched[1];
+    const long long burnin = reinterpret_cast<const long long*>(sched)[2], decay = reinterpret_cast<const long long*>(sched)[3];
+    if (f < burnin) return (float)init;
+    double p = 1.0;
+    if (decay > 0) p = fmin(1.0, (double)(f - burnin) / (double)decay);
+    return (float)__dadd_rn(init, __dmul_rn(__dsub_rn(fin, init), p));
+}
+
+template <int WT>
+__global__ __launch_bounds__(64) void rollout_ply_kernel(EnvDev d, RolloutPly a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int env = blockIdx.x, lane = threadIdx.x;
+    GameT<WT> g;
+    load_game(g, d, env, lds);
+    short* rm = d.resp_maker + (size_t)env * d.nv;
+    short* rb = d.resp_breaker + (size_t)env * d.nv;
+    int* res = a.result + 5 * env;
+    const float eps = schedule_eps(a.sched, a.frames[0] + a.frame_add);
+    // the pick of select_actions_kernel (every lane holds it)
+    const int r0 = a.gptr[env], r1 = a.gptr[env + 1];
+    float best;
+    int arg;
+    graph_first_max(a.q, r0, r1, lane, best, arg);
+    int rank = arg == 0x7fffffff ? -1 : arg - r0;          // -1: graph without a legal move
+    unsigned char ex = 0;
+    const int nact = r1 - r0 - 2;
+    if (nact > 0 && a.u[2 * env] < eps) {
+        int k = (int)(a.u[2 * env + 1] * (float)nact);
+        if (k >= nact) k = nact - 1;
+        rank = 2 + k;
+        ex = 1;
+    }
+    const int v = rank >= 0 ? (int)a.backmap[r0 + rank] : -1;
+    // the move of env_step_kernel with remove_dc = 1, auto_reset = 1
+    int err = 0;
+    if (v < 2 || v >= d.nv || !g.alive[v]) err = 1;
+    int mt = d.maker_turn[env], moves = d.total_moves[env];
+    int winner = -1;
+    if (!err) {
+        ++moves;
+        winner = play_vertex(g, v, mt, true, rm, rb);
+    }
+    const int length = moves;
+    if (winner >= 0) {
+        reset_game_lds(g, d);
+        for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
+        mt = a.reset_maker_turn;
+        moves = 0;
+    }
+    int na, ne;
+    count_game(g, &na, &ne);
+    // the game and its snapshot from the one LDS copy
+    __syncthreads();
+    uint64_t* dst = d.adj + (size_t)env * d.nv * d.W;
+    uint64_t* snap = a.adj_out + (size_t)env * d.nv * d.W;
+    for (int i = threadIdx.x; i < d.nv * d.W; i += 64) { const uint64_t w = g.adj[i]; dst[i] = w; snap[i] = w; }
+    for (int i = threadIdx.x; i < d.nv; i += 64) {
+        const uint8_t al = g.alive[i];
+        d.alive[(size_t)env * d.nv + i] = al;
+        a.alive_out[(size_t)env * d.nv + i] = al;
+    }
+    if (lane == 0) {
+        d.maker_turn[env] = mt; d.total_moves[env] = moves;
+        res[0] = winner; res[1] = length; res[2] = na; res[3] = ne; res[4] = err;
+        a.act_rank[env] = rank; a.act_vertex[env] = v; a.expl[env] = ex;
+        if (env == 0 && a.eps_out) a.eps_out[0] = eps;
+    }
+}
+
+__global__ void frames_add_kernel(long long* frames, long long delta) { frames[0] += delta; }
 
 // Observation of every env into batched buffers (convert_graph.py:77-122, old_style=True; Batch.from_data_list):
 //   x [N][3] = (degree, is_terminal, maker_to_move);  backmap [N] rank -> vertex id (int64)
@@ -746,6 +842,17 @@ static void launch_arena_ply(const EnvDev& d, const int* gptr, const float* q, c
                                                                     reset_maker_turn, game, log_row, result, live);
 }
 
+template <int WT>
+static void launch_rollout_ply(const EnvDev& d, const RolloutPly& a, hipStream_t st) {
+    static bool once = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_ply_kernel<WT>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        return true;
+    }();
+    (void)once;
+    rollout_ply_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, a);
+}
+
 }  // namespace hexgnn
 
 using namespace hexgnn;
@@ -882,6 +989,36 @@ int hexgnn_arena_ply(hexgnn_env* h, const int* gptr, const float* q, const int64
         case 4: launch_arena_ply<4>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
         default: launch_arena_ply<kMaxW>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
     }
+    return check_launch();
+}
+
+int hexgnn_rollout_ply(hexgnn_env* h, const hexgnn_rollout_call* c, hexgnn_stream_t stream_) {
+    if (!h || !c || c->struct_bytes != sizeof(hexgnn_rollout_call)) return HEXGNN_EINVAL;
+    if (!c->sched || !c->frames || c->frame_add < 0) return HEXGNN_EINVAL;
+    if (!c->gptr || !c->q || !c->backmap || !c->u || !c->action_vertex || !c->action_rank || !c->exploratory || !c->result ||
+        !c->adj_out || !c->alive_out)
+        return HEXGNN_EINVAL;
+    Env* e = reinterpret_cast<Env*>(h);
+    hipStream_t st = (hipStream_t)stream_;
+    RolloutPly a;
+    a.gptr = c->gptr; a.q = c->q; a.backmap = c->backmap; a.u = c->u;
+    a.sched = static_cast<const double*>(c->sched); a.frames = reinterpret_cast<const long long*>(c->frames);
+    a.frame_add = c->frame_add; a.reset_maker_turn = c->reset_maker_turn ? 1 : 0;
+    a.act_vertex = c->action_vertex; a.act_rank = c->action_rank; a.expl = c->exploratory; a.result = c->result;
+    a.adj_out = c->adj_out; a.alive_out = c->alive_out; a.eps_out = c->eps_out;
+    switch (e->d.W) {          // as hexgnn_env_step: register-resident vertex sets for the common board sizes
+        case 1: launch_rollout_ply<1>(e->d, a, st); break;
+        case 2: launch_rollout_ply<2>(e->d, a, st); break;
+        case 3: launch_rollout_ply<3>(e->d, a, st); break;
+        case 4: launch_rollout_ply<4>(e->d, a, st); break;
+        default: launch_rollout_ply<kMaxW>(e->d, a, st); break;
+    }
+    return check_launch();
+}
+
+int hexgnn_frames_add(int64_t* frames, int64_t delta, hexgnn_stream_t stream_) {
+    if (!frames) return HEXGNN_EINVAL;
+    frames_add_kernel<<<1, 1, 0, (hipStream_t)stream_>>>(reinterpret_cast<long long*>(frames), (long long)delta);
     return check_launch();
 }
 

@@ -131,6 +131,59 @@ class RolloutResult:
         return self
 
 
+class EpsSchedule:
+    """The exploration schedule of the published training recipes (``--init_eps / --final_eps / --eps_decay_frames``, reference
+    README.md:5-8,48) in the form ``hexgnn_rollout_ply`` reads from device memory: epsilon is ``init`` for the first ``burnin``
+    env frames, then moves linearly to ``final`` over ``decay_frames`` frames and stays there.  The trainer that owns the
+    reference's schedule is in its un-vendored Rainbow submodule: the formula is the one include/hexgnn.h fixes (parity unpinned).
+
+    ``value(frame)`` is the host mirror of the kernel's evaluation, bit for bit; ``to_device`` hands out the 32-byte block a
+    ``DeviceRollout`` points its plies at, and ``update`` rewrites every block handed out in place, so a captured rollout follows
+    a changed schedule without a new capture."""
+
+    def __init__(self, init: float, final: float, decay_frames: int, burnin: int = 0):
+        self._blocks = {}
+        self._set(init, final, decay_frames, burnin)
+
+    def _set(self, init, final, decay_frames, burnin):
+        init, final = float(init), float(final)
+        if not (0.0 <= init <= 1.0 and 0.0 <= final <= 1.0):
+            raise ValueError("epsilon is a probability: init and final in [0, 1]")
+        if int(decay_frames) != decay_frames or int(burnin) != burnin or decay_frames < 0 or burnin < 0:
+            raise ValueError("decay_frames and burnin are whole, non-negative frame counts")
+        self.init, self.final, self.decay_frames, self.burnin = init, final, int(decay_frames), int(burnin)
+
+    def value(self, frame: int) -> np.float32:
+        """Epsilon at env frame ``frame``: float64 operations rounded one by one, then one rounding to float32."""
+        f = int(frame)
+        if f < self.burnin:
+            return np.float32(self.init)
+        p = min(1.0, float(f - self.burnin) / float(self.decay_frames)) if self.decay_frames > 0 else 1.0
+        return np.float32(self.init + (self.final - self.init) * p)
+
+    def _words(self) -> torch.Tensor:
+        return torch.from_numpy(np.concatenate([np.array([self.init, self.final], dtype=np.float64).view(np.int64),
+                                                np.array([self.burnin, self.decay_frames], dtype=np.int64)]))
+
+    def to_device(self, device) -> torch.Tensor:
+        """The block ``double init, double final, int64 burnin, int64 decay`` as an int64 [4] tensor on ``device`` (one per
+        device, shared by every rollout that runs this schedule there)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        blk = self._blocks.get(device)
+        if blk is None:
+            blk = self._blocks[device] = self._words().to(device)
+        return blk
+
+    def update(self, init=None, final=None, decay_frames=None, burnin=None) -> None:
+        """Change the schedule (arguments left out keep their value) and rewrite the device blocks in place, stream-ordered."""
+        self._set(self.init if init is None else init, self.final if final is None else final,
+                  self.decay_frames if decay_frames is None else decay_frames, self.burnin if burnin is None else burnin)
+        for blk in self._blocks.values():
+            blk.copy_(self._words())
+
+
 class DeviceRollout:
     """``steps`` lock-step moves of every env of an ``Env_manager`` as a closed device loop: observation (HIP builder) ->
     Q-network forward (advantages only) -> epsilon-greedy -> env step with dead/captured removal and auto reset -> graph
@@ -139,13 +192,23 @@ class DeviceRollout:
     reference does this with a Python loop over envs per move (graph_game/multi_env_manager.py:76-103 +
     GN0/RainbowDQN/evaluate_elo.py:253-275).  ``steps`` must be even so the side to move is the same before and after;
     the model's weights are read at run time (training between runs is fine, ``grow_*`` needs a new rollout).
-    ``run_continue()`` issues a run without the host's sizes and without a read-back; ``DeviceTransitionFeed`` consumes it."""
+    ``run_continue()`` issues a run without the host's sizes and without a read-back; ``DeviceTransitionFeed`` consumes it.
 
-    def __init__(self, mgr: "Env_manager", model, steps: int = 16, eps: float = 0.05, graph: bool = True):
+    ``eps`` is a float, frozen for the rollout's life (under ``graph=True`` it is a kernel argument of the captured graph), or an
+    ``EpsSchedule``: every ply then computes its epsilon on the device from the schedule's block and the frame counter
+    ``frames`` (int64 [1], advanced by ``steps * num_envs`` behind every run), and picks, moves and snapshots in one launch
+    (``hexgnn_rollout_ply``), so the published decay runs under one capture and through ``run_continue``.  ``eps_log`` (float32
+    [steps]) holds the epsilon every ply of the last run used; ``frames_issued`` is the host's count of the frames of every run
+    issued so far (no synchronisation: ``schedule.value(rollout.frames_issued)`` is the epsilon the next run starts with);
+    ``set_frames(n)`` sets both (resuming from a checkpoint)."""
+
+    def __init__(self, mgr: "Env_manager", model, steps: int = 16, eps: Union[float, EpsSchedule] = 0.05, graph: bool = True):
         if steps < 2 or steps % 2:
             raise ValueError("steps must be a positive even number")
         self._live_norm = live_norm_of(model)
-        self.mgr, self.model, self.T, self.eps = mgr, model, steps, float(eps)
+        self.mgr, self.model, self.T = mgr, model, steps
+        self.schedule = eps if isinstance(eps, EpsSchedule) else None
+        self.eps = None if self.schedule is not None else float(eps)
         self.start_side = mgr.global_onturn
         dev = mgr.device
         k, nv, W = mgr.num_envs, mgr._nv, mgr._words
@@ -167,12 +230,20 @@ class DeviceRollout:
         self.sizes0_dev = torch.zeros((k, 2), dtype=torch.int32, device=dev)     # run_continue: graph sizes at the run's start
         self._sizes0_host = None   # the same for a run issued by run_begin (host-known)
         self._graph = None
+        self.frames = self.eps_log = self._sched_dev = None
+        self.frames_issued = 0
+        if self.schedule is not None:
+            self.frames = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.eps_log = torch.zeros(T, dtype=torch.float32, device=dev)
+            self._sched_dev = self.schedule.to_device(self.frames.device)
         if graph:
             from .graphs import GraphedStep
             self.obs.set_offsets(mgr._sizes)
             state = self.mgr._state_tensors()
             self._graph = GraphedStep(self._body, warmup=1)
             self.mgr._restore_state_tensors(state)      # warm-up + capture played moves: put the boards back
+            if self.frames is not None:
+                self.frames.zero_()                     # ... and the frame counter the warm-up advanced
         self._mgr_touch = mgr._touch
 
     # -- pieces ----------------------------------------------------------------------------------------
@@ -189,6 +260,22 @@ class DeviceRollout:
         for t in range(self.T):
             obs.observe_env(mgr._h)
             adv = acting_forward(self.model, obs, maker, mgr._nv, self._live_norm)
+            if self.schedule is not None:
+                u = self.uni[t]
+                u.uniform_()
+                # pick, move with auto reset (finished envs restart on the side everyone moves to next) and snapshot t + 1
+                call = _lib.RolloutCall(
+                    struct_bytes=C.sizeof(_lib.RolloutCall), frame_add=t * k, reset_maker_turn=int(not maker),
+                    gptr=obs.node_off.data_ptr(), q=adv.reshape(-1).data_ptr(), backmap=obs.backmap.data_ptr(), u=u.data_ptr(),
+                    sched=self._sched_dev.data_ptr(), frames=self.frames.data_ptr(), action_vertex=self.vert[t].data_ptr(),
+                    action_rank=self.rank[t].data_ptr(), exploratory=self.expl[t].data_ptr(), result=self.result[t].data_ptr(),
+                    adj_out=self.adj[t + 1].data_ptr(), alive_out=self.alive[t + 1].data_ptr(),
+                    eps_out=self.eps_log[t:].data_ptr())
+                _lib.check(L.hexgnn_rollout_ply(mgr._h, C.byref(call), ops._stream()), "hexgnn_rollout_ply")
+                _lib.check(L.hexgnn_env_offsets(k, self.result[t].data_ptr(), obs.node_off.data_ptr(),
+                                                obs.edge_off.data_ptr(), ops._stream()), "hexgnn_env_offsets")
+                maker = not maker
+                continue
             u = None
             if self.eps > 0:
                 u = self.uni[t]
@@ -204,8 +291,19 @@ class DeviceRollout:
                                             obs.edge_off.data_ptr(), ops._stream()), "hexgnn_env_offsets")
             self._export(t + 1)
             maker = not maker
+        if self.schedule is not None:
+            _lib.check(L.hexgnn_frames_add(self.frames.data_ptr(), self.T * k, ops._stream()), "hexgnn_frames_add")
 
     # -- public ----------------------------------------------------------------------------------------
+    def set_frames(self, n: int) -> None:
+        """Set the frame counter the schedule is evaluated at (device word and host count), e.g. when resuming a checkpoint."""
+        if self.schedule is None:
+            raise RuntimeError("this rollout plays with a fixed epsilon: build it with an EpsSchedule")
+        if n < 0:
+            raise ValueError("a frame count is not negative")
+        self.frames.fill_(int(n))
+        self.frames_issued = int(n)
+
     def run(self) -> RolloutResult:
         return self.run_end(self.run_begin())
 
@@ -225,6 +323,7 @@ class DeviceRollout:
         sizes0 = mgr._sizes.copy()
         self._sizes0_host, self._mgr_touch = sizes0, mgr._touch
         self._run_no += 1
+        self.frames_issued += self.T * mgr.num_envs
         self.obs.set_offsets(mgr._sizes)
         if self._graph is not None:
             self._graph.replay()
@@ -247,6 +346,7 @@ class DeviceRollout:
         self.sizes0_dev.copy_(self.result[self.T - 1, :, 2:4])     # (before the run overwrites its result words)
         self._sizes0_host = None
         self._run_no += 1
+        self.frames_issued += self.T * mgr.num_envs
         if self._graph is not None:
             self._graph.replay()
         else:

@@ -791,6 +791,51 @@ int hexgnn_arena_ply(hexgnn_env* env, const int* gptr, const float* q, const int
                      const float* u, int* forced, int reset_maker_turn, int* game, int* log_row, int* result, int* live,
                      hexgnn_stream_t stream);
 
+/* ---- self-play ply with the exploration schedule on the device (entry points added to ABI 7, nothing existing changes).
+ *      One ply of the acting loop in one launch, one workgroup per env: what hexgnn_select_actions ->
+ *      hexgnn_env_step(remove_dead_and_captured = 1, auto_reset = 1) -> hexgnn_env_export (boards only) do in three, with the
+ *      same outputs and bits, and with epsilon read from DEVICE memory, so that a captured rollout follows the decay schedule of
+ *      the published recipes (--init_eps / --final_eps / --eps_decay_frames, reference README.md:5-8,48) without a new capture.
+ *      The trainer that owns the schedule lives in the reference's un-vendored Rainbow submodule (.gitmodules:1-4): the
+ *      formula is fixed HERE, PARITY UNPINNED.
+ *   sched  [4] 8-byte words (device): double init, double final, int64 burnin, int64 decay.
+ *   frames [1] int64 (device): env frames played before this run; frame_add (host): the frames played earlier in this run
+ *          (ply t of a run over k envs passes t k).  The kernel only reads frames; hexgnn_frames_add advances it behind the
+ *          run's last ply (stream order keeps every ply's read in front of it).
+ *   eps:   f = *frames + frame_add;  f < burnin: eps = (float) init;  else p = decay <= 0 ? 1 : min(1, (double)(f - burnin) /
+ *          (double) decay) and eps = (float)(init + (final - init) * p), every fp64 operation rounded on its own (no fused
+ *          multiply-add): the float32 cast of the same expression in IEEE double arithmetic on the host, bit for bit.
+ *   pick:  gptr / q / backmap / u [num_envs][2] / action_vertex / action_rank / exploratory as hexgnn_select_actions (gptr =
+ *          the node_off of hexgnn_env_observe): the first maximum; explored when u[2 g] < eps, then rank 2 + min((int)(u[2 g + 1]
+ *          n_act), n_act - 1); rank -1 / vertex -1 for a graph without a non-terminal node.
+ *   move:  result [num_envs][5] and reset_maker_turn as hexgnn_env_step; a dead or out-of-range vertex (the -1 above included)
+ *          is error 1 and leaves the env untouched.
+ *   adj_out [num_envs][nv][words] u64 / alive_out [num_envs][nv] u8: the boards after the ply in hexgnn_env_export's layout
+ *          (a rollout's snapshot slot), written from the workgroup's own copy of the game.
+ *   eps_out [1] f32 (may be NULL): the epsilon this ply used.
+ * Every other pointer is required: HEXGNN_EINVAL before anything is launched. */
+typedef struct hexgnn_rollout_call {
+    size_t struct_bytes;                 /* sizeof(hexgnn_rollout_call), else HEXGNN_EINVAL */
+    int64_t frame_add;
+    int reset_maker_turn;
+    const int* gptr;
+    const float* q;
+    const int64_t* backmap;
+    const float* u;
+    const void* sched;
+    const int64_t* frames;
+    int* action_vertex;
+    int* action_rank;
+    uint8_t* exploratory;
+    int* result;
+    uint64_t* adj_out;
+    uint8_t* alive_out;
+    float* eps_out;
+} hexgnn_rollout_call;
+int hexgnn_rollout_ply(hexgnn_env* env, const hexgnn_rollout_call* call, hexgnn_stream_t stream);
+/* *frames += delta (one thread; frames [1] int64 on the device). */
+int hexgnn_frames_add(int64_t* frames, int64_t delta, hexgnn_stream_t stream);
+
 /* ---- layout helpers (host tensors <-> padded layout) ---------------------------------------- */
 /* dst[n][HP] <- src[n][hidden] (row stride src_stride floats), pad columns zeroed; and back. */
 int hexgnn_pad_rows(int n, int hidden, const float* src, int src_stride, float* dst, hexgnn_stream_t stream);

@@ -363,8 +363,11 @@ class DeviceRollout:
         owner = (self, run_no)
         res = self.result.cpu().numpy()                      # the only read-back (also the synchronisation point)
         if res[:, :, 4].any():
-            t, i = np.argwhere(res[:, :, 4])[0]
-            raise ValueError("illegal action at step %d for env %d" % (t, i))
+            # (the error path alone reads these; rank -1: no finite advantage among the graph's non-terminal nodes, or no such node)
+            t, i = (int(v) for v in np.argwhere(res[:, :, 4])[0])
+            nodes = int(sizes0[i, 0]) if t == 0 else int(res[t - 1, i, 2])
+            raise ValueError("illegal action at step %d for env %d (rank %d, vertex %d, exploratory %d, nodes %d)"
+                             % (t, i, int(self.rank[t, i]), int(self.vert[t, i]), int(self.expl[t, i]), nodes))
         ranks = self.rank.cpu().numpy().astype(np.int64)
         verts = self.vert.cpu().numpy().astype(np.int64)
         expl = self.expl.cpu().numpy().astype(bool)

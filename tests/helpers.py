@@ -452,9 +452,11 @@ class QnetCases:
         assert o["ok"], "c_in %d hidden %d mode %d: %s" % (c_in, hidden, mode, o["text"])
         return o
 
+    CONST, CONST_SPLIT = 5e-6, 8e-6        # the absolute floor under 3 x the fp32 oracle's own distance: exact fp32, f16x3
+
     @staticmethod
     def check(tag, o, q, out_v, grads, c_in, mode, split):
-        const = 8e-6 if split else 5e-6
+        const = QnetCases.CONST_SPLIT if split else QnetCases.CONST
         eq = abs_bound(tag, "Q", q, o["q32"], o["q64"], const)
         ev = abs_bound(tag, "out_v", out_v, o["v32"], o["v64"], const) if mode == 1 else None
         names = [k for k, _ in qnet_params(o["ref"])]
@@ -883,3 +885,84 @@ class TdCases:
         o = self._oracles[(key, hidden)]
         assert o["ok"], "%s hidden %d: %s" % (key, hidden, o["text"])
         return o
+
+
+# ---- the self-play acting path at the published widths (tests/test_gpu_acting_path.py) -------------------------------------------
+
+# shape -> (board size, body layers, hidden); two head layers.  L: the published GNN-L (123-row start graphs: all eight waves own
+# rows, 5 padding rows; NT 7 with two pad columns); S: GNN-S (NT 3 with pad columns, 51 rows: waves 4-7 own none); W: 146 rows, the
+# layer-major kernels over a capacity-sized target with clear_tail
+ACTING_SHAPES = {"L": (11, 15, 110), "S": (7, 10, 35), "W": (12, 3, 110)}
+ACTING_ENVS = 6
+
+
+def acting_script(hexref, size, odd, recorded=None, k=ACTING_ENVS, max_plies=400):
+    """A script of legal random moves that brings ``k`` lock-stepped envs from the start position to ``k`` DIFFERENT node counts
+    with at least one env auto-reset on the way, found on the C env oracle alone: per seed (``recorded`` first, then 0, 1, ..) every
+    env plays ``default_rng(seed)``'s choice among its legal vertices, and the script ends at the first ply count of the wanted
+    parity (even: the maker is to move) at which both properties hold.  Returns dict(seed, moves [plies][k], ref = the oracle
+    manager at the end, reset [k] = which envs were reset)."""
+    for seed in ([] if recorded is None else [recorded]) + list(range(64)):
+        ref = hexref.RefEnvManager(k, size)
+        ref.reset()
+        rng = np.random.default_rng(seed)
+        moves, reset = [], np.zeros(k, dtype=bool)
+        for ply in range(1, max_plies + 1):
+            acts = [int(v[rng.integers(len(v))]) for v in ref.get_valid_actions()]
+            _, _, dones, _ = ref.step(acts)
+            moves.append(acts)
+            reset |= dones
+            nodes = [e.num_vertices() for e in ref.envs]
+            if ply % 2 == int(odd) and reset.any() and len(set(nodes)) == k and min(nodes) >= 4:
+                return dict(seed=seed, moves=moves, ref=ref, reset=reset)
+    raise AssertionError("Hex-%d: no move script below seed 64 gives %d different graph sizes and a reset env" % (size, k))
+
+
+def oracle_batch(games):
+    """The oracle's own observations of ``games`` (RefGame), collated: (x, edge_index, batch, ptr, backmap) as CPU tensors."""
+    obs = [g.observe() for g in games]
+    offs = np.concatenate([[0], np.cumsum([o[0].shape[0] for o in obs])]).astype(np.int64)
+    return (torch.from_numpy(np.concatenate([o[0] for o in obs])),
+            torch.from_numpy(np.concatenate([o[1] + off for o, off in zip(obs, offs[:-1])], 1)),
+            torch.from_numpy(np.repeat(np.arange(len(obs)), np.diff(offs))), torch.from_numpy(offs),
+            torch.from_numpy(np.concatenate([o[2] for o in obs])))
+
+
+def graph_spreads(a, ptr):
+    """max - min of ``a`` over the non-terminal rows of every graph."""
+    p = [int(v) for v in ptr]
+    return [(a[p[g] + 2:p[g + 1]].max() - a[p[g] + 2:p[g + 1]].min()).item() for g in range(len(p) - 1)]
+
+
+def acting_oracle(body, hidden, batch, maker, recorded=None, head=2, need_margin=True):
+    """Advantages (``advantages_only``: 2 tanh(a) per node) of the sharpened ``modern_two_headed`` oracle on ``batch`` in float64
+    and fp32, at the first weight seed below SEEDS (``recorded`` first; the conditions are evaluated there as anywhere) at which
+    the float64 oracle alone has no ReLU input within MARGIN of zero (relative to its tensor's rms) and an advantage spread of at
+    least 0.5 over the non-terminal rows of every graph.  ``need_margin=False`` (a batch on which a full scan found no seed
+    below SEEDS with that margin: the caller records the scan) takes the first seed that meets the spread condition and reports
+    the margin it has."""
+    import copy
+    from oracle.model_ref import get_pre_defined_ref
+    x, ei, bv, ptr = batch[:4]
+    assert bool((x[:, 2] == (1.0 if maker else 0.0)).all()), "the batch's side flag"
+    x64 = x.double()
+    for seed in ([] if recorded is None else [recorded]) + list(range(SEEDS)):
+        torch.manual_seed(seed)
+        ref = sharpen_(get_pre_defined_ref("modern_two_headed", model_args(body, hidden, head)))
+        ref64 = copy.deepcopy(ref).double()
+        out = []
+        margin = model_relu_margin(ref64, maker, lambda: out.append(ref64(x64, ei, bv, ptr, advantages_only=True).reshape(-1)))
+        if need_margin and margin < MARGIN:
+            continue
+        spread = min(graph_spreads(out[0], ptr))
+        if spread >= 0.5:
+            break
+    else:
+        raise AssertionError("%d + %d layers, hidden %d, %d rows: no weight seed below %d meets the oracle conditions"
+                             % (body, head, hidden, x.shape[0], SEEDS))
+    with torch.no_grad():
+        a32 = ref(x, ei, bv, ptr, advantages_only=True).reshape(-1)
+    text = "smallest |ReLU input| / rms %.3g (%s), smallest advantage spread of a graph %.3g (>= 0.5)" \
+           % (margin, ">= 2^-16" if need_margin else "no condition", spread)
+    return dict(ref=ref, ref64=ref64, seed=seed, ok=(margin >= MARGIN or not need_margin) and spread >= 0.5, text=text, margin=margin,
+                a64=out[0].detach(), a32=a32)

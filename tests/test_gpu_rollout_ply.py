@@ -291,6 +291,19 @@ def test_no_playable_vertex_and_missing_schedule_words():
         assert torch.equal(P.rm, rm) and torch.equal(P.rb, rb)
     assert torch.equal(B.snap_adj, adj) and torch.equal(B.snap_alive, alive)
 
+    # the same boards under DeviceRollout, both ply forms: run_end says which kind of illegal action it was (rank -1: the graph
+    # had nothing to pick from, or no finite advantage), with the env's graph size at that step
+    from gnn_hex_amd.multi_env_manager import DeviceRollout
+    mgr_c = _manager(k, 5)
+    st = mgr_c._state_tensors()
+    st.update(adj=adj, alive=alive, mt=torch.ones(k, dtype=torch.int32, device=DEV), tm=tm, rm=rm, rb=rb,
+              sizes=np.array([[2, 0]] * k, dtype=np.int64), onturn="m")
+    mgr_c._restore_state_tensors(st)
+    for e in (0.0, EpsSchedule(0.0, 0.0, 0)):
+        ro = DeviceRollout(mgr_c, _model(3, 16), steps=2, eps=e, graph=False)
+        with pytest.raises(ValueError, match=r"^illegal action at step 0 for env 0 \(rank -1, vertex -1, exploratory 0, nodes 2\)$"):
+            ro.run()
+
     # a missing schedule block / frame counter (and every other required pointer) is refused on the host: nothing is launched
     fresh = _Ply(mgr_b)
     for field in ("sched", "frames", "gptr", "q", "backmap", "u", "action_vertex", "action_rank", "exploratory", "result",

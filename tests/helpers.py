@@ -966,3 +966,331 @@ def acting_oracle(body, hidden, batch, maker, recorded=None, head=2, need_margin
            % (margin, ">= 2^-16" if need_margin else "no condition", spread)
     return dict(ref=ref, ref64=ref64, seed=seed, ok=(margin >= MARGIN or not need_margin) and spread >= 0.5, text=text, margin=margin,
                 a64=out[0].detach(), a32=a32)
+
+
+# ---- the stand-alone head tails (tests/test_gpu_head_tail.py) and the HexAra head kernels (tests/test_gpu_hexara_kernels.py) ----
+
+# rows per graph of the "full" batch: both sides of the 16- and 32-row unrolled steps of the two row phases (row + 14 < r1,
+# row + 30 < r1), of the per-row strides 64 and 256, and of the 1024 rows head_bwd_kernel keeps in LDS
+HEAD_ROWS = [1, 2, 3, 15, 16, 17, 30, 31, 32, 33, 34, 47, 48, 49, 63, 64, 65, 66, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025, 1300]
+HEAD_WIDTHS = [2, 3, 16, 35, 62, 63, 64, 65, 66, 110, 127, 128]       # H / 2 = 1, 31, 32, 33, 64; odd H; padded width = H
+HEAD_WIDE = 144                                                         # the same calls reach wide.hip
+HEAD_MODE_WIDTHS = (35, 66, 128)                                        # all five modes run here
+HEAD_NAMES = {"mlp": ["lin_w", "lin_b", "v0_w", "v0_b", "v1_w", "v1_b"], "linear": ["lin_w", "lin_b", "val_w", "val_b"]}
+HEAD_TOP = 8.0                                                          # above every |N(0, 1)| draw of these batches (asserted)
+
+
+def head_sizes(name):
+    """Rows per graph: "full" = HEAD_ROWS in a fixed shuffled order with an empty graph in the middle and one at the end; "row1" and
+    "rows1025" = one graph."""
+    if name == "row1":
+        return [1]
+    if name == "rows1025":
+        return [1025]
+    assert name == "full", name
+    sizes = [int(v) for v in np.random.default_rng(11).permutation(HEAD_ROWS)]
+    assert sizes != sorted(sizes) and sizes != sorted(sizes, reverse=True)
+    return sizes[:len(sizes) // 2] + [0] + sizes[len(sizes) // 2:] + [0]
+
+
+def tie_rows(cnt, g):
+    """Offsets (lo, hi) of the two rows of a graph that hold column 1's maximum in the "ties" family: opposite row parities, the
+    lower one in the odd row phase for even g and in the even phase for odd g; hi is the last row of its parity."""
+    if cnt < 4:
+        return 0, 1
+    if g % 2 == 0:
+        return 1, (cnt - 1) & ~1
+    return 0, cnt - 1 if (cnt - 1) % 2 == 1 else cnt - 2
+
+
+def head_inputs(name, hidden, family):
+    """dict(sizes, ptr, batch, b, h [n, hidden], r1 [n], r2 [b], sel): family "randn": h ~ N(0, 1); "ties": h = relu(N(0, 1)) (about
+    half the entries exactly 0: min ties are the norm, as behind a ReLU layer), column 0 constant over every graph, column 1 equal
+    to its maximum HEAD_TOP in exactly the two rows ``tie_rows`` of every graph with two or more rows, column 2 equal to HEAD_TOP in
+    rows 1021 and 1024 of every graph above 1024 rows.  r1, r2 ~ U(-1, 1) weight the outputs in the loss; ``sel`` = one row of every
+    non-empty graph (``one_row_per_graph`` on the pointer without its empty graphs)."""
+    sizes = head_sizes(name)
+    ptr = torch.tensor([0] + list(np.cumsum(sizes)), dtype=torch.long)
+    b, n = len(sizes), int(ptr[-1])
+    batch = torch.repeat_interleave(torch.arange(b), torch.tensor(sizes))
+    gen = torch.Generator().manual_seed((hidden * 7919 + n) * 2 + (family == "ties"))
+    h = torch.randn(n, hidden, generator=gen)
+    assert float(h.abs().max()) < HEAD_TOP
+    if family == "ties":
+        assert hidden >= 4
+        h = torch.relu(h)
+        for g, cnt in enumerate(sizes):
+            r0 = int(ptr[g])
+            if cnt == 0:
+                continue
+            h[r0:r0 + cnt, 0] = 0.25 + 0.125 * (g % 5)
+            if cnt >= 2:
+                lo, hi = tie_rows(cnt, g)
+                assert lo < hi < cnt and (lo + hi) % 2 == 1
+                h[r0 + lo, 1] = h[r0 + hi, 1] = HEAD_TOP
+            if cnt > 1024:
+                h[r0 + 1021, 2] = h[r0 + 1024, 2] = HEAD_TOP
+    else:
+        assert family == "randn", family
+    r1, r2 = torch.rand(n, generator=gen) * 2 - 1, torch.rand(b, generator=gen) * 2 - 1
+    sel, _ = one_row_per_graph(torch.unique_consecutive(ptr))
+    return dict(sizes=sizes, ptr=ptr, batch=batch, b=b, n=n, h=h, r1=r1, r2=r2, sel=sel)
+
+
+def head_modules(kind, hidden, seed, vscale=0.02):
+    """(advantage Linear(H, 1), value head) at torch's default init under manual_seed(seed): kind "mlp" -> MLPRef(H / 2, 1, 4 H, 1)
+    with its first layer scaled by ``vscale`` (``sharpen_``: tanh(v) must not saturate on sum-pooled inputs of a thousand rows),
+    "linear" -> Linear(H, 1)."""
+    from oracle.model_ref import MLPRef
+    torch.manual_seed(seed)
+    lin = torch.nn.Linear(hidden, 1)
+    if kind == "mlp":
+        val = MLPRef(hidden // 2, 1, 4 * hidden, 1)
+        with torch.no_grad():
+            val.layers[0].weight.mul_(vscale)
+    else:
+        assert kind == "linear", kind
+        val = torch.nn.Linear(hidden, 1)
+    return lin, val
+
+
+def head_params(lin, val):
+    """Parameters in the order of ops.HeadTailFn / ops.HeadLinearTailFn (HEAD_NAMES)."""
+    return [lin.weight, lin.bias] + [p for layer in getattr(val, "layers", [val]) for p in (layer.weight, layer.bias)]
+
+
+def head_pooled(h, batch, b, val):
+    """What the value head reads: [sum | max | min | mean] over every graph's rows for the MLP, the mean alone for the Linear; an
+    empty graph pools to zeros, max / min send their gradient to the first row that attains them (scatter_ref)."""
+    from oracle.model_ref import scatter_ref
+    aggr = ("sum", "max", "min", "mean") if hasattr(val, "layers") else ("mean",)
+    return torch.cat([scatter_ref(h, batch, dim_size=b, reduce=a) for a in aggr], dim=1)
+
+
+def head_tail_ref(h, batch, b, mode, lin, val):
+    """HeadNetwork.forward behind its SAGE layers (advantage linear, pooling, value head) and DuellingTwoHeaded's combine as one
+    torch expression.  Returns (q [n], out_v [b] or None): mode 0 Q; 1 (A - mean A, tanh(v)); 2 2 tanh(a); 3 raw (a, v); 4 raw a."""
+    from oracle.model_ref import scatter_ref
+    a = lin(h).reshape(-1)
+    if mode == 4:
+        return a, None
+    t = 2 * torch.tanh(a)
+    if mode == 2:
+        return t, None
+    v = val(head_pooled(h, batch, b, val)).reshape(-1)
+    if mode == 3:
+        return a, v
+    centred = t - scatter_ref(t, batch, dim_size=b, reduce="mean").index_select(0, batch)
+    if mode == 1:
+        return centred, torch.tanh(v)
+    return torch.tanh(v).index_select(0, batch) + centred, None
+
+
+def head_loss(q, out_v, r1, r2):
+    """sum(q * R1) + sum(out_v * R2): separable, so every row and every graph has a gradient of its own."""
+    loss = (q * r1).sum()
+    return loss if out_v is None else loss + (out_v * r2).sum()
+
+
+def head_ref_run(lin, val, h, batch, b, mode, r1, r2):
+    ps = head_params(lin, val)
+    for p in ps:
+        p.grad = None
+    h = h.detach().clone().requires_grad_(True)
+    q, v = head_tail_ref(h, batch, b, mode, lin, val)
+    head_loss(q, v, r1, r2).backward()
+    return dict(q=q.detach(), v=None if v is None else v.detach(), dh=h.grad.detach().clone(),
+                grads=[None if p.grad is None else p.grad.detach().clone() for p in ps])
+
+
+def head_dev_run(kind, ps, h, gptr, b, hidden, mode, r1, r2):
+    """The same step through ops.HeadTailFn / ops.HeadLinearTailFn; ``ps`` (CPU tensors in HEAD_NAMES order), h, r1, r2 on the CPU."""
+    from gnn_hex_amd import ops
+    leaves = [p.detach().cuda().clone().requires_grad_(True) for p in ps]
+    hd = h.cuda().requires_grad_(True)
+    out = (ops.HeadTailFn if kind == "mlp" else ops.HeadLinearTailFn).apply(hd, gptr, b, hidden, mode, *leaves)
+    q, v = (out[1], out[0]) if mode in (1, 3) else (out, None)
+    head_loss(q, v, r1.cuda(), r2.cuda()).backward()
+    torch.cuda.synchronize()
+    return dict(q=q.detach(), v=None if v is None else v.detach(), dh=hd.grad, grads=[p.grad for p in leaves])
+
+
+def head_same_bits(tag, a, b):
+    for k in ("q", "v", "dh"):
+        assert (a[k] is None) == (b[k] is None) and (a[k] is None or torch.equal(a[k], b[k])), "%s: %s differs" % (tag, k)
+    for i, (ga, gb) in enumerate(zip(a["grads"], b["grads"])):
+        assert (ga is None) == (gb is None) and (ga is None or torch.equal(ga, gb)), "%s: gradient %d differs" % (tag, i)
+
+
+class HeadCases:
+    """The stand-alone head-tail cases: per (kind, batch, hidden, family) the first weight seed below SEEDS at which, in float64 on
+    the CPU, every pre-activation of the value MLP's ReLU is at least MARGIN x its tensor's rms away from 0 (the Linear value head
+    has no ReLU: seed 0), and per (mode, loss form) the float64 and fp32 results of the torch expression -- once per session.
+    Loss forms: "dense" R1 ~ U(-1, 1) on every row; "sel" R1 non-zero on one row per graph (the shape of a TD-loss gradient)."""
+
+    def __init__(self):
+        self._inputs, self._seeds, self._oracles = {}, {}, {}
+
+    def inputs(self, name, hidden, family):
+        key = (name, hidden, family)
+        if key not in self._inputs:
+            self._inputs[key] = head_inputs(name, hidden, family)
+        return self._inputs[key]
+
+    def margin(self, kind, name, hidden, family, seed):
+        if kind == "linear":
+            return 1.0
+        inp = self.inputs(name, hidden, family)
+        _, val = head_modules(kind, hidden, seed)
+        val = val.double()
+        if "pooled64" not in inp:
+            inp["pooled64"] = head_pooled(inp["h"].double(), inp["batch"], inp["b"], val)
+        with torch.no_grad():
+            return relu_margin_of([val.layers[0](inp["pooled64"])])
+
+    def seed(self, kind, name, hidden, family):
+        key = (kind, name, hidden, family)
+        if key not in self._seeds:
+            for seed in range(SEEDS):
+                margin = self.margin(kind, name, hidden, family, seed)
+                if margin >= MARGIN:
+                    break
+            else:
+                raise AssertionError("%s %s hidden %d %s: no weight seed below %d keeps the value MLP's ReLU inputs clear of zero"
+                                     % (kind, name, hidden, family, SEEDS))
+            self._seeds[key] = (seed, margin)
+        return self._seeds[key]
+
+    def r1(self, inp, loss):
+        if loss == "dense":
+            return inp["r1"]
+        assert loss == "sel", loss
+        r1 = torch.zeros_like(inp["r1"])
+        r1[inp["sel"]] = inp["r1"][inp["sel"]]
+        assert int((r1 != 0).sum()) == sum(1 for s in inp["sizes"] if s > 0)
+        return r1
+
+    def oracle(self, kind, name, hidden, family, mode, loss="dense"):
+        import copy
+        key = (kind, name, hidden, family, mode, loss)
+        if key not in self._oracles:
+            seed, margin = self.seed(kind, name, hidden, family)
+            inp = self.inputs(name, hidden, family)
+            lin, val = head_modules(kind, hidden, seed)
+            r1 = self.r1(inp, loss)
+            r64 = head_ref_run(copy.deepcopy(lin).double(), copy.deepcopy(val).double(), inp["h"].double(), inp["batch"], inp["b"],
+                               mode, r1.double(), inp["r2"].double())
+            r32 = head_ref_run(lin, val, inp["h"], inp["batch"], inp["b"], mode, r1, inp["r2"])
+            print("oracle head %s %s hidden %d %s mode %d %s: weight seed %d, smallest |ReLU input| / rms %.3g (>= 2^-16)"
+                  % (kind, name, hidden, family, mode, loss, seed, margin))
+            self._oracles[key] = dict(inp=inp, r1=r1, seed=seed, margin=margin, r64=r64, r32=r32,
+                                      ps=[p.detach().clone() for p in head_params(lin, val)])
+        o = self._oracles[key]
+        assert o["margin"] >= MARGIN
+        return o
+
+    def run(self, kind, name, hidden, family, mode, loss="dense"):
+        o = self.oracle(kind, name, hidden, family, mode, loss)
+        inp = o["inp"]
+        return o, head_dev_run(kind, o["ps"], inp["h"], inp["ptr"].to(torch.int32).cuda(), inp["b"], hidden, mode, o["r1"], inp["r2"])
+
+    @staticmethod
+    def check(tag, kind, o, res, mode):
+        """The rule of tests/test_gpu_wide_parity.py's stand-alone head case: q and out_v within max(3 x the fp32 expression's own,
+        5e-6) of float64, dh and every parameter gradient within max(3 x its own, 2e-3) in relative norm; no value-head gradient
+        in modes 2 and 4.  Returns {name: (kernel's figure, the fp32 expression's)}."""
+        r64, r32 = o["r64"], o["r32"]
+        assert tuple(res["q"].shape) == tuple(r64["q"].shape)
+        figs = {"q": abs_bound(tag, "q", res["q"], r32["q"], r64["q"], QnetCases.CONST)}
+        assert (res["v"] is None) == (mode not in (1, 3))
+        if res["v"] is not None:
+            assert tuple(res["v"].shape) == tuple(r64["v"].shape)
+            figs["out_v"] = abs_bound(tag, "out_v", res["v"], r32["v"], r64["v"], QnetCases.CONST)
+        assert tuple(res["dh"].shape) == tuple(r64["dh"].shape)
+        figs["dh"] = rel_bound(tag, "dh", res["dh"], r32["dh"], r64["dh"])
+        for name, g, a32, a64 in zip(HEAD_NAMES[kind], res["grads"], r32["grads"], r64["grads"]):
+            if a64 is None:
+                assert mode in (2, 4) and name[0] == "v", name
+                assert g is None or float(g.abs().max()) == 0.0, "%s: %s has a gradient in mode %d" % (tag, name, mode)
+                continue
+            assert g is not None and tuple(g.shape) == tuple(a64.shape), name
+            figs[name] = rel_bound(tag, name, g, a32, a64)
+        print("%s: " % tag + "; ".join("%s %.3g (fp32 %.3g)" % ((k,) + v) for k, v in figs.items()))
+        return figs
+
+
+def sage_scalar_ref(h, ei, wl, bl, wr):
+    """SAGEConv(H, 1) as scalars: out_i = b + h_i . w_r + mean over the in-edges (j -> i) of h_j . w_l (duplicates counted, a row
+    without in-edges gets 0 for the mean)."""
+    from oracle.model_ref import scatter_ref
+    s = h @ wl.reshape(-1)
+    return bl.reshape(()) + h @ wr.reshape(-1) + scatter_ref(s.index_select(0, ei[0]), ei[1], dim_size=h.shape[0], reduce="mean")
+
+
+def policy_ref(pi_raw, should_swap, x, ptr, swap_allowed):
+    """The output surgery and log-softmax of SageTorchScriptRef.forward (oracle/hexara_ref.py) on given logits: the two terminal
+    rows of every graph dropped; with ``swap_allowed`` the graph's swap logit appended where feature 2 is set -- probed on the
+    graph's LAST row for every graph but the last one and on the FIRST row of the last graph; log-softmax per segment.
+    Returns (pi [live], output_graph_indices [live], output_batch_ptr [b + 1])."""
+    from oracle.hexara_ref import scatter_log_softmax_ref
+    nb = ptr.numel() - 1
+    pieces, seg_ids, starts = [], [], [0]
+    for gi in range(nb):
+        lo, hi = int(ptr[gi]), int(ptr[gi + 1])
+        seg = pi_raw[lo + 2:hi]
+        if swap_allowed:
+            probe_row = hi - 1 if gi < nb - 1 else lo
+            if bool(x[probe_row, 2] != 0):
+                seg = torch.cat((seg, should_swap[gi:gi + 1]))
+        pieces.append(seg)
+        seg_ids.append(torch.full((seg.numel(),), gi, dtype=torch.long))
+        starts.append(starts[-1] + seg.numel())
+    gi = torch.cat(seg_ids)
+    return scatter_log_softmax_ref(torch.cat(pieces), gi), gi, torch.tensor(starts, dtype=torch.long)
+
+
+# graph rows -> 1, 2, 128, 255..258, 512, 513 and 698 entries in front of the swap slot: both sides of policy_lsm_*_kernel's stride 256
+POLICY_ROWS = [3, 4, 130, 257, 258, 259, 260, 514, 515, 700]
+POLICY_BATCHES = {"rows": POLICY_ROWS, "many": [3] * 300, "one": [259]}
+
+
+def policy_inputs(name, last, family):
+    """dict(x [n, 3], ptr, pi_raw [n], should_swap [b], r): feature 2 is set per ROW -- graph g: g % 4 == 0 on its first row only,
+    1 on its last row only, 2 on no row, 3 on every row; the LAST graph on its first row only (``last`` = "first": the first-row
+    rule gives a slot, the last-row rule would not) or on its last row only ("last": the other way round).  family "unit":
+    logits ~ N(0, 1); "spread": U(-30, 30), where nothing but the subtracted maximum keeps exp() in range.  r ~ U(-1, 1) [n]
+    weights the live outputs in the loss (its first entries)."""
+    sizes = POLICY_BATCHES[name]
+    ptr = torch.tensor([0] + list(np.cumsum(sizes)), dtype=torch.long)
+    b, n = len(sizes), int(ptr[-1])
+    gen = torch.Generator().manual_seed(n * 4 + 2 * (last == "last") + (family == "spread"))
+    x = torch.zeros(n, 3)
+    x[:, 0] = torch.randint(0, 9, (n,), generator=gen).float()
+    for g in range(b):
+        lo, hi = int(ptr[g]), int(ptr[g + 1])
+        x[lo:lo + 2, 1] = 1.0
+        kind = g % 4 if g < b - 1 else {"first": 0, "last": 1}[last]
+        if kind == 0:
+            x[lo, 2] = 1.0
+        elif kind == 1:
+            x[hi - 1, 2] = 1.0
+        elif kind == 3:
+            x[lo:hi, 2] = 1.0
+    if family == "spread":
+        pi_raw, ss = (torch.rand(n, generator=gen) * 2 - 1) * 30, (torch.rand(b, generator=gen) * 2 - 1) * 30
+    else:
+        assert family == "unit", family
+        pi_raw, ss = torch.randn(n, generator=gen), torch.randn(b, generator=gen)
+    return dict(x=x, ptr=ptr, b=b, n=n, pi_raw=pi_raw, should_swap=ss, r=torch.rand(n, generator=gen) * 2 - 1)
+
+
+def policy_ref_run(inp, swap_allowed, dtype):
+    """Forward and backward of sum(pi * r[:live]) through ``policy_ref``: dict(pi, gi, ptr, d_raw [n], d_ss [b] or None)."""
+    raw = inp["pi_raw"].to(dtype).clone().requires_grad_(True)
+    ss = inp["should_swap"].to(dtype).clone().requires_grad_(True)
+    pi, gi, optr = policy_ref(raw, ss, inp["x"], inp["ptr"], swap_allowed)
+    (pi * inp["r"][:pi.numel()].to(dtype)).sum().backward()
+    d_ss = None
+    if swap_allowed:
+        d_ss = torch.zeros_like(ss) if ss.grad is None else ss.grad.detach().clone()
+    return dict(pi=pi.detach(), gi=gi, ptr=optr, d_raw=raw.grad.detach().clone(), d_ss=d_ss)

@@ -2,7 +2,8 @@
 
 ``models.get_pre_defined("modern_two_headed", args)`` mirrors ``GN0.models.get_pre_defined``;
 ``multi_env_manager.Env_manager`` mirrors ``graph_game.multi_env_manager.Env_manager``;
-``arena.Elo_handler`` mirrors ``GN0.RainbowDQN.evaluate_elo.Elo_handler`` (matches played on the device).
+``arena.Elo_handler`` mirrors ``GN0.RainbowDQN.evaluate_elo.Elo_handler`` (matches played on the device);
+``positions`` sets up positions from stone lists and puts the model's output back on the board (the long-range task).
 Everything numeric runs in libhexgnn.so (hand-written HIP kernels for gfx950, C ABI in
 include/hexgnn.h); importing this package does not load the library, calling into it does and
 fails loudly when it is missing.

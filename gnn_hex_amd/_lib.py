@@ -64,6 +64,26 @@ class RolloutCall(C.Structure):
                 + _fields(vp, "gptr q backmap u sched frames action_vertex action_rank exploratory result adj_out alive_out eps_out"))
 
 
+class SetupCall(C.Structure):
+    """``hexgnn_setup_call`` of include/hexgnn.h, field for field (tests/test_positions_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "max_stones from_start maker_turn_start maker_turn_after")
+                + _fields(vp, "stones count result applied adj_out alive_out side_out sizes_out"))
+
+
+STONE_COLOURS = {"b": 0, "m": 1, "turn": 2}      # HEXGNN_STONE's colour field
+
+
+def stone(vertex: int, colour, remove: bool = False) -> int:
+    """``HEXGNN_STONE(vertex, colour, remove)``; ``colour`` is "b", "m" or "turn" (or the field's number 0 / 1 / 2)."""
+    c = STONE_COLOURS.get(colour) if isinstance(colour, str) else (int(colour) if colour in (0, 1, 2) else None)
+    if c is None:
+        raise ValueError("a stone's colour is \"m\", \"b\" or \"turn\", not %r" % (colour,))
+    v = int(vertex)
+    if not 0 <= v < 65536:
+        raise ValueError("a stone's vertex id is 0 .. 65535, not %d" % v)
+    return v | (c << 16) | (int(bool(remove)) << 18)
+
+
 _SIGS = {
     "hexgnn_abi_version": (ci, []),
     "hexgnn_strerror": (C.c_char_p, [ci]),
@@ -168,6 +188,8 @@ _SIGS = {
     "hexgnn_arena_ply": (ci, [vp, vp, vp, vp, ci, C.c_float, vp, vp, ci, vp, vp, vp, vp, vp]),
     "hexgnn_rollout_ply": (ci, [vp, C.POINTER(RolloutCall), vp]),
     "hexgnn_frames_add": (ci, [vp, C.c_int64, vp]),
+    "hexgnn_env_setup": (ci, [vp, C.POINTER(SetupCall), vp]),
+    "hexgnn_board_values": (ci, [ci, ci, vp, vp, vp, C.c_float, vp, vp, vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_forward_backward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

@@ -5,6 +5,8 @@
 // (GN0/util/convert_graph.py:60-130, torch_geometric Batch.from_data_list): reset / make_move /
 // dead_and_captured / who_won / observe for num_envs lock-stepped games, emitting the batched observation
 // (features, edge_index, backmap, ptr, and the sorted CSR the model kernels consume) directly in device memory.
+// env_setup_kernel applies a list of stones per env in one launch, forced colours included (make_move(v, force_color=...),
+// py:89-93,110-111, as GN0/tests/test_models_on_long_range_task.py:20-30 fills its boards): a latency kernel, never timed.
 //
 // Data layout.  Per env: a symmetric adjacency BIT MATRIX adj[nv][W] (nv = size^2+2 vertices with their original
 // ids, W = ceil(nv/64) 64-bit words), alive[nv], side to move, move count.  A step loads the env's matrix into LDS
@@ -665,6 +667,91 @@ __global__ __launch_bounds__(64) void rollout_ply_kernel(EnvDev d, RolloutPly a)
 
 __global__ void frames_add_kernel(long long* frames, long long delta) { frames[0] += delta; }
 
+// A list of stones per env in one launch (include/hexgnn.h: hexgnn_env_setup): make_move(v, force_color, remove_dead_and_captured)
+// stone by stone on the one LDS copy of the game, every stone through play_vertex.  A coloured stone plays for its colour and
+// leaves the side flag and the move count alone; colour 2 is the move of the side on turn.
+struct SetupArgs {
+    int L, from_start, maker_turn_start, maker_turn_after;
+    const int* stones;           // [num_envs][L]
+    const int* count;            // [num_envs]
+    int* result;                 // [num_envs][5]
+    int* applied;                // [num_envs]
+    uint64_t* adj_out;           // [num_envs][L][nv][W] or null (then all four are)
+    uint8_t* alive_out;          // [num_envs][L][nv]
+    uint8_t* side_out;           // [num_envs][L]
+    int* sizes_out;              // [num_envs][L][2]
+};
+
+template <int WT>
+__global__ __launch_bounds__(64) void env_setup_kernel(EnvDev d, SetupArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int env = blockIdx.x, lane = threadIdx.x;
+    GameT<WT> g;
+    load_game(g, d, env, lds);
+    short* rm = d.resp_maker + (size_t)env * d.nv;
+    short* rb = d.resp_breaker + (size_t)env * d.nv;
+    int mt = d.maker_turn[env], moves = d.total_moves[env];
+    int winner = -1;
+    if (a.from_start) {
+        reset_game_lds(g, d);
+        for (int i = lane; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
+        mt = a.maker_turn_start;
+        moves = 0;
+    } else {
+        winner = g.who_won();                                 // stones on top of a decided position are error 2
+    }
+    int cnt = a.count[env];
+    cnt = cnt < 0 ? 0 : (cnt > a.L ? a.L : cnt);
+    const int* list = a.stones + (size_t)env * a.L;
+    int err = 0, done = 0;                                    // done: stones applied; on error the offending stone
+    for (int j = 0; j < cnt; ++j) {
+        g.sync();
+        const int s = list[j];
+        const int v = s & 0xffff, colour = (s >> 16) & 3, remove_dc = (s >> 18) & 1;
+        if (winner >= 0) { err = 2; break; }
+        if (((unsigned)s >> 19) != 0u || colour == 3 || v < 2 || v >= d.nv || !g.alive[v]) { err = 1; break; }
+        int side = colour == 2 ? mt : colour;
+        winner = play_vertex(g, v, side, remove_dc != 0, rm, rb);
+        if (colour == 2) { mt = !mt; ++moves; }
+        ++done;
+        if (a.adj_out) {                                      // the position after stone j (none once the game is decided)
+            const size_t slot = (size_t)env * a.L + j;
+            int na = 0, ne = 0;
+            if (winner < 0) {
+                count_game(g, &na, &ne);
+                uint64_t* sa = a.adj_out + slot * d.nv * d.W;
+                for (int i = lane; i < d.nv * d.W; i += 64) sa[i] = g.adj[i];
+                for (int i = lane; i < d.nv; i += 64) a.alive_out[slot * d.nv + i] = g.alive[i];
+            }
+            if (lane == 0) { a.side_out[slot] = (uint8_t)mt; a.sizes_out[2 * slot] = na; a.sizes_out[2 * slot + 1] = ne; }
+        }
+    }
+    if (err) {                                                // the env goes back to the start position
+        reset_game_lds(g, d);
+        for (int i = lane; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
+        mt = a.maker_turn_start;
+        moves = 0;
+        winner = -1;
+    } else if (a.maker_turn_after >= 0) {
+        mt = a.maker_turn_after;
+    }
+    if (a.adj_out) {                                          // slots that hold no position
+        for (int j = done + lane; j < a.L; j += 64) {
+            const size_t slot = (size_t)env * a.L + j;
+            a.side_out[slot] = (uint8_t)mt; a.sizes_out[2 * slot] = 0; a.sizes_out[2 * slot + 1] = 0;
+        }
+    }
+    int na, ne;
+    count_game(g, &na, &ne);
+    store_game(g, d, env);
+    if (lane == 0) {
+        d.maker_turn[env] = mt; d.total_moves[env] = moves;
+        int* res = a.result + 5 * env;
+        res[0] = winner; res[1] = moves; res[2] = na; res[3] = ne; res[4] = err;
+        a.applied[env] = done;
+    }
+}
+
 // Observation of every env into batched buffers (convert_graph.py:77-122, old_style=True; Batch.from_data_list):
 //   x [N][3] = (degree, is_terminal, maker_to_move);  backmap [N] rank -> vertex id (int64)
 //   edge_local [2][E]: per graph, first the E_g/2 edges (s > t, sorted by (s,t)) then the flipped copies, LOCAL ranks
@@ -853,6 +940,17 @@ static void launch_rollout_ply(const EnvDev& d, const RolloutPly& a, hipStream_t
     rollout_ply_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, a);
 }
 
+template <int WT>
+static void launch_env_setup(const EnvDev& d, const SetupArgs& a, hipStream_t st) {
+    static bool once = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&env_setup_kernel<WT>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        return true;
+    }();
+    (void)once;
+    env_setup_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, a);
+}
+
 }  // namespace hexgnn
 
 using namespace hexgnn;
@@ -1012,6 +1110,29 @@ int hexgnn_rollout_ply(hexgnn_env* h, const hexgnn_rollout_call* c, hexgnn_strea
         case 3: launch_rollout_ply<3>(e->d, a, st); break;
         case 4: launch_rollout_ply<4>(e->d, a, st); break;
         default: launch_rollout_ply<kMaxW>(e->d, a, st); break;
+    }
+    return check_launch();
+}
+
+int hexgnn_env_setup(hexgnn_env* h, const hexgnn_setup_call* c, hexgnn_stream_t stream_) {
+    if (!c || c->struct_bytes != sizeof(hexgnn_setup_call)) return HEXGNN_EINVAL;
+    if (!h || c->max_stones < 1 || c->maker_turn_after < -1 || c->maker_turn_after > 1) return HEXGNN_EINVAL;
+    if (!c->stones || !c->count || !c->result || !c->applied) return HEXGNN_EINVAL;
+    const int snaps = (c->adj_out != nullptr) + (c->alive_out != nullptr) + (c->side_out != nullptr) + (c->sizes_out != nullptr);
+    if (snaps != 0 && snaps != 4) return HEXGNN_EINVAL;
+    Env* e = reinterpret_cast<Env*>(h);
+    hipStream_t st = (hipStream_t)stream_;
+    SetupArgs a;
+    a.L = c->max_stones; a.from_start = c->from_start ? 1 : 0; a.maker_turn_start = c->maker_turn_start ? 1 : 0;
+    a.maker_turn_after = c->maker_turn_after;
+    a.stones = c->stones; a.count = c->count; a.result = c->result; a.applied = c->applied;
+    a.adj_out = c->adj_out; a.alive_out = c->alive_out; a.side_out = c->side_out; a.sizes_out = c->sizes_out;
+    switch (e->d.W) {          // as hexgnn_env_step: register-resident vertex sets for the common board sizes
+        case 1: launch_env_setup<1>(e->d, a, st); break;
+        case 2: launch_env_setup<2>(e->d, a, st); break;
+        case 3: launch_env_setup<3>(e->d, a, st); break;
+        case 4: launch_env_setup<4>(e->d, a, st); break;
+        default: launch_env_setup<kMaxW>(e->d, a, st); break;
     }
     return check_launch();
 }

@@ -867,6 +867,73 @@ class Env_manager:
         states = self.observe()
         return states, rewards, dones.astype(bool), infos
 
+    # ---- positions -------------------------------------------------------------------------------------
+    def _pack_stones(self, stones, counts=None):
+        """``(int32 [num_envs][L] HEXGNN_STONE rows, int32 [num_envs] counts)`` as host arrays, L >= 1."""
+        k = self.num_envs
+        if isinstance(stones, np.ndarray) or torch.is_tensor(stones):
+            arr = np.ascontiguousarray(stones.cpu().numpy() if torch.is_tensor(stones) else stones).astype(np.int32)
+            if arr.ndim != 2 or arr.shape[0] != k or arr.shape[1] < 1:
+                raise ValueError("a stone array has the shape [%d][L], L >= 1" % k)
+            cnt = np.full(k, arr.shape[1], dtype=np.int32) if counts is None else np.asarray(counts, dtype=np.int32).reshape(-1)
+            if cnt.shape[0] != k or (cnt < 0).any() or (cnt > arr.shape[1]).any():
+                raise ValueError("counts: %d entries in 0 .. %d" % (k, arr.shape[1]))
+            return arr, np.ascontiguousarray(cnt)
+        if counts is not None:
+            raise ValueError("counts go with a packed stone array")
+        rows = [list(r) for r in stones]
+        if len(rows) != k:
+            raise ValueError("expected %d stone lists" % k)
+        arr = np.zeros((k, max(1, max(len(r) for r in rows))), dtype=np.int32)
+        for i, r in enumerate(rows):
+            arr[i, :len(r)] = [_lib.stone(*s) for s in r]
+        return arr, np.asarray([len(r) for r in rows], dtype=np.int32)
+
+    def set_positions(self, stones, onturn="m", from_start=True, counts=None) -> ObsList:
+        """Put a position on every env with ONE launch (``hexgnn_env_setup``) and observe it: the reference's
+        ``make_move(v, force_color=..., remove_dead_and_captured=...)`` stone by stone
+        (GN0/tests/test_models_on_long_range_task.py:20-30).  ``stones``: per env a sequence of ``(vertex, colour)`` or
+        ``(vertex, colour, remove)`` with colour ``"m"`` / ``"b"`` (a forced stone: the side and the move count stay) or
+        ``"turn"`` (the move of the side on turn); or an int32 ``[num_envs][L]`` array of ``_lib.stone`` values with ``counts``.
+        ``from_start``: every env starts from ``Hex_game(size)``, maker to move as there; else the stones go on top of the
+        current boards.  After its last stone every env has ``onturn`` to move, and so has ``global_onturn``: the batched
+        model needs one side per batch.  ``ValueError`` names env and stone for an illegal stone (a terminal, an out-of-range
+        or dead vertex) and for a stone behind the one that decided the game -- such an env is back at the start position --
+        and is raised for a position that is decided after its last stone, which cannot be observed.  A latency path: one
+        launch and one read-back of the result record; nobody has timed it."""
+        if onturn not in ("m", "b"):
+            raise ValueError("onturn must be \"m\" or \"b\"")
+        arr, cnt = self._pack_stones(stones, counts)
+        k, dev = self.num_envs, self.device
+        st = torch.from_numpy(arr).to(dev)
+        ct = torch.from_numpy(cnt).to(dev)
+        result = torch.empty((k, 5), dtype=torch.int32, device=dev)
+        applied = torch.empty(k, dtype=torch.int32, device=dev)
+        call = _lib.SetupCall(struct_bytes=C.sizeof(_lib.SetupCall), max_stones=arr.shape[1], from_start=int(bool(from_start)),
+                              maker_turn_start=1, maker_turn_after=int(onturn == "m"), stones=st.data_ptr(), count=ct.data_ptr(),
+                              result=result.data_ptr(), applied=applied.data_ptr())
+        self._touch += 1
+        _lib.check(_lib.lib().hexgnn_env_setup(self._h, C.byref(call), ops._stream()), "hexgnn_env_setup")
+        res = result.cpu().numpy()
+        self.global_onturn = onturn
+        self._sizes = res[:, 2:4].astype(np.int64)
+        self.last_obs = None
+        if from_start:
+            self._creation_time = [time.perf_counter()] * k
+        if res[:, 4].any():
+            # an env with an error went back to the start position with the maker to move: give it everyone's side
+            _lib.check(_lib.lib().hexgnn_env_set_maker_turn(self._h, int(onturn == "m"), ops._stream()),
+                       "hexgnn_env_set_maker_turn")
+            bad = int(np.nonzero(res[:, 4])[0][0])
+            j = int(applied[bad])
+            what = ("is not a live board vertex" if res[bad, 4] == 1 else "follows the stone that decided the game")
+            raise ValueError("env %d, stone %d (vertex %d) %s" % (bad, j, int(arr[bad, j]) & 0xffff, what))
+        if (res[:, 0] >= 0).any():
+            bad = int(np.nonzero(res[:, 0] >= 0)[0][0])
+            raise ValueError("env %d: the position is decided after its last stone (%s has won) and cannot be observed"
+                             % (bad, "the maker" if res[bad, 0] == 0 else "the breaker"))
+        return self.observe()
+
     def reset(self) -> ObsList:
         L = _lib.lib()
         self.global_onturn = "m"

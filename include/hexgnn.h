@@ -836,6 +836,67 @@ int hexgnn_rollout_ply(hexgnn_env* env, const hexgnn_rollout_call* call, hexgnn_
 /* *frames += delta (one thread; frames [1] int64 on the device). */
 int hexgnn_frames_add(int64_t* frames, int64_t delta, hexgnn_stream_t stream);
 
+/* ---- position set-up and board-indexed evaluation (entry points added to ABI 7, nothing existing changes).
+ *      hexgnn_env_setup applies a LIST of stones per env in one launch, one 64-lane workgroup per env with the game in LDS as
+ *      hexgnn_env_step holds it: the reference's make_move(v, force_color=..., remove_dead_and_captured=...)
+ *      (graph_game/shannon_node_switching_game.py:80-116) called stone by stone, which is how
+ *      GN0/tests/test_models_on_long_range_task.py:20-30,68-69,89-90 fills its boards and how play_vs_model, explore_sgf_game.py
+ *      and visualize_transitions.py rebuild a position from a move list.  A latency kernel: nobody has timed it, no
+ *      performance is claimed for it and no test depends on a time.
+ *   A stone is HEXGNN_STONE(vertex, colour, remove_dc):
+ *     colour 0 ('b') / 1 ('m'): make_move(v, force_color=colour, remove_dead_and_captured=remove_dc): the side to move and the
+ *                               move count stay as they are.
+ *     colour 2:                 the move of the side on turn: the side flips and the move counts; with remove_dc = 1 exactly what
+ *                               hexgnn_env_step(remove_dead_and_captured = 1, auto_reset = 0) does.
+ *     Every stone goes through the move routine hexgnn_env_step, hexgnn_arena_ply and hexgnn_rollout_ply share.
+ *   from_start = 1: every env first becomes Hex_game(size) with maker_turn_start to move, move count 0 and empty response sets.
+ *   from_start = 0: the stones go on top of what the env holds (a decided position takes no stone: error 2 at stone 0).
+ *   maker_turn_after: -1 keeps the side the stones left, 0 / 1 sets it for every env after its last stone (a batched
+ *     observation needs one side for all graphs).
+ *   result [num_envs][5]: hexgnn_env_step's record after the last stone (feeds hexgnn_env_offsets): a winner when the last
+ *     stone decided the position -- there is no auto reset, and the residual graph of a decided game is unspecified as
+ *     hexgnn_env_step says --, the move count, nodes, directed edges, error.
+ *   applied [num_envs]: stones applied; on an error the index of the offending stone.
+ *   Errors (result[env][4]): 1 = the stone names a terminal, an out-of-range vertex or a vertex that is no longer alive (played,
+ *     or removed as dead / captured earlier in the list), or is no HEXGNN_STONE value (colour 3, bits above 18);
+ *     2 = the stone follows one that decided the position.  The response sets are written straight to global memory while the
+ *     list is applied, so an env with an error is not left untouched: it is RESET to the start position with maker_turn_start to
+ *     move (also when from_start = 0), move count 0 and empty response sets, and result describes that start position.  Other
+ *     envs of the launch are not affected.  All of this is decided by the kernel's own checks before a vertex is used.
+ *   Snapshots (optional, all four pointers or none): slot [env][j] receives the position after stone j in hexgnn_env_export's
+ *     layout, side_out the side to move there (before maker_turn_after applies), sizes_out (nodes, directed edges) -- what
+ *     hexgnn_states_observe takes.  A slot that holds no position has sizes (0, 0) and undefined boards: the slot of a stone
+ *     that decided the game, the slots from an offending stone on, and the slots behind count[env].
+ * struct_bytes is checked first; a required pointer that is NULL, max_stones < 1, a maker_turn_after outside -1..1 or one to
+ * three of the four snapshot pointers give HEXGNN_EINVAL before anything is launched. */
+#define HEXGNN_STONE(v, colour, remove_dc) ((v) | ((colour) << 16) | ((remove_dc) << 18))
+/* colour: 0 = breaker ('b'), 1 = maker ('m'), 2 = the side on turn */
+typedef struct hexgnn_setup_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_setup_call), else HEXGNN_EINVAL */
+    int max_stones;          /* L, row length of `stones`; >= 1 */
+    int from_start;
+    int maker_turn_start;    /* read when from_start == 1, and for an env that is reset after an error */
+    int maker_turn_after;
+    const int* stones;       /* [num_envs][L] HEXGNN_STONE entries */
+    const int* count;        /* [num_envs], 0..L (clamped into that range) */
+    int* result;             /* [num_envs][5] */
+    int* applied;            /* [num_envs] */
+    uint64_t* adj_out;       /* [num_envs][L][nv][words] */
+    uint8_t* alive_out;      /* [num_envs][L][nv] */
+    uint8_t* side_out;       /* [num_envs][L], 1 = maker to move */
+    int* sizes_out;          /* [num_envs][L][2] */
+} hexgnn_setup_call;
+int hexgnn_env_setup(hexgnn_env* env, const hexgnn_setup_call* call, hexgnn_stream_t stream);
+/* Q back on the board, one workgroup per graph: board[g][:] = fill, then board[g][backmap[i] - 2] = q[i] for the graph's
+ * non-terminal rows i in [gptr[g] + 2, gptr[g + 1]) -- the board_outputs vector of
+ * GN0/tests/test_models_on_long_range_task.py:47-52 and of advantage_model_to_evaluater (graph_game/hex_gui.py), which hold the
+ * fill (-5 there) on occupied cells.  best[g] (may be NULL) is the board cell of the first maximum over those rows, the
+ * torch.argmax the task takes, found with hexgnn_select_actions' comparison and tie rule (a NaN never compares greater);
+ * -1 for a graph without a non-terminal row or whose rows are all NaN.  hex_size 1..25; a backmap entry outside the board is
+ * not written.  A latency kernel as well: no performance claim. */
+int hexgnn_board_values(int b, int hex_size, const int* gptr, const float* q, const int64_t* backmap, float fill,
+                        float* board /*[b][hex_size^2]*/, int* best /*[b] or NULL*/, hexgnn_stream_t stream);
+
 /* ---- layout helpers (host tensors <-> padded layout) ---------------------------------------- */
 /* dst[n][HP] <- src[n][hidden] (row stride src_stride floats), pad columns zeroed; and back. */
 int hexgnn_pad_rows(int n, int hidden, const float* src, int src_stride, float* dst, hexgnn_stream_t stream);

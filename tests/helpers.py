@@ -193,6 +193,118 @@ def feature_batch(sizes, c_in, seed, p_edge=0.08):
             torch.tensor(ptr, dtype=torch.long))
 
 
+def reorder_graphs(x, ei, ptr, order):
+    """The collated batch with its graphs in the order ``order`` (position k holds graph order[k], as ``data.pack_order`` gives
+    it): ``(x, edge_index, batch, ptr, rows)``, rows[i] = the old row of new row i; edges stay grouped by graph, each graph's
+    edges in the order they had."""
+    p = ptr.tolist()
+    order = [int(g) for g in order]
+    assert sorted(order) == list(range(len(p) - 1))
+    rows = torch.cat([torch.arange(p[g], p[g + 1]) for g in order])
+    new_of = torch.empty_like(rows)
+    new_of[rows] = torch.arange(rows.numel())
+    eg = torch.bucketize(ei[1], ptr[1:], right=True)                    # graph of every edge
+    assert bool((eg == torch.bucketize(ei[0], ptr[1:], right=True)).all())
+    cols = torch.cat([torch.nonzero(eg == g).reshape(-1) for g in order])
+    sizes = [p[g + 1] - p[g] for g in order]
+    nptr = torch.tensor([0] + list(np.cumsum(sizes)), dtype=torch.long)
+    batch = torch.repeat_interleave(torch.arange(len(order)), torch.tensor(sizes))
+    return x[rows], new_of[ei[:, cols]], batch, nptr, rows
+
+
+# ---- graph-aligned row-block tables of the one-launch stack kernels (tests/test_gpu_block_tables.py) ---------------------------
+
+# The smallest batch with every geometric case of a table: feature_batch(TABLE_SIZES, 2, seed=102, p_edge=TABLE_P_EDGE), 392 rows.
+# head64: the 200-row graph is a 64-row head and two 68-row pieces -- three blocks, so the kernel's block_of() has a neighbour
+# that is neither blk - 1 nor blk + 1; head0: block 1 = the 72-row tail of the 200-row graph + the whole 40-row graph, block 3
+# starts with the LAST row of the cut 129-row graph, four whole graphs behind it; packed: data.pack_order's order and table.
+TABLE_SIZES = [200, 40, 129, 1, 2, 3, 17]
+TABLE_P_EDGE = 0.06
+TABLE_STARTS = {"head64": [0, 64, 132, 200, 240, 304, 369, 392], "head0": [0, 128, 240, 368, 392],
+                "packed": [0, 64, 132, 200, 264, 329, 392]}
+TABLE_ORDER = [0, 2, 1, 6, 5, 4, 3]                                    # pack_order(TABLE_SIZES)[0]
+TABLE_GROUPS = {"head64": (3, [0, 3, 6, 7]), "head0": (2, [0, 2, 4])}   # table -> (budget, block_groups(sizes, table, budget))
+# wave counts of table_geometry() on that batch, and the fewest a table may have for its cases to count as covered
+TABLE_WAVES = {
+    "head64": dict(next_only=4, prev_only=4, both=5, far=9, remote_short=11, remote_long=11, slot3=22),
+    "head0": dict(next_only=8, prev_only=5, both=0, far=0, remote_short=1, remote_long=12, slot3=13),
+    "packed": dict(next_only=4, prev_only=4, both=5, far=9, remote_short=11, remote_long=11, slot3=22)}
+TABLE_WAVES_MIN = {
+    "head64": dict(next_only=4, prev_only=4, both=4, far=4, remote_short=4, remote_long=4, slot3=4),
+    "head0": dict(next_only=4, prev_only=4, remote_long=4, slot3=4),
+    "packed": dict(next_only=4, prev_only=4, both=4, far=4, remote_short=4, remote_long=4, slot3=4)}
+# head0 on the same sizes at p_edge 0.04: the other side of its split into remote waves without / with a long row
+TABLE_P_EDGE_SPARSE = 0.04
+TABLE_WAVES_SPARSE = dict(next_only=8, prev_only=5, both=0, far=0, remote_short=12, remote_long=1, slot3=13)
+TABLE_WAVES_SPARSE_MIN = dict(next_only=4, prev_only=4, remote_short=4, slot3=4)
+TABLE_ELL = 16                 # neighbour slots of a row in the kernels' registers (kEll); rows above it are "long"
+
+
+def table_geometry(edge_index, starts, ptr=None):
+    """What the waves of a row-block table read, on the host with numpy: every block of ``starts`` cut into its eight 16-row
+    waves, a row's in-neighbours taken in ascending source order (the CSR GraphStructure documents; slot k = the k-th of them).
+    A wave is *remote* when a neighbour of one of its rows lies in another block.  Returns counts of waves:
+      next_only / prev_only   every remote neighbour in block blk + 1 / blk - 1 (the two register fast paths of block_of());
+      both                    remote neighbours in blk - 1 and blk + 1 and nowhere else;
+      far                     a remote neighbour two or more blocks away (the bisection);
+      remote_long / _short    remote waves with / without a row of more than 16 neighbours (a long-row wave also waits for its
+                              own block);
+      slot3                   a remote neighbour in a slot k < 16 with k % 4 == 3 (the tail ring's fourth landing buffer);
+      idle                    waves without rows (blocks shorter than 113 rows).
+    With ``ptr`` also the blocks ``mixed`` (rows of a graph that continues in another block together with whole graphs) and
+    ``last_row_first`` (the block's first row is the last row of a graph that began in an earlier block)."""
+    ei = np.asarray(edge_index)
+    starts = np.asarray(starts, dtype=np.int64)
+    n, nb = int(starts[-1]), len(starts) - 1
+    assert starts[0] == 0 and np.all(np.diff(starts) > 0) and np.all(np.diff(starts) <= 128)
+    assert ei.size == 0 or (ei.min() >= 0 and ei.max() < n)
+    perm = np.lexsort((ei[0], ei[1]))                                  # by target row, then ascending source
+    src, dst = ei[0][perm], ei[1][perm]
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))])
+    block = np.searchsorted(starts, np.arange(n), side="right") - 1     # block of every row
+    out = dict(next_only=0, prev_only=0, both=0, far=0, remote_short=0, remote_long=0, slot3=0, idle=0)
+    for blk in range(nb):
+        for w in range(8):
+            r0 = int(starts[blk]) + 16 * w
+            r1 = min(r0 + 16, int(starts[blk + 1]))
+            if r1 <= r0:
+                out["idle"] += 1
+                continue
+            rel, long_row, slot3 = set(), False, False
+            for row in range(r0, r1):
+                nbrs = src[rowptr[row]:rowptr[row + 1]]
+                long_row |= len(nbrs) > TABLE_ELL
+                for k, j in enumerate(nbrs):
+                    if block[j] != blk:
+                        rel.add(int(block[j]) - blk)
+                        slot3 |= k < TABLE_ELL and k % 4 == 3
+            if not rel:
+                continue
+            out["remote_long" if long_row else "remote_short"] += 1
+            out["slot3"] += int(slot3)
+            if any(abs(d) >= 2 for d in rel):
+                out["far"] += 1
+            elif rel == {1}:
+                out["next_only"] += 1
+            elif rel == {-1}:
+                out["prev_only"] += 1
+            else:
+                out["both"] += 1
+    if ptr is not None:
+        p = [int(v) for v in np.asarray(ptr)]
+        cut = [any(p[g] < s < p[g + 1] for s in starts) for g in range(len(p) - 1)]     # graphs that span blocks
+        mixed, last_first = [], []
+        for blk in range(nb):
+            b0, b1 = int(starts[blk]), int(starts[blk + 1])
+            inside = [g for g in range(len(p) - 1) if p[g] < b1 and p[g + 1] > b0 and p[g + 1] > p[g]]
+            if any(cut[g] for g in inside) and any(not cut[g] for g in inside):
+                mixed.append(blk)
+            if any(cut[g] and p[g] < b0 and p[g + 1] - 1 == b0 for g in inside):
+                last_first.append(blk)
+        out["mixed"], out["last_row_first"] = mixed, last_first
+    return out
+
+
 def qnet_ref(c_in, hidden, body, head, seed):
     """The oracle's Q-network with ``c_in`` raw features: DuellingTwoHeadedRef built directly (get_pre_defined_ref fixes
     in_channels = 2) with the ``modern_two_headed`` head, in the sharpened state."""
@@ -361,16 +473,24 @@ def same_bits(tag, a, b):
 class QnetCases:
     """The Q-network cases of one batch shape and depth: ``feature_batch(sizes, c_in, seed=100 + c_in)`` with one selected row
     per graph, ``body`` + ``head`` layers, loss ``feature_loss``; per (c_in, hidden) the float64 and fp32 oracle results at the
-    first weight seed that meets the four input conditions (see tests/test_gpu_feature_counts.py), once per session."""
+    first weight seed that meets the four input conditions (see tests/test_gpu_feature_counts.py), once per session.
+    ``p_edge``: the batch's edge probability; ``order``: the batch with its graphs in that order (``reorder_graphs``), every
+    graph keeping its selected row and its target."""
 
-    def __init__(self, sizes, body, head):
+    def __init__(self, sizes, body, head, p_edge=0.08, order=None):
         self.sizes, self.body, self.head = list(sizes), body, head
+        self.p_edge, self.order = p_edge, None if order is None else list(order)
         self._batches, self._oracles = {}, {}
 
     def batch(self, c_in):
         if c_in not in self._batches:
-            x, ei, batch, ptr = feature_batch(self.sizes, c_in, seed=100 + c_in)
-            self._batches[c_in] = (x, ei, batch, ptr) + one_row_per_graph(ptr)
+            x, ei, batch, ptr = feature_batch(self.sizes, c_in, seed=100 + c_in, p_edge=self.p_edge)
+            sel, tgt = one_row_per_graph(ptr)
+            if self.order is not None:
+                local = sel - ptr[:-1]
+                x, ei, batch, ptr, _ = reorder_graphs(x, ei, ptr, self.order)
+                sel, tgt = ptr[:-1] + local[self.order], tgt[self.order]
+            self._batches[c_in] = (x, ei, batch, ptr, sel, tgt)
         return self._batches[c_in]
 
     def dev(self, c_in):
@@ -475,14 +595,14 @@ class QnetCases:
 
 # ---- a SAGE stack through autograd: the oracle's side --------------------------------------------------------------------------
 
-def stack_model(kind, c_in, hidden, seed):
+def stack_model(kind, c_in, hidden, seed, layers=3):
     from oracle.model_ref import GraphSAGERef, SAGEConvRef
     torch.manual_seed(seed)
     if kind == "single":                # a bare SAGEConv(c_in, H): no ReLU behind it
         m = torch.nn.Module()
         m.convs, m.norms = torch.nn.ModuleList([SAGEConvRef(c_in, hidden)]), None
     else:
-        m = GraphSAGERef(c_in, hidden, 3, norm=True if kind == "norm" else None)
+        m = GraphSAGERef(c_in, hidden, layers, norm=True if kind == "norm" else None)
     return sharpen_(m)
 
 
@@ -643,12 +763,15 @@ def norm_kernel_oracle(kind, n, hidden, variant, zero_grads=()):
 
 # ---- the norm stack (ops.sage_norm_stack) on batches of any size --------------------------------------------------------------
 
-def stack_conditions(kind, m64, c_in, x64, ei, r64, padded):
+def stack_conditions(kind, m64, c_in, x64, ei, r64, padded, layers=3, p_edge=0.08):
     """The input conditions of a SAGE stack on its float64 oracle, with the loss scaled by the smallest power of two at which every
-    gradient tensor reaches |g|max >= 1e-2 (exact in every arithmetic, no relative figure changes): (ok, text, scale, y64, g64, dx64)."""
+    gradient tensor reaches |g|max >= 1e-2 (exact in every arithmetic, no relative figure changes): (ok, text, scale, y64, g64, dx64).
+    ``layers`` and ``p_edge`` say what the caller built ``m64`` and ``ei`` with: the ReLU margin is taken over exactly ``layers``
+    pre-activation tensors, and the text names both where they are not the defaults."""
     pre = []
     with torch.no_grad():
         stack_forward(kind, m64, x64, ei, pre)
+    assert len(pre) == (0 if kind == "single" else layers), (kind, len(pre), layers)
     margin = relu_margin_of(pre)
     if margin < MARGIN:
         return False, "smallest |ReLU input| / rms %.3g" % margin, 1.0, None, None, None
@@ -671,25 +794,32 @@ def stack_conditions(kind, m64, c_in, x64, ei, r64, padded):
     text = "output sensitivity per feature %.3g..%.3g (> 0.1), layer-0 gradient column share %.3g..%.3g (>= 0.02), output spread " \
            "%.3g (>= 0.5), smallest |g|max %.3g (>= 1e-2) at loss scale %g, smallest |ReLU input| / rms %.3g (>= 2^-16)" \
            % (min(sens), max(sens), min(shares), max(shares), spread, gmax * scale, scale, margin)
+    if (layers, p_edge) != (3, 0.08):
+        text += "; %d layers, p_edge %g" % (layers, p_edge)
     return ok, text, scale, y64, g64, dx64
 
 
-def stack_oracle(kind, c_in, hidden, sizes):
-    """A three-layer stack on ``feature_batch(sizes, c_in, seed=100 + c_in)``, loss scale * sum(y * R) / n with R ~ U(-1, 1): the
-    float64 and fp32 oracle results at the first weight seed below SEEDS that meets ``stack_conditions``."""
+def stack_oracle(kind, c_in, hidden, sizes, layers=3, p_edge=0.08, order=None):
+    """A stack of ``layers`` layers on ``feature_batch(sizes, c_in, seed=100 + c_in, p_edge=p_edge)`` (``order``: its graphs in
+    that order, ``reorder_graphs``; R stays with its rows), loss scale * sum(y * R) / n with R ~ U(-1, 1): the float64 and fp32
+    oracle results at the first weight seed below SEEDS that meets ``stack_conditions``."""
     import copy
-    x, ei, _, _ = feature_batch(sizes, c_in, seed=100 + c_in)
+    x, ei, bv, ptr = feature_batch(sizes, c_in, seed=100 + c_in, p_edge=p_edge)
     gen = torch.Generator().manual_seed(7)
     r = torch.rand(x.shape[0], hidden, generator=gen) * 2 - 1
+    if order is not None:
+        x, ei, bv, ptr, rows = reorder_graphs(x, ei, ptr, order)
+        r = r[rows]
     padded = c_in == hidden
     for seed in range(SEEDS):
-        m = stack_model(kind, c_in, hidden, seed)
+        m = stack_model(kind, c_in, hidden, seed, layers)
         if kind == "norm":                  # non-trivial affine parameters (the default is weight 1, bias 0)
             with torch.no_grad():
                 for nm in m.norms:
                     nm.weight.add_(torch.randn(hidden) * 0.2)
                     nm.bias.add_(torch.randn(hidden) * 0.2)
-        ok, text, scale, y64, g64, dx64 = stack_conditions(kind, copy.deepcopy(m).double(), c_in, x.double(), ei, r.double(), padded)
+        ok, text, scale, y64, g64, dx64 = stack_conditions(kind, copy.deepcopy(m).double(), c_in, x.double(), ei, r.double(), padded,
+                                                           layers, p_edge)
         if ok:
             break
     else:
@@ -697,7 +827,8 @@ def stack_oracle(kind, c_in, hidden, sizes):
                              % (kind, c_in, hidden, x.shape[0], SEEDS))
     y32, g32, dx32 = stack_run(kind, m, x, ei, r, padded, scale)
     print("oracle %s c_in %d hidden %d rows %d: weight seed %d; %s" % (kind, c_in, hidden, x.shape[0], seed, text))
-    return dict(m=m, x=x, ei=ei, r=r, scale=scale, seed=seed, ok=ok, text=text, y64=y64, g64=g64, dx64=dx64, y32=y32, g32=g32, dx32=dx32)
+    return dict(m=m, x=x, ei=ei, ptr=ptr, r=r, scale=scale, seed=seed, ok=ok, text=text, y64=y64, g64=g64, dx64=dx64, y32=y32, g32=g32,
+                dx32=dx32)
 
 
 # ---- the two model families with their norms ----------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhexgnn.so")
 _lib = None
-ABI_VERSION = 7          # HEXGNN_ABI_VERSION of include/hexgnn.h this binding was written against
+ABI_VERSION = 8          # HEXGNN_ABI_VERSION of include/hexgnn.h this binding was written against
 
 vp = C.c_void_p
 ci = C.c_int
@@ -40,6 +40,19 @@ class QNetCall(C.Structure):
 
 
 QNET_CALL_BYTES = C.sizeof(QNetCall)
+
+
+class SageStackCall(C.Structure):
+    """``hexgnn_sage_stack_call`` of include/hexgnn.h, field for field (tests/test_stack_call_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "n c_in hidden num_layers x_stride need_backward flags")
+                + _fields(vp, "rowptr col rowptr_t col_t invdeg x wl bl wr wpack acts saved workspace")
+                + _fields(sz, "workspace_bytes")
+                + _fields(vp, "block_starts") + _fields(ci, "num_blocks") + _fields(vp, "group_starts") + _fields(ci, "num_groups")
+                + _fields(vp, "nw nb") + _fields(C.c_float, "eps") + _fields(vp, "pre stats norm_ws") + _fields(sz, "norm_ws_bytes")
+                + _fields(vp, "n_live dy dx d_wl d_bl d_wr d_nw d_nb") + _fields(ci, "tap_layer") + _fields(vp, "tap_out"))
+
+
+SAGE_STACK_CALL_BYTES = C.sizeof(SageStackCall)
 
 
 class TransitionsCall(C.Structure):
@@ -104,19 +117,10 @@ _SIGS = {
     "hexgnn_dw_slice_plan": (ci, [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]),
     "hexgnn_sage_stack_backward": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, sz, ci, vp]),
-    "hexgnn_sage_stack_backward_tap": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
-                                            vp, vp, vp, vp, sz, ci, ci, vp, vp]),
-    "hexgnn_sage_stack_forward_blocks": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp]),
-    "hexgnn_sage_stack_backward_blocks": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
-                                               vp, vp, vp, vp, sz, ci, ci, vp, vp, ci, vp]),
-    "hexgnn_sage_stack_forward_groups": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, ci,
-                                              vp]),
-    "hexgnn_sage_stack_backward_groups": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp,
-                                               vp, vp, vp, vp, sz, ci, ci, vp, vp, ci, vp, ci, vp]),
+    "hexgnn_sage_stack_call_forward": (ci, [C.POINTER(SageStackCall), vp]),
+    "hexgnn_sage_stack_call_backward": (ci, [C.POINTER(SageStackCall), vp]),
     "hexgnn_sage_norm_stack_forward": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp,
                                             vp, vp, sz, ci, vp]),
-    "hexgnn_sage_norm_stack_forward_live": (ci, [ci, vp, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_float, vp, vp,
-                                                 vp, vp, vp, vp, sz, ci, vp]),
     "hexgnn_sage_norm_stack_backward_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "hexgnn_sage_norm_stack_backward": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp,
                                              vp, vp, vp, vp, vp, sz, vp, sz, vp]),

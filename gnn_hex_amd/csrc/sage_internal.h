@@ -37,7 +37,7 @@ struct StackKArgs {
     const int* bstart;                 // null: block b = rows [128 b, 128 b + 128); else [nblocks + 1] row offsets (block b =
     int nblocks;                       //   rows [bstart[b], bstart[b + 1]), at most 128 each, a partition of [0, n))
     int gbase, gcount;                 // the launch runs blocks [gbase, gbase + gcount) of the table, one per workgroup (a group of
-                                       //   whole graphs: hexgnn_sage_stack_*_groups); gcount == 0: the whole table, filled by launch_stack
+                                       //   whole graphs: hexgnn_sage_stack_call's groups); gcount == 0: the whole table, filled by launch_stack
     int* status;
     unsigned skew;                     // test aid (HEXGNN_STACK_SKEW): != 0 delays every block by a pseudo-random time per layer;
 };                                     // 0xDE00bbbb: block bbbb never publishes its progress (its readers must time out)

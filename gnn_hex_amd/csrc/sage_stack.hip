@@ -83,7 +83,7 @@ __device__ __forceinline__ void sage_stack_body(const StackKArgs& a, f32x4* wlds
         const f32x4* w4 = reinterpret_cast<const f32x4*>(wp);
         for (int p = wave; p < 2 * NT * NT; p += 8) dma_piece(w4 + p * 64, 16 * lane, lds_w + p * 1024);
     };
-    // the block's rows.  With a block table (graph-aligned blocks: hexgnn_sage_stack_forward_blocks) the range comes from the
+    // the block's rows.  With a block table (graph-aligned blocks: hexgnn_sage_stack_call.block_starts) the range comes from the
     // table and is checked HERE (the table is device data the host never saw): a range that is not a piece of a partition of
     // [0, n) in pieces of at most 128 rows makes the block empty and sets HEXGNN_EINVAL in the status word
     // (a launch runs the blocks [gbase, gbase + gridDim.x) of a table of nblocks: a group of whole graphs.  Block indices,

@@ -68,7 +68,7 @@ def blocks_for_order(sizes: List[int], block: int = BLOCK_ROWS, head: int = 64) 
 
 def pack_order(sizes: List[int], block: int = BLOCK_ROWS, max_blocks: Optional[int] = None, head: int = 64):
     """Order of the graphs of a batch, and the row blocks that go with it, for the one-launch SAGE stack kernels
-    (``hexgnn_sage_stack_*_blocks``): a workgroup owns a block of at most ``block`` consecutive rows, and a block that holds
+    (``hexgnn_sage_stack_call.block_starts``): a workgroup owns a block of at most ``block`` consecutive rows, and a block that holds
     only WHOLE graphs never waits for another block.  The order in which a batch lists its graphs is the collation's to
     choose (a replay batch is a random draw; the reference's loss is a mean over it), so the graphs are packed:
 
@@ -125,7 +125,7 @@ def _pack_layout(sizes: List[int], block: int, hd: int):
 
 
 def block_groups(sizes_in_order: List[int], starts: Optional[List[int]], max_blocks: int) -> Optional[List[int]]:
-    """Groups of a block table that has more blocks than can be resident at once (``hexgnn_sage_stack_*_groups``): block
+    """Groups of a block table that has more blocks than can be resident at once (``hexgnn_sage_stack_call.group_starts``): block
     indices ``[0, ..., nb]``, every group at most ``max_blocks`` blocks, a cut only where a block start is also a graph start --
     a group then holds whole graphs and none of its blocks waits for a block of another group, so each group is one launch.
     Greedy, every group up to the farthest cut it can reach: the fewest groups.  ``[0, nb]`` when the table fits as it is;

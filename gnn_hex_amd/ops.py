@@ -90,7 +90,7 @@ def sticky_status(device) -> torch.Tensor:
 def _blocks_of(edge_index, n: int):
     """The collation's row-block table of a batch (``edge_index._hex_blocks`` = (int32 device tensor [nb + 1], nb), attached by
     ``Batch.from_data_list(..., pack=True)`` / ``data.attach_blocks``): graph-aligned blocks for the one-launch stack kernels
-    (``hexgnn_sage_stack_*_blocks``).  Anything malformed is ignored (the default 128-row blocks then)."""
+    (``hexgnn_sage_stack_call.block_starts``).  Anything malformed is ignored (the default 128-row blocks then)."""
     blk = getattr(edge_index, "_hex_blocks", None)
     if blk is None:
         return None
@@ -108,8 +108,8 @@ def _blocks_of(edge_index, n: int):
 def _groups_of(edge_index, n: int):
     """The collation's block table of a batch that needs more blocks than can be resident at once, with its groups
     (``edge_index._hex_block_groups`` = (int32 device tensor [nb + 1], nb, groups), ``data.attach_block_groups``): every group
-    is one launch of the one-launch stack kernels (``hexgnn_sage_stack_*_groups``).  Returns (table, nb, groups, the groups as
-    a C int array) or None; anything malformed is ignored."""
+    is one launch of the one-launch stack kernels (``hexgnn_sage_stack_call.group_starts``).  Returns (table, nb, groups, the
+    groups as a C int array) or None; anything malformed is ignored."""
     grp = getattr(edge_index, "_hex_block_groups", None)
     if grp is None:
         return None
@@ -127,16 +127,35 @@ def _groups_of(edge_index, n: int):
     return (t, nb, groups, (C.c_int * len(groups))(*groups))
 
 
-def _stack_entry(L, gs, forward: bool):
-    """Entry point of the layer-major stack for a batch and its trailing table arguments: the ``_groups`` form when the batch
-    carries a grouped table, the ``_blocks`` form otherwise."""
-    grp = gs.groups
-    if grp is not None:
-        name = "hexgnn_sage_stack_forward_groups" if forward else "hexgnn_sage_stack_backward_groups"
-        return getattr(L, name), name, (grp[0].data_ptr(), grp[1], grp[3], len(grp[2]) - 1)
-    blk = gs.blocks
-    name = "hexgnn_sage_stack_forward_blocks" if forward else "hexgnn_sage_stack_backward_blocks"
-    return getattr(L, name), name, (blk[0].data_ptr() if blk else None, blk[1] if blk else 0)
+def _stack_call(gs, gp, n, c_in, hidden, layers, x, x_stride, arrays, wpack, acts, saved, need_bwd, flags=0, norm=None):
+    """The ``hexgnn_sage_stack_call`` of a layer-major stack's forward over ``gs``, with the batch's grouped table, else its
+    plain table, else the default blocks; the backward sets its own fields on the same object.  Everything but ``gs`` is an
+    address or a number: ``gp`` = (rowptr, col, rowptr_t, col_t, invdeg) or None (taken from ``gs``), ``arrays`` = the wl / bl /
+    wr pointer arrays (None each: packed by the CSR call), ``norm`` = the norm group's fields by name (the norm stack).
+    The descriptor holds RAW ADDRESSES: its owner keeps what they point at."""
+    if gp is None:
+        gp = (gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.rowptr_t.data_ptr(), gs.col_t.data_ptr(), gs.invdeg.data_ptr())
+    d = _lib.SageStackCall(struct_bytes=_lib.SAGE_STACK_CALL_BYTES, n=n, c_in=c_in, hidden=hidden, num_layers=layers,
+                           x_stride=x_stride, need_backward=int(need_bwd), flags=flags, rowptr=gp[0], col=gp[1], rowptr_t=gp[2],
+                           col_t=gp[3], invdeg=gp[4], x=x, wl=arrays[0], bl=arrays[1], wr=arrays[2], wpack=wpack, acts=acts,
+                           saved=saved, tap_layer=-1, **(norm or {}))
+    if norm is None and gs.groups is not None:
+        t, nb, groups, cgroups = gs.groups
+        d.block_starts, d.num_blocks, d.group_starts, d.num_groups = t.data_ptr(), nb, C.addressof(cgroups), len(groups) - 1
+    elif norm is None and gs.blocks:                     # (the norm stack runs a launch per layer: no table)
+        d.block_starts, d.num_blocks = gs.blocks[0].data_ptr(), gs.blocks[1]
+    return d
+
+
+def _ptr_arrays(tensors: Sequence[torch.Tensor], k: int):
+    """``tensors`` dealt into ``k`` pointer arrays (every k-th tensor each), and the arrays' addresses as a descriptor holds them."""
+    arrays = [_ptr_array(tensors[i::k]) for i in range(k)]
+    return arrays, [C.addressof(a) for a in arrays]
+
+
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    """``t`` as a contiguous fp32 tensor (``t`` itself when it is one)."""
+    return t if (t.is_contiguous() and t.dtype == torch.float32) else t.float().contiguous()
 
 
 class GraphStructure:
@@ -367,6 +386,40 @@ def _logical(padded: torch.Tensor, hidden: int) -> torch.Tensor:
 # GraphSAGE stack
 # ------------------------------------------------------------------------------------------------
 
+def _stack_inputs(x, c_in: int, hidden: int, params):
+    """What both stacks are handed: (n, hp, the input rows, their stride, the parameters as contiguous fp32) -- raw features
+    (c_in != hidden) as fp32 rows of any stride, a hidden-wide input in the padded layout."""
+    n = int(x.shape[0])
+    hp = padded_width(hidden)
+    if c_in != hidden:
+        if x.dtype != torch.float32 or x.stride(1) != 1:
+            x = x.float().contiguous()
+        xin, x_stride = x, (x.stride(0) if n > 0 else c_in)
+    else:
+        xin, x_stride = as_padded(x, hidden, trust_pads=False), hp
+    return n, hp, xin, x_stride, [_f32c(p) for p in params]
+
+
+def _stack_backward(ctx, grad_out, k: int, ws_bytes: int):
+    """The backward of both stacks (``k`` parameters per layer): the backward fields of the forward's descriptor, one call.
+    Returns (the input gradient or None, the parameter gradients)."""
+    n, c_in, hidden, num_layers, hp = ctx.dims
+    dev = grad_out.device
+    dy = as_padded(grad_out, hidden, trust_pads=True)
+    want_dx = ctx.needs_input_grad[0] and c_in == hidden
+    dx = torch.empty((n, hp), dtype=torch.float32, device=dev) if want_dx else None
+    grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.param_shapes]
+    ws = _bytes(ws_bytes, dev)
+    d = ctx.desc
+    garrays, ga = _ptr_arrays(grads, k)
+    d.dy, d.dx, d.workspace, d.workspace_bytes = dy.data_ptr(), dx.data_ptr() if dx is not None else None, ws.data_ptr(), ws_bytes
+    d.d_wl, d.d_bl, d.d_wr = ga[:3]
+    if k == 5:
+        d.d_nw, d.d_nb = ga[3:]
+    _lib.check(_lib.lib().hexgnn_sage_stack_call_backward(d, _stream()), "hexgnn_sage_stack_call_backward")
+    return (_logical(dx, hidden) if dx is not None else None), tuple(grads)
+
+
 class SageStackFn(torch.autograd.Function):
     """y = relu(SAGE_L(... relu(SAGE_1(x)) ...)); CachifiedGNN.forward, GN0/models.py:261-294."""
 
@@ -374,59 +427,28 @@ class SageStackFn(torch.autograd.Function):
     def forward(ctx, x, gs: GraphStructure, c_in: int, hidden: int, num_layers: int, flags: int, *params):
         L = _lib.lib()
         dev = x.device
-        n = int(x.shape[0])
-        hp = padded_width(hidden)
-        small = c_in != hidden
-        if small:
-            if x.dtype != torch.float32 or x.stride(1) != 1:
-                x = x.float().contiguous()
-            xin, x_stride = x, (x.stride(0) if n > 0 else c_in)
-        else:
-            xin = as_padded(x, hidden, trust_pads=False)
-            x_stride = hp
-        params = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous() for p in params]
-        wl, bl, wr = params[0::3], params[1::3], params[2::3]
+        n, hp, xin, x_stride, params = _stack_inputs(x, c_in, hidden, params)
+        arrays, pa = _ptr_arrays(params, 3)
         need_bwd = any(ctx.needs_input_grad)
         acts = torch.empty((num_layers, n, hp), dtype=torch.float32, device=dev)
         wpack = _bytes(L.hexgnn_sage_stack_pack_bytes(c_in, hidden, num_layers), dev)
         # (hidden > 128: the plain kernels materialise every layer's aggregate, with or without a backward)
         saved = _bytes(L.hexgnn_sage_stack_saved_bytes(n, c_in, hidden, num_layers), dev) if (need_bwd or hidden > 128) else None
-        fn, name, tbl = _stack_entry(L, gs, True)
-        _lib.check(fn(
-            n, c_in, hidden, num_layers, gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.invdeg.data_ptr(),
-            xin.data_ptr(), x_stride, _ptr_array(wl), _ptr_array(bl), _ptr_array(wr), wpack.data_ptr(),
-            acts.data_ptr(), saved.data_ptr() if saved is not None else None, int(need_bwd), int(flags),
-            *tbl, _stream()), name)
+        desc = _stack_call(gs, None, n, c_in, hidden, num_layers, xin.data_ptr(), x_stride, pa, wpack.data_ptr(), acts.data_ptr(),
+                           saved.data_ptr() if saved is not None else None, need_bwd, int(flags))
+        _lib.check(L.hexgnn_sage_stack_call_forward(desc, _stream()), "hexgnn_sage_stack_call_forward")
         if need_bwd:
-            ctx.gs = gs
-            ctx.flags = int(flags)
-            ctx.dims = (n, c_in, hidden, num_layers, hp, x_stride)
-            ctx.bufs = (xin, acts, saved, wpack)
+            # the descriptor holds raw addresses; ctx keeps what they point at: gs (the graph arrays, the table, the groups' C
+            # array), bufs (input rows and the forward's buffers), keep (the pointer arrays)
+            ctx.desc, ctx.gs, ctx.bufs, ctx.keep = desc, gs, (xin, acts, saved, wpack), arrays
+            ctx.dims = (n, c_in, hidden, num_layers, hp)
             ctx.param_shapes = [p.shape for p in params]
         return acts[num_layers - 1][:, :hidden]
 
     @staticmethod
     def backward(ctx, grad_out):
-        L = _lib.lib()
-        n, c_in, hidden, num_layers, hp, x_stride = ctx.dims
-        xin, acts, saved, wpack = ctx.bufs
-        gs = ctx.gs
-        dev = acts.device
-        dy = as_padded(grad_out, hidden, trust_pads=True)
-        want_dx = ctx.needs_input_grad[0] and c_in == hidden
-        dx = torch.empty((n, hp), dtype=torch.float32, device=dev) if want_dx else None
-        grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.param_shapes]
-        ws_bytes = L.hexgnn_sage_stack_backward_workspace_bytes(n, c_in, hidden, num_layers)
-        ws = _bytes(ws_bytes, dev)
-        fn, name, tbl = _stack_entry(L, gs, False)
-        _lib.check(fn(
-            n, c_in, hidden, num_layers, gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.rowptr_t.data_ptr(),
-            gs.col_t.data_ptr(), gs.invdeg.data_ptr(), xin.data_ptr(), x_stride, acts.data_ptr(),
-            saved.data_ptr(), wpack.data_ptr(), dy.data_ptr(), dx.data_ptr() if dx is not None else None,
-            _ptr_array(grads[0::3]), _ptr_array(grads[1::3]), _ptr_array(grads[2::3]), ws.data_ptr(), ws_bytes,
-            ctx.flags, -1, None, *tbl, _stream()), name)
-        gx = _logical(dx, hidden) if dx is not None else None
-        return (gx, None, None, None, None, None) + tuple(grads)
+        gx, grads = _stack_backward(ctx, grad_out, 3, _lib.lib().hexgnn_sage_stack_backward_workspace_bytes(*ctx.dims[:4]))
+        return (gx, None, None, None, None, None) + grads
 
 
 SAGE_LINEAR_LAST = 1      # HEXGNN_SAGE_LINEAR_LAST: no ReLU after the last layer of the stack
@@ -492,18 +514,8 @@ class SageNormStackFn(torch.autograd.Function):
     def forward(ctx, x, gs: GraphStructure, c_in: int, hidden: int, num_layers: int, eps: float, live, *params):
         L = _lib.lib()
         dev = x.device
-        n = int(x.shape[0])
-        hp = padded_width(hidden)
-        small = c_in != hidden
-        if small:
-            if x.dtype != torch.float32 or x.stride(1) != 1:
-                x = x.float().contiguous()
-            xin, x_stride = x, (x.stride(0) if n > 0 else c_in)
-        else:
-            xin = as_padded(x, hidden, trust_pads=False)
-            x_stride = hp
-        params = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous() for p in params]
-        wl, bl, wr, nw, nb = params[0::5], params[1::5], params[2::5], params[3::5], params[4::5]
+        n, hp, xin, x_stride, params = _stack_inputs(x, c_in, hidden, params)
+        arrays, pa = _ptr_arrays(params, 5)
         # live: ops.live_rows' device-side row count (forward-only)
         need_bwd = any(ctx.needs_input_grad) and live is None
         # [pre | acts]: contraction outputs and norm + ReLU outputs of every layer
@@ -514,41 +526,27 @@ class SageNormStackFn(torch.autograd.Function):
         stats = torch.empty((num_layers, 2), dtype=torch.float32, device=dev)
         nws_bytes = L.hexgnn_graph_layernorm_workspace_bytes(hidden)
         nws = _bytes(nws_bytes, dev)
-        _lib.check(L.hexgnn_sage_norm_stack_forward_live(
-            n, live.data_ptr() if live is not None else None, c_in, hidden, num_layers, gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.invdeg.data_ptr(), xin.data_ptr(),
-            x_stride, _ptr_array(wl), _ptr_array(bl), _ptr_array(wr), _ptr_array(nw), _ptr_array(nb), float(eps),
-            wpack.data_ptr(), pre.data_ptr(), acts.data_ptr(), saved.data_ptr() if saved is not None else None,
-            stats.data_ptr(), nws.data_ptr(), nws_bytes, int(need_bwd), _stream()), "hexgnn_sage_norm_stack_forward_live")
+        norm = dict(nw=pa[3], nb=pa[4], eps=float(eps), pre=pre.data_ptr(), stats=stats.data_ptr(), norm_ws=nws.data_ptr(),
+                    norm_ws_bytes=nws_bytes, n_live=live.data_ptr() if live is not None else None)
+        desc = _stack_call(gs, None, n, c_in, hidden, num_layers, xin.data_ptr(), x_stride, pa[:3],
+                           wpack.data_ptr(), acts.data_ptr(), saved.data_ptr() if saved is not None else None, need_bwd, 0, norm)
+        _lib.check(L.hexgnn_sage_stack_call_forward(desc, _stream()), "hexgnn_sage_stack_call_forward")
         if need_bwd:
-            ctx.gs = gs
-            ctx.dims = (n, c_in, hidden, num_layers, hp, x_stride, float(eps))
-            ctx.bufs = (xin, pre, acts, saved, wpack, stats, nw)
+            # (as in SageStackFn: ctx keeps what the descriptor's addresses point at; + the fp32 norm weights, which the
+            # backward reads through `nw` and which may be copies that nothing else owns)
+            ctx.desc, ctx.gs, ctx.bufs, ctx.keep = desc, gs, (xin, both, saved, wpack, stats, params[3::5]), arrays
+            ctx.dims = (n, c_in, hidden, num_layers, hp)
             ctx.param_shapes = [p.shape for p in params]
         return acts[num_layers - 1][:, :hidden]
 
     @staticmethod
     def backward(ctx, grad_out):
         L = _lib.lib()
-        n, c_in, hidden, num_layers, hp, x_stride, eps = ctx.dims
-        xin, pre, acts, saved, wpack, stats, nw = ctx.bufs
-        gs = ctx.gs
-        dev = acts.device
-        dy = as_padded(grad_out, hidden, trust_pads=True)
-        want_dx = ctx.needs_input_grad[0] and c_in == hidden
-        dx = torch.empty((n, hp), dtype=torch.float32, device=dev) if want_dx else None
-        grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.param_shapes]
-        ws_bytes = L.hexgnn_sage_norm_stack_backward_workspace_bytes(n, c_in, hidden, num_layers)
-        ws = _bytes(ws_bytes, dev)
-        nws_bytes = L.hexgnn_graph_layernorm_workspace_bytes(hidden)
-        nws = _bytes(nws_bytes, dev)
-        _lib.check(L.hexgnn_sage_norm_stack_backward(
-            n, c_in, hidden, num_layers, gs.rowptr_t.data_ptr(), gs.col_t.data_ptr(), gs.invdeg.data_ptr(), xin.data_ptr(),
-            x_stride, pre.data_ptr(), acts.data_ptr(), saved.data_ptr(), wpack.data_ptr(), stats.data_ptr(), _ptr_array(nw),
-            eps, dy.data_ptr(), dx.data_ptr() if dx is not None else None, _ptr_array(grads[0::5]), _ptr_array(grads[1::5]),
-            _ptr_array(grads[2::5]), _ptr_array(grads[3::5]), _ptr_array(grads[4::5]), ws.data_ptr(), ws_bytes,
-            nws.data_ptr(), nws_bytes, _stream()), "hexgnn_sage_norm_stack_backward")
-        gx = _logical(dx, hidden) if dx is not None else None
-        return (gx, None, None, None, None, None, None) + tuple(grads)
+        nws_bytes = L.hexgnn_graph_layernorm_workspace_bytes(ctx.dims[2])
+        nws = _bytes(nws_bytes, grad_out.device)
+        ctx.desc.norm_ws, ctx.desc.norm_ws_bytes = nws.data_ptr(), nws_bytes
+        gx, grads = _stack_backward(ctx, grad_out, 5, L.hexgnn_sage_norm_stack_backward_workspace_bytes(*ctx.dims[:4]))
+        return (gx, None, None, None, None, None, None) + grads
 
 
 def sage_norm_stack(x: torch.Tensor, gs: GraphStructure, c_in: int, hidden: int, convs, norms) -> torch.Tensor:
@@ -576,8 +574,8 @@ class GraphLayerNormFn(torch.autograd.Function):
         hp = padded_width(hidden)
         n = int(x.shape[0])
         xp = as_padded(x, hidden, trust_pads=False)
-        w = weight if (weight.is_contiguous() and weight.dtype == torch.float32) else weight.float().contiguous()
-        b = bias if (bias.is_contiguous() and bias.dtype == torch.float32) else bias.float().contiguous()
+        w = _f32c(weight)
+        b = _f32c(bias)
         y = torch.empty((n, hp), dtype=torch.float32, device=x.device)
         stats = torch.empty(2, dtype=torch.float32, device=x.device)
         ws_bytes = L.hexgnn_graph_layernorm_workspace_bytes(hidden)
@@ -628,8 +626,7 @@ class GraphColNormFn(torch.autograd.Function):
         hp = padded_width(hidden)
         n = int(x.shape[0])
         xp = as_padded(x, hidden, trust_pads=False)
-        ps = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous()
-              for p in (weight, bias, mean_scale)]
+        ps = [_f32c(p) for p in (weight, bias, mean_scale)]
         y = torch.empty((n, hp), dtype=torch.float32, device=x.device)
         stats = torch.zeros((2, hp), dtype=torch.float32, device=x.device)
         use_cache = cache is not None
@@ -690,8 +687,7 @@ class HeadTailFn(torch.autograd.Function):
         n = int(h.shape[0])
         hp = padded_width(hidden)
         hpad = as_padded(h, hidden, trust_pads=False)
-        ps = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous()
-              for p in (lin_w, lin_b, v0_w, v0_b, v1_w, v1_b)]
+        ps = [_f32c(p) for p in (lin_w, lin_b, v0_w, v0_b, v1_w, v1_b)]
         q = torch.empty(n, dtype=torch.float32, device=dev)
         out_v = torch.empty(b, dtype=torch.float32, device=dev) if mode in (1, 3) else None
         saved = _bytes(L.hexgnn_head_saved_bytes(n, b, hidden), dev)
@@ -747,8 +743,7 @@ class HeadLinearTailFn(torch.autograd.Function):
         n = int(h.shape[0])
         hp = padded_width(hidden)
         hpad = as_padded(h, hidden, trust_pads=False)
-        ps = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous()
-              for p in (lin_w, lin_b, val_w, val_b)]
+        ps = [_f32c(p) for p in (lin_w, lin_b, val_w, val_b)]
         q = torch.empty(n, dtype=torch.float32, device=dev)
         out_v = torch.empty(b, dtype=torch.float32, device=dev) if mode in (1, 3) else None
         saved = _bytes(L.hexgnn_head_linear_saved_bytes(n, b), dev)
@@ -805,7 +800,7 @@ class SageScalarFn(torch.autograd.Function):
         dev = h.device
         n = int(h.shape[0])
         hpad = as_padded(h, hidden, trust_pads=False)
-        ps = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous() for p in (wl, bl, wr)]
+        ps = [_f32c(p) for p in (wl, bl, wr)]
         out = torch.empty(n, dtype=torch.float32, device=dev)
         dots = torch.empty((n, 2), dtype=torch.float32, device=dev)
         _lib.check(L.hexgnn_sage_scalar_forward(n, hidden, gs.rowptr.data_ptr(), gs.col.data_ptr(), gs.invdeg.data_ptr(),
@@ -1068,7 +1063,8 @@ class _QNetCall:
     ``nonleaf``: a parameter of the call is computed per forward (no staging, see qnet_backward); ``live``: td_step() over
     capacity-sized buffers -- the 1-element int32 device tensor that holds the live row count (``x._hex_live_rows``).
 
-    ``desc`` (fused kernels): the call's ``hexgnn_qnet_call``, filled by the forward; the backward sets its backward group.  It
+    ``desc``: the call's ``hexgnn_qnet_call`` (``layered``: the stack's ``hexgnn_sage_stack_call``, which reads the graph arrays,
+    the table and groups of ``gs``, x, ``bufs`` and ``keep``), filled by the forward; the backward sets its backward group.  It
     holds raw addresses, and these attributes keep what they point at alive for as long as it can be used: ``x``: x; ``gs`` and
     ``gptr``: the graph arrays and the status word; ``bufs``: acts | wpack | saved; ``cache``: the parameters (``cache.params``);
     ``keep``: the pointer arrays wl / bl / wr the forward was given (``cache.refresh()`` replaces the cache's own); ``td``: td_dq |
@@ -1088,7 +1084,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
     deferred grouped build's arguments (models.py): the build then runs here, with the weight pack in the same launch.
 
     ``layered``: the same network on the layer-major kernels (graphs above 128 nodes, hidden 113..128): body + head SAGE layers
-    as ONE stack of body_layers + head_layers layers (``hexgnn_sage_stack_forward_blocks``; the head's gnn is just more SAGE
+    as ONE stack of body_layers + head_layers layers (``hexgnn_sage_stack_call_forward``; the head's gnn is just more SAGE
     layers with ReLU), then the head tail (``hexgnn_head_forward``).  Against the per-module composition (body stack, head
     stack, head tail as three autograd functions) the backward has ONE batched weight-gradient GEMM + ONE slab reduce over all
     hidden layers instead of two of each, no stack-boundary combine, and ~1 ms less Python per step.
@@ -1143,9 +1139,9 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
     stream = _stream()
     td = live = step_ws = None
     if layered:
-        fn, name, tbl = _stack_entry(L, gs, True)
-        _lib.check(fn(n, c_in, hidden, tot, gp[0], gp[1], gp[4], x.data_ptr(), x_stride, wl, bl, wr, wpack, base, saved,
-                      int(need_bwd), 0, *tbl, stream), name)
+        desc = _stack_call(gs, gp, n, c_in, hidden, tot, x.data_ptr(), x_stride, cache.wlp if wl is not None else (None,) * 3,
+                           wpack, base, saved, need_bwd)
+        _lib.check(L.hexgnn_sage_stack_call_forward(desc, stream), "hexgnn_sage_stack_call_forward")
         _lib.check(L.hexgnn_head_forward(n, b, hidden, mode, gp[5], base + 4 * (tot - 1) * n * hp, t[0], t[1], t[2], t[3],
                                          t[4], t[5], q.data_ptr(), out_v.data_ptr() if out_v is not None else None,
                                          saved + bwd_bytes[0], stream), "hexgnn_head_forward")
@@ -1181,7 +1177,7 @@ def qnet_forward(cache: QNetParamCache, x, gs: GraphStructure, gptr, b: int, c_i
             None, None, demb_p, None, None, None)
         _lib.check(L.hexgnn_qnet_call_forward(desc, int(step_ws is not None), stream), "hexgnn_qnet_call_forward")
     call = _QNetCall()
-    call.desc, call.keep = (None, None) if layered else (desc, (wl, bl, wr))
+    call.desc, call.keep = desc, (wl, bl, wr)
     call.cache, call.gs, call.gptr, call.x = cache, gs, gptr, x
     # (bwd_bytes: the fused backward's workspace bytes; layered: (stack saved, stack workspace, head workspace) bytes)
     call.dims = (n, b, c_in, hidden, tot, body_layers, mode, hp, x_stride, a_bytes, w_bytes, bwd_bytes)
@@ -1245,8 +1241,7 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
         d_v = torch.zeros(b, dtype=torch.float32, device=dev) if d_v is None else d_v.float().contiguous()
     else:
         d_v = None
-    dq = torch.zeros(n, dtype=torch.float32, device=dev) if dq is None else \
-        (dq if (dq.dtype == torch.float32 and dq.is_contiguous()) else dq.float().contiguous())
+    dq = torch.zeros(n, dtype=torch.float32, device=dev) if dq is None else _f32c(dq)
     if call.assign:
         flat, gviews = cache.grad_buffer(dev)
     else:
@@ -1279,12 +1274,11 @@ def qnet_backward(call: _QNetCall, dq, d_v=None, defer_lower: bool = False):
         d_wl = vp(*[fb + 4 * offs[3 * l] for l in range(tot)])
         d_bl = vp(*[fb + 4 * offs[3 * l + 1] for l in range(tot)])
         d_wr = vp(*[fb + 4 * offs[3 * l + 2] for l in range(tot)])
-        fn, name, tbl = _stack_entry(L, call.gs, False)
-        _lib.check(fn(
-            n, c_in, hidden, tot, gp[0], gp[1], gp[2], gp[3], gp[4], call.x.data_ptr(), x_stride, base,
-            base + a_bytes + w_bytes, base + a_bytes, dh_ptr, None, d_wl, d_bl, d_wr, ws.data_ptr(), ws_bytes, 2,
-            body_layers - 1 if d_emb is not None else -1, d_emb.data_ptr() if d_emb is not None else None,
-            *tbl, stream), name)
+        desc = call.desc          # (the stack's hexgnn_sage_stack_call; everything set here lives until the call below returns)
+        desc.flags, desc.dy, desc.workspace, desc.workspace_bytes = 2, dh_ptr, ws.data_ptr(), ws_bytes
+        desc.d_wl, desc.d_bl, desc.d_wr = C.addressof(d_wl), C.addressof(d_bl), C.addressof(d_wr)
+        desc.tap_layer, desc.tap_out = (body_layers - 1, d_emb.data_ptr()) if d_emb is not None else (-1, None)
+        _lib.check(L.hexgnn_sage_stack_call_backward(desc, stream), "hexgnn_sage_stack_call_backward")
     else:
         ws_bytes = bwd_bytes
         td = call.td
@@ -1370,7 +1364,7 @@ class QNetFusedFn(torch.autograd.Function):
         # a parameter that is computed per forward (FactorizedNoisyLinear's mu + sigma * eps) is no leaf: its gradient is
         # an intermediate that autograd still has to carry to mu / sigma, so it must not be all-reduced in place
         nonleaf = any(p.grad_fn is not None for p in params)
-        conv = [p if (p.is_contiguous() and p.dtype == torch.float32) else p.float().contiguous() for p in params]
+        conv = [_f32c(p) for p in params]
         if cache is None or any(p is not c for p, c in zip(conv, cache.params)):
             cache = QNetParamCache(conv, body_layers + head_layers)
         q, out_v, call = qnet_forward(cache, x, gs, gptr, b, c_in, hidden, body_layers, head_layers, mode,

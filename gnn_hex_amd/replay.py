@@ -43,7 +43,7 @@ class GraphReplayBuffer:
 
         ``group_blocks``: a draw with more rows than can be resident at once (256 Hex-13 boards: one launch per layer otherwise)
         is packed with ``data.pack_groups`` and both batches carry their table in groups of whole graphs, one launch per group
-        (``hexgnn_sage_stack_*_groups``).  Off by default: see ``Batch.from_data_list``."""
+        (``hexgnn_sage_stack_call.group_starts``).  Off by default: see ``Batch.from_data_list``."""
         self.capacity, self.hex_size = int(capacity), int(hex_size)
         self.pack_blocks = bool(pack_blocks) and hex_size * hex_size + 2 > 128
         self.group_blocks = bool(group_blocks)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define HEXGNN_ABI_VERSION 7
+#define HEXGNN_ABI_VERSION 8
 
 #define HEXGNN_OK 0
 #define HEXGNN_EINVAL (-1)       /* bad argument (null pointer, negative size, ...) */
@@ -91,7 +91,7 @@ int hexgnn_csr_build_grouped_pack_e(int n, int e, int b, const int64_t* src, con
  * GN0/models.py:537): block_starts_out [max_blocks + 1] receives the partition gnn_hex_amd.data.blocks_for_order would give for
  * this graph order, unused entries = n (empty blocks: such a workgroup exits at once), or the plain 128-row partition when the
  * aligned one needs more than max_blocks blocks.  Pass it on as (block_starts, num_blocks = max_blocks) of
- * hexgnn_sage_stack_*_blocks.  Requires ceil(n / 128) <= max_blocks <= 512. */
+ * hexgnn_sage_stack_call.  Requires ceil(n / 128) <= max_blocks <= 512. */
 int hexgnn_csr_build_grouped_pack_b(int n, int e, int b, const int64_t* src, const int64_t* dst, const int* gptr,
                                     const int64_t* ptr64, const int64_t* edge_ptr64, int* gptr_out, int* rowptr, int* col,
                                     int* rowptr_t, int* col_t, float* invdeg, int* status, int c_in, int hidden,
@@ -154,72 +154,73 @@ int hexgnn_sage_stack_backward(int n, int c_in, int hidden, int num_layers,
                                void* workspace, size_t workspace_bytes, int flags /* as in the forward call */,
                                hexgnn_stream_t stream);
 
-/* The same call with a TAP: tap_out [n][HP] (may be NULL) receives the gradient w.r.t. the OUTPUT of layer tap_layer
- * (0 <= tap_layer < num_layers - 1) -- DuellingTwoHeaded's final_conv_grads when body and head layers run as one stack
- * (GN0/models.py:553-554: embeds.register_hook). */
-int hexgnn_sage_stack_backward_tap(int n, int c_in, int hidden, int num_layers,
-                                   const int* rowptr, const int* col,
-                                   const int* rowptr_t, const int* col_t, const float* invdeg,
-                                   const float* x, int x_stride,
-                                   const float* acts, const void* saved, const void* wpack,
-                                   const float* dy, float* dx,
-                                   float* const* d_wl, float* const* d_bl, float* const* d_wr,
-                                   void* workspace, size_t workspace_bytes, int flags,
-                                   int tap_layer, float* tap_out, hexgnn_stream_t stream);
-
-/* Both directions with GRAPH-ALIGNED row blocks (round 4).  The one-launch stack kernels give every workgroup a block of at
- * most 128 consecutive rows; by default block b = rows [128 b, 128 b + 128), which cuts graphs wherever a multiple of 128 falls,
- * and a block that holds part of a graph waits, layer by layer, for the blocks that hold the rest.  block_starts (DEVICE array,
- * num_blocks + 1 ascending row offsets, block_starts[0] = 0, block_starts[num_blocks] = n, pieces of at most 128 rows) lets the
- * collation decide instead: with the graphs ordered so that blocks hold whole graphs (gnn_hex_amd.data.pack_order; the
- * reference's Batch.from_data_list, GN0/RainbowDQN/Rainbow/common/utils.py via torch_geometric, keeps the caller's order, and
- * the order of a replay batch carries no meaning) only graphs above 128 rows couple blocks -- the two or three they span.
- * The table's content is checked by the kernel (a block whose range is not such a piece computes nothing and the launch
- * reports HEXGNN_EINVAL through hexgnn_stack_status); num_blocks must lie in [ceil(n / 128), 512]; empty blocks are allowed (a
- * table padded at its end with entries == n, as hexgnn_csr_build_grouped_pack_b writes it: such a workgroup exits at once).
- * A table with more blocks than hexgnn_stack_block_budget() is ignored (default blocks).  Results equal the default
- * blocks' to fp32 rounding (the order in which a row's neighbour sum takes in-block and out-of-block neighbours differs).
- * block_starts == NULL (num_blocks 0): exactly the calls above.  Per-layer launches (batch too large for one resident
- * workgroup per CU, HEXGNN_NO_PERSIST) and hidden > 128 ignore the table. */
-int hexgnn_sage_stack_forward_blocks(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
-                                     const float* invdeg, const float* x, int x_stride, const float* const* wl,
-                                     const float* const* bl, const float* const* wr, void* wpack, float* acts,
-                                     void* saved, int need_backward, int flags, const int* block_starts, int num_blocks,
-                                     hexgnn_stream_t stream);
-int hexgnn_sage_stack_backward_blocks(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
-                                      const int* rowptr_t, const int* col_t, const float* invdeg, const float* x,
-                                      int x_stride, const float* acts, const void* saved, const void* wpack,
-                                      const float* dy, float* dx, float* const* d_wl, float* const* d_bl,
-                                      float* const* d_wr, void* workspace, size_t workspace_bytes, int flags,
-                                      int tap_layer, float* tap_out, const int* block_starts, int num_blocks,
-                                      hexgnn_stream_t stream);
-
-/* The same with the table's blocks in GROUPS, for batches whose table has more blocks than can be resident at once (a uniform
- * Hex-13 replay batch of 256 graphs: 512 blocks on 256 CUs).  Graphs are independent: a range of blocks that holds whole graphs
- * never waits for a block outside it, so the one-launch kernel runs group after group on the caller's stream -- one launch per
- * group and direction instead of one per layer.  group_starts (HOST array, num_groups + 1 block indices, read before the call
- * returns): group_starts[0] = 0 < group_starts[1] < ... < group_starts[num_groups] = num_blocks; every cut must fall where a
- * block start is also a graph start (gnn_hex_amd.data.block_groups / pack_groups).  Rejected with HEXGNN_EINVAL on the host,
- * before anything is launched: groups without a table, a list that is not strictly ascending (an empty group), wrong end
- * points, num_blocks outside [1, 512] (the progress counters of a call are indexed by the table's block index, so 512 caps the
- * whole table, not a group).  A cut that an edge crosses cannot be seen by the host; the kernel does not wait across it: the
- * rows of a wave that would read a block outside its launch's group become NaN and hexgnn_stack_status reports HEXGNN_EINVAL.
- * If the largest group does not pass the residency test of the one-launch kernels (budget, CU mask, another stream in flight),
- * under HEXGNN_NO_PERSIST / hexgnn_debug_stack_mode(0, ...), for hidden <= 32 and for hidden > 128 the groups are ignored and
- * the call is the _blocks one.  num_groups == 0: exactly the _blocks call.  A block's arithmetic depends on the table only:
- * results are bit-identical to one launch over the same table. */
-int hexgnn_sage_stack_forward_groups(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
-                                     const float* invdeg, const float* x, int x_stride, const float* const* wl,
-                                     const float* const* bl, const float* const* wr, void* wpack, float* acts,
-                                     void* saved, int need_backward, int flags, const int* block_starts, int num_blocks,
-                                     const int* group_starts, int num_groups, hexgnn_stream_t stream);
-int hexgnn_sage_stack_backward_groups(int n, int c_in, int hidden, int num_layers, const int* rowptr, const int* col,
-                                      const int* rowptr_t, const int* col_t, const float* invdeg, const float* x,
-                                      int x_stride, const float* acts, const void* saved, const void* wpack,
-                                      const float* dy, float* dx, float* const* d_wl, float* const* d_bl,
-                                      float* const* d_wr, void* workspace, size_t workspace_bytes, int flags,
-                                      int tap_layer, float* tap_out, const int* block_starts, int num_blocks,
-                                      const int* group_starts, int num_groups, hexgnn_stream_t stream);
+/* ---- The stack as ONE descriptor (ABI 8): everything a layer-major stack's forward and its backward need, written once, for the
+ *      plain stack and for the stack with the whole-batch LayerNorm between every contraction and its ReLU (below: nw / nb set).
+ *      A caller fills it for the forward, hands the SAME object to the backward after setting the backward group, and selects a
+ *      capability by a field value.  It replaces the _blocks, _groups, _tap and _live entry points of ABI 7;
+ *      hexgnn_sage_stack_forward / _backward above and hexgnn_sage_norm_stack_forward / _backward below stay as positional
+ *      adapters onto the same implementation.  Plain pointers and sizes; device pointers unless marked HOST.  Fields a call does
+ *      not read may hold anything. ---- */
+typedef struct hexgnn_sage_stack_call {
+    /* sizeof(hexgnn_sage_stack_call), else HEXGNN_EINVAL before anything else is looked at */
+    size_t struct_bytes;
+    /* shape: as hexgnn_sage_stack_forward / _backward.  need_backward is read by the forward only.  flags: the forward takes
+     * HEXGNN_SAGE_LINEAR_LAST, the backward also HEXGNN_SAGE_DY_IN_PLACE (not both); 0 for the norm stack */
+    int n, c_in, hidden, num_layers, x_stride, need_backward, flags;
+    /* graph: the CSR (forward) and its transpose (backward), invdeg [n], x [n][x_stride] */
+    const int* rowptr; const int* col; const int* rowptr_t; const int* col_t; const float* invdeg; const float* x;
+    /* parameters: HOST arrays of num_layers device pointers; all three NULL = packed into wpack by the
+     * hexgnn_csr_build_grouped_pack of this step (plain stack only) */
+    const float* const* wl; const float* const* bl; const float* const* wr;
+    /* buffers: wpack, acts and saved go from the forward to the backward; workspace
+     * (hexgnn_sage_stack_backward_workspace_bytes, or hexgnn_sage_norm_stack_backward_workspace_bytes) is the backward's */
+    void* wpack; float* acts; void* saved; void* workspace; size_t workspace_bytes;
+    /* row blocks, both directions: GRAPH-ALIGNED row blocks (round 4).  The one-launch stack kernels give every workgroup a block
+     * of at most 128 consecutive rows; by default block b = rows [128 b, 128 b + 128), which cuts graphs wherever a multiple of
+     * 128 falls, and a block that holds part of a graph waits, layer by layer, for the blocks that hold the rest.  block_starts
+     * (DEVICE array, num_blocks + 1 ascending row offsets, block_starts[0] = 0, block_starts[num_blocks] = n, pieces of at most
+     * 128 rows) lets the collation decide instead: with the graphs ordered so that blocks hold whole graphs
+     * (gnn_hex_amd.data.pack_order; the reference's Batch.from_data_list, GN0/RainbowDQN/Rainbow/common/utils.py via
+     * torch_geometric, keeps the caller's order, and the order of a replay batch carries no meaning) only graphs above 128 rows
+     * couple blocks -- the two or three they span.  The table's content is checked by the kernel (a block whose range is not such
+     * a piece computes nothing and the launch reports HEXGNN_EINVAL through hexgnn_stack_status); num_blocks must lie in
+     * [ceil(n / 128), 512]; empty blocks are allowed (a table padded at its end with entries == n, as
+     * hexgnn_csr_build_grouped_pack_b writes it: such a workgroup exits at once).  A table with more blocks than
+     * hexgnn_stack_block_budget() is ignored (default blocks).  Results equal the default blocks' to fp32 rounding (the order in
+     * which a row's neighbour sum takes in-block and out-of-block neighbours differs).  block_starts == NULL (num_blocks 0): the
+     * default blocks.  Per-layer launches (batch too large for one resident workgroup per CU, HEXGNN_NO_PERSIST) and hidden > 128
+     * ignore the table.
+     * group_starts: the table's blocks in GROUPS, for batches whose table has more blocks than can be resident at once (a
+     * uniform Hex-13 replay batch of 256 graphs: 512 blocks on 256 CUs).  Graphs are independent: a range of blocks that holds
+     * whole graphs never waits for a block outside it, so the one-launch kernel runs group after group on the caller's stream --
+     * one launch per group and direction instead of one per layer.  group_starts (HOST array, num_groups + 1 block indices, read
+     * before the call returns): group_starts[0] = 0 < group_starts[1] < ... < group_starts[num_groups] = num_blocks; every cut
+     * must fall where a block start is also a graph start (gnn_hex_amd.data.block_groups / pack_groups).  Rejected with
+     * HEXGNN_EINVAL on the host, before anything is launched: groups without a table, a list that is not strictly ascending (an
+     * empty group), wrong end points, num_blocks outside [1, 512] (the progress counters of a call are indexed by the table's
+     * block index, so 512 caps the whole table, not a group).  A cut that an edge crosses cannot be seen by the host; the kernel
+     * does not wait across it: the rows of a wave that would read a block outside its launch's group become NaN and
+     * hexgnn_stack_status reports HEXGNN_EINVAL.  If the largest group does not pass the residency test of the one-launch kernels
+     * (budget, CU mask, another stream in flight), under HEXGNN_NO_PERSIST / hexgnn_debug_stack_mode(0, ...), for hidden <= 32
+     * and for hidden > 128 the groups are ignored and the table alone is used.  num_groups == 0: no groups.  A block's arithmetic
+     * depends on the table only: results are bit-identical to one launch over the same table. */
+    const int* block_starts; int num_blocks; const int* group_starts /* HOST */; int num_groups;
+    /* norm stack (see hexgnn_sage_norm_stack_forward below): nw / nb = HOST arrays of the norms' weight / bias; both NULL = the
+     * plain stack.  Set, the call takes no table, no groups, no tap_out and no flags (HEXGNN_EINVAL), and hidden <= 128.  pre
+     * [L][n][HP], stats [L][2], norm_ws (hexgnn_graph_layernorm_workspace_bytes).  n_live (forward, or NULL; need_backward must
+     * then be 0): forward-only over capacity-sized buffers -- the SAGE layers run over all n rows (rowptr must describe empty
+     * rows behind the live ones), every norm's statistics cover the first *n_live rows only */
+    const float* const* nw; const float* const* nb; float eps; float* pre; float* stats; void* norm_ws; size_t norm_ws_bytes;
+    const int* n_live;
+    /* backward: dy, dx and d_wl / d_bl / d_wr (HOST arrays) as in hexgnn_sage_stack_backward, d_nw / d_nb (HOST arrays) the norm
+     * stack's.  TAP: tap_out [n][HP] (may be NULL) receives the gradient w.r.t. the OUTPUT of layer tap_layer
+     * (0 <= tap_layer < num_layers - 1, checked before anything is launched) -- DuellingTwoHeaded's final_conv_grads when body
+     * and head layers run as one stack (GN0/models.py:553-554: embeds.register_hook) */
+    const float* dy; float* dx; float* const* d_wl; float* const* d_bl; float* const* d_wr; float* const* d_nw;
+    float* const* d_nb; int tap_layer; float* tap_out;
+} hexgnn_sage_stack_call;
+int hexgnn_sage_stack_call_forward(const hexgnn_sage_stack_call* call, hexgnn_stream_t stream);
+int hexgnn_sage_stack_call_backward(const hexgnn_sage_stack_call* call, hexgnn_stream_t stream);
 
 /* ---- head tail: HeadNetwork.forward after its gnn (GN0/models.py:374-384), MLP value head
  *      (GN0/models.py:36-82: Linear(4H,H/2) -> relu -> Linear(H/2,1)) and the dueling combine of
@@ -344,14 +345,6 @@ int hexgnn_sage_norm_stack_forward(int n, int c_in, int hidden, int num_layers, 
                                    const float* const* nb, float eps, void* wpack, float* pre, float* acts, void* saved,
                                    float* stats, void* norm_ws, size_t norm_ws_bytes, int need_backward,
                                    hexgnn_stream_t stream);
-/* Forward-only (need_backward must be 0 when n_live is given) over capacity-sized buffers: the SAGE layers run over all n rows
- * (rowptr must describe empty rows behind the live ones), every norm's statistics cover the first *n_live rows only. */
-int hexgnn_sage_norm_stack_forward_live(int n, const int* n_live, int c_in, int hidden, int num_layers, const int* rowptr,
-                                        const int* col, const float* invdeg, const float* x, int x_stride,
-                                        const float* const* wl, const float* const* bl, const float* const* wr,
-                                        const float* const* nw, const float* const* nb, float eps, void* wpack, float* pre,
-                                        float* acts, void* saved, float* stats, void* norm_ws, size_t norm_ws_bytes,
-                                        int need_backward, hexgnn_stream_t stream);
 size_t hexgnn_sage_norm_stack_backward_workspace_bytes(int n, int c_in, int hidden, int num_layers);
 int hexgnn_sage_norm_stack_backward(int n, int c_in, int hidden, int num_layers, const int* rowptr_t, const int* col_t,
                                     const float* invdeg, const float* x, int x_stride, const float* pre,

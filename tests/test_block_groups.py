@@ -1,4 +1,4 @@
-"""Groups of a row-block table (data.block_groups / pack_groups, hexgnn_sage_stack_*_groups): a batch whose table has more
+"""Groups of a row-block table (data.block_groups / pack_groups, hexgnn_sage_stack_call.group_starts): a batch whose table has more
 blocks than can be resident at once runs the one-launch stack kernels group after group, each group a range of blocks that
 holds whole graphs.  Host side only: the cutting, and the entry points' argument checks (made before the device is touched)."""
 import ctypes
@@ -134,12 +134,13 @@ def test_group_lists_are_validated_on_the_host(direction):
     one = ctypes.c_void_p(16)                 # (nor any other pointer)
 
     def call(block_starts, num_blocks, group_starts, num_groups):
-        if direction == "forward":
-            return L.hexgnn_sage_stack_forward_groups(640, 110, 110, 3, one, one, one, one, 112, None, None, None, one, one, one,
-                                                      1, 0, block_starts, num_blocks, group_starts, num_groups, None)
-        return L.hexgnn_sage_stack_backward_groups(640, 110, 110, 3, one, one, one, one, one, one, 112, one, one, one, one, None,
-                                                   one, one, one, one, 1 << 30, 0, -1, None, block_starts, num_blocks,
-                                                   group_starts, num_groups, None)
+        ptrs = {name: one for name, kind in _lib.SageStackCall._fields_ if kind is ctypes.c_void_p}
+        d = _lib.SageStackCall(**dict(
+            ptrs, struct_bytes=_lib.SAGE_STACK_CALL_BYTES, n=640, c_in=110, hidden=110, num_layers=3, x_stride=112, need_backward=1,
+            flags=0, wl=None, bl=None, wr=None, workspace_bytes=1 << 30, nw=None, nb=None, n_live=None, dx=None, tap_layer=-1,
+            tap_out=None, block_starts=ctypes.cast(block_starts, ctypes.c_void_p), num_blocks=num_blocks,
+            group_starts=ctypes.cast(group_starts, ctypes.c_void_p), num_groups=num_groups))
+        return (L.hexgnn_sage_stack_call_forward if direction == "forward" else L.hexgnn_sage_stack_call_backward)(d, None)
 
     assert call(None, 0, _ints([0, 5]), 1) == -1                      # groups without a table
     assert call(table, 5, None, 2) == -1                              # ... without a list

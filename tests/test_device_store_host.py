@@ -26,7 +26,7 @@ def test_new_symbols_are_declared_and_exported():
     for name, struct in (("hexgnn_transitions_assemble", "hexgnn_transitions_call"), ("hexgnn_replay_store_dev", "hexgnn_store_call")):
         assert re.search(r"\bint\s+%s\s*\(\s*const\s+%s\s*\*" % (name, struct), header), name
         assert hasattr(raw, name) and name in _lib.exported_symbols()
-    assert L.hexgnn_abi_version() == 7 and re.search(r"#define\s+HEXGNN_ABI_VERSION\s+7\b", header)
+    assert L.hexgnn_abi_version() == 8 and re.search(r"#define\s+HEXGNN_ABI_VERSION\s+8\b", header)
     # the header names the reference code the new entry points replace
     assert "graph_game/multi_env_manager.py:113-165" in header[header.index("rollout -> replay without the host"):]
 

@@ -1,5 +1,5 @@
 """The one-launch SAGE stack kernels on batches with more row blocks than can be resident at once: the table's blocks run in
-groups of whole graphs, one launch per group and direction (hexgnn_sage_stack_*_groups, data.block_groups / pack_groups).
+groups of whole graphs, one launch per group and direction (hexgnn_sage_stack_call.group_starts, data.block_groups / pack_groups).
 
 The budget is driven down with hexgnn_stack_reserve_cus so that small batches need groups: the 63-graph Hex-5..13 list has 63
 blocks in the caller's order and runs as three groups under a budget of 24.  A block's arithmetic depends on the table only,

@@ -1,4 +1,4 @@
-"""Graph-aligned row blocks for the one-launch SAGE stack kernels (hexgnn_sage_stack_*_blocks, data.pack_order).
+"""Graph-aligned row blocks for the one-launch SAGE stack kernels (hexgnn_sage_stack_call.block_starts, data.pack_order).
 
 * a packed MIX batch with its block table gives the Q-values and gradients of the same batch on the default 128-row blocks
   (and of the per-graph reference order, graph by graph through ``batch.order``) to fp32 rounding, bit-identically run to run,

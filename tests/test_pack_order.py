@@ -1,6 +1,6 @@
 """gnn_hex_amd.data.pack_order: the graph order + row-block table of a packed batch (host logic, no GPU).
 
-Properties the one-launch stack kernels rely on (include/hexgnn.h, hexgnn_sage_stack_forward_blocks): the blocks partition the
+Properties the one-launch stack kernels rely on (include/hexgnn.h, hexgnn_sage_stack_call.block_starts): the blocks partition the
 rows, none is longer than 128, and only graphs above 128 rows are cut -- at their own multiples of 128."""
 import random
 

@@ -85,7 +85,7 @@ def test_setup_call_is_declared_exported_and_mirrored():
     assert re.search(r"\bint\s+hexgnn_board_values\s*\(\s*int\s+b\s*,\s*int\s+hex_size\s*,\s*const\s+int\s*\*\s*gptr", header)
     for name in ("hexgnn_env_setup", "hexgnn_board_values"):
         assert hasattr(raw, name) and name in _lib.exported_symbols()
-    assert _lib.lib().hexgnn_abi_version() == 7
+    assert _lib.lib().hexgnn_abi_version() == 8
     m = re.search(r"typedef\s+struct\s+hexgnn_setup_call\s*\{(.*?)\}\s*hexgnn_setup_call\s*;", header, re.S)
     kinds = {"size_t": ctypes.c_size_t, "int": ctypes.c_int}
     want = []

@@ -1,12 +1,13 @@
 // Acting on Q-values, one wave per graph: epsilon-greedy / argmax action selection and the double-DQN targets, with their C
-// entry points.  Both pick "the greedy node" with graph_first_max (hexgnn_reduce.h).
+// entry points.  Both pick "the greedy node" with graph_first_max, and the selection explores with eps_greedy_rank, the pick
+// rollout_ply_kernel (env.hip) makes as well (both in hexgnn_reduce.h).
 #include "hexgnn_reduce.h"
 
 namespace hexgnn {
 
 // Greedy = first node attaining the maximum of q[gptr[g]+2 : gptr[g+1]] (torch.argmax tie rule;
-// GN0/RainbowDQN/evaluate_elo.py:253-266); with u given, env g explores when u[2g] < eps and then plays node
-// 2 + floor(u[2g+1] * (n_g - 2)).  Outputs the node rank inside its graph, the vertex id (backmap, what
+// GN0/RainbowDQN/evaluate_elo.py:253-266); with u given, env g explores by eps_greedy_rank on its pair u[2g], u[2g+1] (a
+// uniformly drawn non-terminal node with probability eps).  Outputs the node rank inside its graph, the vertex id (backmap, what
 // Env_manager.validate_actions returns, multi_env_manager.py:62-64) and the exploratory flag.
 __global__ __launch_bounds__(64) void select_actions_kernel(int b, const int* __restrict__ gptr, const float* __restrict__ q,
                                                           const int64_t* __restrict__ backmap, float eps,
@@ -18,15 +19,8 @@ __global__ __launch_bounds__(64) void select_actions_kernel(int b, const int* __
     int arg;
     graph_first_max(q, r0, r1, lane, best, arg);
     if (lane == 0) {
-        int rank = arg == 0x7fffffff ? -1 : arg - r0;      // -1: graph without a legal move
-        unsigned char ex = 0;
-        const int nact = r1 - r0 - 2;
-        if (u && nact > 0 && u[2 * g] < eps) {
-            int k = (int)(u[2 * g + 1] * (float)nact);
-            if (k >= nact) k = nact - 1;
-            rank = 2 + k;
-            ex = 1;
-        }
+        unsigned char ex;
+        const int rank = eps_greedy_rank(arg, r0, r1, eps, u ? u + 2 * g : nullptr, ex);
         act_rank[g] = rank;
         if (act_vertex) act_vertex[g] = rank >= 0 ? (backmap ? (int)backmap[r0 + rank] : rank) : -1;
         if (expl) expl[g] = ex;

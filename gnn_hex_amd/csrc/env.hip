@@ -13,6 +13,16 @@
 // (Hex-11: 123 x 2 x 8 B = 2 KB), lane l owns vertices l, l+64, ...; set algebra is word-parallel, "is this set a
 // clique" / "find the twin" are per-lane tests combined with wave ballots.  Integer/bit work: no MFMA, bound by LDS
 // latency; results are bit-exact against oracle/env_ref.c (same canonical ascending order).
+//
+// The per-env kernels (env_step_kernel, arena_ply_kernel, rollout_ply_kernel, env_setup_kernel) are built from one copy of each
+// piece: load_game / store_game (write_game: the env and, for the rollout and the set-up, a snapshot), play_vertex, play_move
+// (legality, the move, the restart of a decided game, the counts), restart_game, put_result; the rollout's pick is
+// eps_greedy_rank of hexgnn_reduce.h, the one select_actions_kernel makes.  A kernel holds what is its own: the arena's resting
+// games, forced entries and record, the rollout's schedule and action outputs, the set-up's stone loop.  Every workgroup is one
+// wave and v, err and the winner are uniform over it; load_game, reset_game_lds, write_game and the GameT primitives hold
+// barriers, so nothing lane-dependent may guard a call of them.  On the host one dispatcher picks the instantiation
+// (dispatch_words) and one launcher raises the LDS limit and launches (launch_boards), for these kernels and the observation.
+#include <type_traits>
 #include <vector>
 #include "hexgnn_reduce.h"
 
@@ -37,7 +47,7 @@ struct Env {   // host handle
 };
 
 // WT = compile-time number of 64-bit words per vertex set.  WT < kMaxW instantiations are launched only for boards with
-// exactly W == WT words (hexgnn_env_step's switch), so Wr() is the constant WT there (register-resident sets, row strides
+// exactly W == WT words (dispatch_words), so Wr() is the constant WT there (register-resident sets, row strides
 // and word loops fully unrolled); WT == kMaxW is the generic fallback with the runtime W.
 template <int WT> struct SetsT { uint64_t w[WT]; };
 
@@ -398,12 +408,19 @@ __device__ __forceinline__ void load_game(G& g, const EnvDev& d, int env, char* 
     for (int i = threadIdx.x; i < d.nv; i += 64) g.alive[i] = d.alive[(size_t)env * d.nv + i];
     __syncthreads();
 }
+// the LDS game written to adj [nv][W] / alive [nv] and, where given, to a second pair: one pass, every LDS word read once
 template <class G>
-__device__ __forceinline__ void store_game(const G& g, const EnvDev& d, int env) {
+__device__ __forceinline__ void write_game(const G& g, uint64_t* adj, uint8_t* alive, uint64_t* adj2 = nullptr,
+                                           uint8_t* alive2 = nullptr) {
     __syncthreads();
-    uint64_t* dst = d.adj + (size_t)env * d.nv * d.W;
-    for (int i = threadIdx.x; i < d.nv * d.W; i += 64) dst[i] = g.adj[i];
-    for (int i = threadIdx.x; i < d.nv; i += 64) d.alive[(size_t)env * d.nv + i] = g.alive[i];
+    for (int i = threadIdx.x; i < g.nv * g.W; i += 64) { const uint64_t w = g.adj[i]; adj[i] = w; if (adj2) adj2[i] = w; }
+    for (int i = threadIdx.x; i < g.nv; i += 64) { const uint8_t al = g.alive[i]; alive[i] = al; if (alive2) alive2[i] = al; }
+}
+// the game back into its env and, where given, into a snapshot slot snap_adj [nv][W] / snap_alive [nv]
+template <class G>
+__device__ __forceinline__ void store_game(const G& g, const EnvDev& d, int env, uint64_t* snap_adj = nullptr,
+                                           uint8_t* snap_alive = nullptr) {
+    write_game(g, d.adj + (size_t)env * d.nv * d.W, d.alive + (size_t)env * d.nv, snap_adj, snap_alive);
 }
 template <class G>
 __device__ __forceinline__ void reset_game_lds(G& g, const EnvDev& d) {
@@ -412,6 +429,12 @@ __device__ __forceinline__ void reset_game_lds(G& g, const EnvDev& d) {
     for (int i = threadIdx.x; i < d.nv; i += 64) g.alive[i] = 1;
     g.maker_won = false;
     __syncthreads();
+}
+// a new game: the start position in LDS, both response tables of the env (rm, rb: its rows of resp_maker / resp_breaker) empty
+template <class G>
+__device__ __forceinline__ void restart_game(G& g, const EnvDev& d, short* rm, short* rb) {
+    reset_game_lds(g, d);
+    for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
 }
 // alive count and directed edge count (uniform)
 template <class G>
@@ -429,8 +452,8 @@ __device__ __forceinline__ void count_game(const G& g, int* n_alive, int* n_dir_
 }
 
 // make_move(v) of the side `mt` on the LDS-resident game (the maker's rewiring, v's removal, dead/captured removal over what the
-// move touched), the side flag flipped, who_won returned.  The one copy behind env_step_kernel, arena_ply_kernel and
-// rollout_ply_kernel, which promise each other's bits.
+// move touched), the side flag flipped, who_won returned.  Called by play_move for the side on turn and by env_setup_kernel's
+// stone loop with forced colours.
 template <int WT>
 __device__ __forceinline__ int play_vertex(GameT<WT>& g, int v, int& mt, bool remove_dc, short* rm, short* rb) {
     typename GameT<WT>::Sets consider;
@@ -444,6 +467,42 @@ __device__ __forceinline__ int play_vertex(GameT<WT>& g, int v, int& mt, bool re
     mt = !mt;
     if (remove_dc && !g.maker_won) g.dead_and_captured(consider, rm, rb);
     return g.who_won();
+}
+
+// One move of the side on turn in env `env`, the one copy behind env_step_kernel, arena_ply_kernel and rollout_ply_kernel, which
+// promise each other's bits: vertex v is tested (only when no error came in; 1 = no playable vertex of this game), counted and
+// played, a decided game is restarted when auto_reset says so, and the game left in LDS is counted.  winner is -1 / 0 / 1, length
+// the move count before any restart, mt and moves what the env holds from here on.  v, err_in and the winner are uniform over the
+// wave, so every barrier below is taken by all 64 lanes: call it from uniform control flow only.
+struct Move { int winner, length, err, mt, moves, n_alive, n_dir_edges; };
+
+template <int WT>
+__device__ __forceinline__ Move play_move(GameT<WT>& g, const EnvDev& d, int env, int v, int err_in, bool remove_dc,
+                                          bool auto_reset, int reset_maker_turn) {
+    short* rm = d.resp_maker + (size_t)env * d.nv;
+    short* rb = d.resp_breaker + (size_t)env * d.nv;
+    Move m;
+    m.err = err_in; m.mt = d.maker_turn[env]; m.moves = d.total_moves[env]; m.winner = -1;
+    if (!m.err && (v < 2 || v >= d.nv || !g.alive[v])) m.err = 1;
+    if (!m.err) {
+        ++m.moves;
+        m.winner = play_vertex(g, v, m.mt, remove_dc, rm, rb);
+    }
+    m.length = m.moves;
+    if (m.winner >= 0 && auto_reset) {
+        restart_game(g, d, rm, rb);
+        m.mt = reset_maker_turn;
+        m.moves = 0;
+    }
+    count_game(g, &m.n_alive, &m.n_dir_edges);
+    return m;
+}
+
+// one lane: the env's side flag and move count, and its result record [winner(-1/0/1), length, n_alive, n_directed_edges, error]
+__device__ __forceinline__ void put_result(const EnvDev& d, int env, int* result, const Move& m) {
+    d.maker_turn[env] = m.mt; d.total_moves[env] = m.moves;
+    int* res = result + 5 * env;
+    res[0] = m.winner; res[1] = m.length; res[2] = m.n_alive; res[3] = m.n_dir_edges; res[4] = m.err;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -478,36 +537,13 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev d, const int* __res
     const int env = blockIdx.x;
     GameT<WT> g;
     load_game(g, d, env, lds);
-    short* rm = d.resp_maker + (size_t)env * d.nv;
-    short* rb = d.resp_breaker + (size_t)env * d.nv;
-    int* res = result + 5 * env;
-    const int v = actions[env];
-    int err = 0;
-    if (v < 2 || v >= d.nv || !g.alive[v]) err = 1;
-    int mt = d.maker_turn[env], moves = d.total_moves[env];
-    int winner = -1;
-    if (!err) {
-        ++moves;
-        winner = play_vertex(g, v, mt, remove_dc != 0, rm, rb);
-    }
-    int length = moves;
-    if (winner >= 0 && auto_reset) {
-        reset_game_lds(g, d);
-        for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
-        mt = reset_maker_turn;
-        moves = 0;
-    }
-    int na, ne;
-    count_game(g, &na, &ne);
+    const Move m = play_move(g, d, env, actions[env], 0, remove_dc != 0, auto_reset != 0, reset_maker_turn);
     store_game(g, d, env);
-    if (threadIdx.x == 0) {
-        d.maker_turn[env] = mt; d.total_moves[env] = moves;
-        res[0] = winner; res[1] = length; res[2] = na; res[3] = ne; res[4] = err;
-    }
+    if (threadIdx.x == 0) put_result(d, env, result, m);
 }
 
-// One ply of a match (include/hexgnn.h: hexgnn_arena_ply): pick with graph_pick, play the vertex exactly as env_step_kernel does
-// with dead/captured removal and auto reset, and keep the game's record.  A decided game rests: only its side flag flips.
+// One ply of a match (include/hexgnn.h: hexgnn_arena_ply): pick with graph_pick, play the vertex with play_move (dead/captured
+// removal and auto reset), and keep the game's record.  A decided game rests: only its side flag flips.
 template <int WT>
 __global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __restrict__ gptr, const float* __restrict__ q,
                                                      const int64_t* __restrict__ backmap, int mode, float temperature,
@@ -519,20 +555,15 @@ __global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __re
     GameT<WT> g;
     load_game(g, d, env, lds);
     int* rec = game + 4 * env;
-    int* res = result + 5 * env;
-    int mt = d.maker_turn[env], moves = d.total_moves[env];
     if (rec[0] >= 0 || rec[3] != 0) {                         // resting: nothing but the side flag and the sizes
-        int na, ne;
-        count_game(g, &na, &ne);
+        Move rest = {-1, 0, 0, !d.maker_turn[env], d.total_moves[env], 0, 0};
+        count_game(g, &rest.n_alive, &rest.n_dir_edges);
         if (lane == 0) {
-            d.maker_turn[env] = !mt;
+            put_result(d, env, result, rest);
             log_row[env] = -1;
-            res[0] = -1; res[1] = 0; res[2] = na; res[3] = ne; res[4] = 0;
         }
-        return;
+        return;                                               // the whole wave, ahead of every barrier of play_move
     }
-    short* rm = d.resp_maker + (size_t)env * d.nv;
-    short* rb = d.resp_breaker + (size_t)env * d.nv;
     int v = forced ? forced[env] : -1;
     int err = 0;
     if (v >= 2) {
@@ -545,35 +576,22 @@ __global__ __launch_bounds__(64) void arena_ply_kernel(EnvDev d, const int* __re
         v = rank >= 0 ? (int)backmap[r0 + rank] : -1;
         if (bad) err = 2;
     }
-    if (!err && (v < 2 || v >= d.nv || !g.alive[v])) err = 1;
-    int winner = -1;
-    if (!err) {
-        ++moves;
-        winner = play_vertex(g, v, mt, true, rm, rb);
-    }
-    const int length = moves;
-    if (winner >= 0) {
-        reset_game_lds(g, d);
-        for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
-        mt = reset_maker_turn;
-        moves = 0;
-    }
-    int na, ne;
-    count_game(g, &na, &ne);
+    Move m = play_move(g, d, env, v, err, true, true, reset_maker_turn);
     store_game(g, d, env);
     if (lane == 0) {
-        d.maker_turn[env] = mt; d.total_moves[env] = moves;
-        res[0] = winner; res[1] = length; res[2] = na; res[3] = ne; res[4] = err ? 1 : 0;
-        if (winner >= 0) { rec[0] = winner; rec[1] = length; }
-        if (!err) rec[2] += 1;
-        rec[3] = err;
+        if (m.winner >= 0) { rec[0] = m.winner; rec[1] = m.length; }
+        if (!m.err) rec[2] += 1;
+        rec[3] = m.err;                                       // the record keeps graph_pick's 2, the result says 0 / 1
         log_row[env] = v;
-        if (winner < 0 && !err) atomicAdd(live, 1);
+        if (m.winner < 0 && !m.err) atomicAdd(live, 1);
+        m.err = m.err ? 1 : 0;
+        put_result(d, env, result, m);
     }
 }
 
-// One ply of self-play (include/hexgnn.h: hexgnn_rollout_ply): select_actions_kernel's pick with epsilon read from the device,
-// env_step_kernel's move with dead/captured removal and auto reset, and the board snapshot of env_export_kernel, per env.
+// One ply of self-play (include/hexgnn.h: hexgnn_rollout_ply): select_actions_kernel's pick (graph_first_max, eps_greedy_rank)
+// with epsilon read from the device, play_move with dead/captured removal and auto reset, and the board snapshot of
+// env_export_kernel, per env.
 struct RolloutPly {
     const int* gptr;
     const float* q;
@@ -610,56 +628,20 @@ __global__ __launch_bounds__(64) void rollout_ply_kernel(EnvDev d, RolloutPly a)
     const int env = blockIdx.x, lane = threadIdx.x;
     GameT<WT> g;
     load_game(g, d, env, lds);
-    short* rm = d.resp_maker + (size_t)env * d.nv;
-    short* rb = d.resp_breaker + (size_t)env * d.nv;
-    int* res = a.result + 5 * env;
     const float eps = schedule_eps(a.sched, a.frames[0] + a.frame_add);
     // the pick of select_actions_kernel (every lane holds it)
     const int r0 = a.gptr[env], r1 = a.gptr[env + 1];
     float best;
     int arg;
     graph_first_max(a.q, r0, r1, lane, best, arg);
-    int rank = arg == 0x7fffffff ? -1 : arg - r0;          // -1: graph without a legal move
-    unsigned char ex = 0;
-    const int nact = r1 - r0 - 2;
-    if (nact > 0 && a.u[2 * env] < eps) {
-        int k = (int)(a.u[2 * env + 1] * (float)nact);
-        if (k >= nact) k = nact - 1;
-        rank = 2 + k;
-        ex = 1;
-    }
+    unsigned char ex;
+    const int rank = eps_greedy_rank(arg, r0, r1, eps, a.u + 2 * env, ex);
     const int v = rank >= 0 ? (int)a.backmap[r0 + rank] : -1;
-    // the move of env_step_kernel with remove_dc = 1, auto_reset = 1
-    int err = 0;
-    if (v < 2 || v >= d.nv || !g.alive[v]) err = 1;
-    int mt = d.maker_turn[env], moves = d.total_moves[env];
-    int winner = -1;
-    if (!err) {
-        ++moves;
-        winner = play_vertex(g, v, mt, true, rm, rb);
-    }
-    const int length = moves;
-    if (winner >= 0) {
-        reset_game_lds(g, d);
-        for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
-        mt = a.reset_maker_turn;
-        moves = 0;
-    }
-    int na, ne;
-    count_game(g, &na, &ne);
+    const Move m = play_move(g, d, env, v, 0, true, true, a.reset_maker_turn);
     // the game and its snapshot from the one LDS copy
-    __syncthreads();
-    uint64_t* dst = d.adj + (size_t)env * d.nv * d.W;
-    uint64_t* snap = a.adj_out + (size_t)env * d.nv * d.W;
-    for (int i = threadIdx.x; i < d.nv * d.W; i += 64) { const uint64_t w = g.adj[i]; dst[i] = w; snap[i] = w; }
-    for (int i = threadIdx.x; i < d.nv; i += 64) {
-        const uint8_t al = g.alive[i];
-        d.alive[(size_t)env * d.nv + i] = al;
-        a.alive_out[(size_t)env * d.nv + i] = al;
-    }
+    store_game(g, d, env, a.adj_out + (size_t)env * d.nv * d.W, a.alive_out + (size_t)env * d.nv);
     if (lane == 0) {
-        d.maker_turn[env] = mt; d.total_moves[env] = moves;
-        res[0] = winner; res[1] = length; res[2] = na; res[3] = ne; res[4] = err;
+        put_result(d, env, a.result, m);
         a.act_rank[env] = rank; a.act_vertex[env] = v; a.expl[env] = ex;
         if (env == 0 && a.eps_out) a.eps_out[0] = eps;
     }
@@ -693,8 +675,7 @@ __global__ __launch_bounds__(64) void env_setup_kernel(EnvDev d, SetupArgs a) {
     int mt = d.maker_turn[env], moves = d.total_moves[env];
     int winner = -1;
     if (a.from_start) {
-        reset_game_lds(g, d);
-        for (int i = lane; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
+        restart_game(g, d, rm, rb);
         mt = a.maker_turn_start;
         moves = 0;
     } else {
@@ -719,16 +700,13 @@ __global__ __launch_bounds__(64) void env_setup_kernel(EnvDev d, SetupArgs a) {
             int na = 0, ne = 0;
             if (winner < 0) {
                 count_game(g, &na, &ne);
-                uint64_t* sa = a.adj_out + slot * d.nv * d.W;
-                for (int i = lane; i < d.nv * d.W; i += 64) sa[i] = g.adj[i];
-                for (int i = lane; i < d.nv; i += 64) a.alive_out[slot * d.nv + i] = g.alive[i];
+                write_game(g, a.adj_out + slot * d.nv * d.W, a.alive_out + slot * d.nv);
             }
             if (lane == 0) { a.side_out[slot] = (uint8_t)mt; a.sizes_out[2 * slot] = na; a.sizes_out[2 * slot + 1] = ne; }
         }
     }
     if (err) {                                                // the env goes back to the start position
-        reset_game_lds(g, d);
-        for (int i = lane; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
+        restart_game(g, d, rm, rb);
         mt = a.maker_turn_start;
         moves = 0;
         winner = -1;
@@ -741,13 +719,11 @@ __global__ __launch_bounds__(64) void env_setup_kernel(EnvDev d, SetupArgs a) {
             a.side_out[slot] = (uint8_t)mt; a.sizes_out[2 * slot] = 0; a.sizes_out[2 * slot + 1] = 0;
         }
     }
-    int na, ne;
-    count_game(g, &na, &ne);
+    Move m = {winner, moves, err, mt, moves, 0, 0};
+    count_game(g, &m.n_alive, &m.n_dir_edges);
     store_game(g, d, env);
     if (lane == 0) {
-        d.maker_turn[env] = mt; d.total_moves[env] = moves;
-        int* res = a.result + 5 * env;
-        res[0] = winner; res[1] = moves; res[2] = na; res[3] = ne; res[4] = err;
+        put_result(d, env, a.result, m);
         a.applied[env] = done;
     }
 }
@@ -895,60 +871,51 @@ __global__ void env_set_turn_kernel(EnvDev d, int maker_turn) {
     if (i < d.num_envs) d.maker_turn[i] = maker_turn;
 }
 
-static size_t env_lds_bytes(const EnvDev& d) {
-    size_t b = sizeof(uint64_t) * ((size_t)d.nv * d.W + 4 * kMaxW);
-    b += (size_t)((d.nv + 15) / 16) * 16;                 // alive
-    b += sizeof(short) * (size_t)((d.nv + 7) / 8) * 8;    // rank
-    b += sizeof(int) * 2 * (size_t)d.nv;                  // lowoff, rowoff
+static size_t env_lds_bytes(int nv, int W) {
+    size_t b = sizeof(uint64_t) * ((size_t)nv * W + 4 * kMaxW);
+    b += (size_t)((nv + 15) / 16) * 16;                   // alive
+    b += sizeof(short) * (size_t)((nv + 7) / 8) * 8;      // rank
+    b += sizeof(int) * 2 * (size_t)nv;                    // lowoff, rowoff
     return align_up(b, 16);
 }
 
-template <int WT>
-static void launch_env_step(const EnvDev& d, const int* actions, int remove_dc, int auto_reset, int reset_maker_turn,
-                            int* result, hipStream_t st) {
-    static bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&env_step_kernel<WT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        return true;
-    }();
-    (void)once;
-    env_step_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, actions, remove_dc, auto_reset, reset_maker_turn, result);
+// f(std::integral_constant<int, WT>) for the board's word count: vertex sets as compile-time register arrays for the common
+// board sizes (W = ceil((n*n+2)/64): Hex <= 7: 1, Hex 8-11: 2, Hex 12-13: 3, Hex 14-15: 4); larger boards take the generic
+// runtime-W instantiation
+template <class F>
+static void dispatch_words(int W, F&& f) {
+    switch (W) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, kMaxW>{}); break;
+    }
 }
 
-template <int WT>
-static void launch_arena_ply(const EnvDev& d, const int* gptr, const float* q, const int64_t* backmap, int mode, float temperature,
-                             const float* u, int* forced, int reset_maker_turn, int* game, int* log_row, int* result, int* live,
-                             hipStream_t st) {
+// One 64-thread workgroup per board with the LDS of an nv x W game; the kernel's dynamic-LDS limit is raised to 64 KiB at the
+// first launch of each instantiation.
+template <auto Kernel, class... Args>
+static void launch_boards(int boards, int nv, int W, hipStream_t st, const Args&... args) {
     static bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&arena_ply_kernel<WT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         return true;
     }();
     (void)once;
-    arena_ply_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, gptr, q, backmap, mode, temperature, u, forced,
-                                                                    reset_maker_turn, game, log_row, result, live);
+    Kernel<<<boards, 64, env_lds_bytes(nv, W), st>>>(args...);
 }
-
-template <int WT>
-static void launch_rollout_ply(const EnvDev& d, const RolloutPly& a, hipStream_t st) {
-    static bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_ply_kernel<WT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        return true;
-    }();
-    (void)once;
-    rollout_ply_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, a);
+// a per-env kernel, Kernel(EnvDev, args...), over the handle's envs
+template <auto Kernel, class... Args>
+static void launch_envs(const EnvDev& d, hipStream_t st, const Args&... args) {
+    launch_boards<Kernel>(d.num_envs, d.nv, d.W, st, d, args...);
 }
-
-template <int WT>
-static void launch_env_setup(const EnvDev& d, const SetupArgs& a, hipStream_t st) {
-    static bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&env_setup_kernel<WT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        return true;
-    }();
-    (void)once;
-    env_setup_kernel<WT><<<d.num_envs, 64, env_lds_bytes(d), st>>>(d, a);
+// the batched observation of k of src's states (hexgnn_env_observe, hexgnn_states_observe)
+static int launch_observe(const StateSrc& src, int k, const int* node_off, const int* edge_off, int64_t e_total, float* x,
+                          int64_t* backmap, int64_t* edge_local, int64_t* edge_global, int* rowptr, int* col, float* invdeg,
+                          int64_t* batch_vec, hipStream_t st) {
+    launch_boards<&env_observe_kernel>(k, src.nv, src.W, st, src, node_off, edge_off, x, backmap, edge_local, edge_global, e_total,
+                                       rowptr, col, invdeg, batch_vec, 1);
+    return check_launch();
 }
 
 }  // namespace hexgnn
@@ -1056,15 +1023,9 @@ int hexgnn_env_step(hexgnn_env* h, const int* actions, int remove_dead_and_captu
     Env* e = reinterpret_cast<Env*>(h);
     hipStream_t st = (hipStream_t)stream_;
     const int rm = reset_maker_turn ? 1 : 0;
-    // vertex sets as compile-time register arrays for the common board sizes (W = ceil((n*n+2)/64): Hex <= 7: 1,
-    // Hex 8-11: 2, Hex 12-13: 3, Hex 14-15: 4); larger boards take the generic runtime-W instantiation
-    switch (e->d.W) {
-        case 1: launch_env_step<1>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
-        case 2: launch_env_step<2>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
-        case 3: launch_env_step<3>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
-        case 4: launch_env_step<4>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
-        default: launch_env_step<kMaxW>(e->d, actions, remove_dead_and_captured, auto_reset, rm, result, st); break;
-    }
+    dispatch_words(e->d.W, [&](auto wt) {
+        launch_envs<&env_step_kernel<decltype(wt)::value>>(e->d, st, actions, remove_dead_and_captured, auto_reset, rm, result);
+    });
     return check_launch();
 }
 
@@ -1080,13 +1041,10 @@ int hexgnn_arena_ply(hexgnn_env* h, const int* gptr, const float* q, const int64
     const hipError_t me = hipMemsetAsync(live, 0, sizeof(int), st);
     if (me != hipSuccess) { g_last_hip_error = (int)me; return HEXGNN_EHIP; }
     const int rm = reset_maker_turn ? 1 : 0;
-    switch (e->d.W) {          // as hexgnn_env_step: register-resident vertex sets for the common board sizes
-        case 1: launch_arena_ply<1>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
-        case 2: launch_arena_ply<2>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
-        case 3: launch_arena_ply<3>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
-        case 4: launch_arena_ply<4>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
-        default: launch_arena_ply<kMaxW>(e->d, gptr, q, backmap, mode, temperature, u, forced, rm, game, log_row, result, live, st); break;
-    }
+    dispatch_words(e->d.W, [&](auto wt) {
+        launch_envs<&arena_ply_kernel<decltype(wt)::value>>(e->d, st, gptr, q, backmap, mode, temperature, u, forced, rm, game,
+                                                            log_row, result, live);
+    });
     return check_launch();
 }
 
@@ -1104,13 +1062,7 @@ int hexgnn_rollout_ply(hexgnn_env* h, const hexgnn_rollout_call* c, hexgnn_strea
     a.frame_add = c->frame_add; a.reset_maker_turn = c->reset_maker_turn ? 1 : 0;
     a.act_vertex = c->action_vertex; a.act_rank = c->action_rank; a.expl = c->exploratory; a.result = c->result;
     a.adj_out = c->adj_out; a.alive_out = c->alive_out; a.eps_out = c->eps_out;
-    switch (e->d.W) {          // as hexgnn_env_step: register-resident vertex sets for the common board sizes
-        case 1: launch_rollout_ply<1>(e->d, a, st); break;
-        case 2: launch_rollout_ply<2>(e->d, a, st); break;
-        case 3: launch_rollout_ply<3>(e->d, a, st); break;
-        case 4: launch_rollout_ply<4>(e->d, a, st); break;
-        default: launch_rollout_ply<kMaxW>(e->d, a, st); break;
-    }
+    dispatch_words(e->d.W, [&](auto wt) { launch_envs<&rollout_ply_kernel<decltype(wt)::value>>(e->d, st, a); });
     return check_launch();
 }
 
@@ -1127,13 +1079,7 @@ int hexgnn_env_setup(hexgnn_env* h, const hexgnn_setup_call* c, hexgnn_stream_t 
     a.maker_turn_after = c->maker_turn_after;
     a.stones = c->stones; a.count = c->count; a.result = c->result; a.applied = c->applied;
     a.adj_out = c->adj_out; a.alive_out = c->alive_out; a.side_out = c->side_out; a.sizes_out = c->sizes_out;
-    switch (e->d.W) {          // as hexgnn_env_step: register-resident vertex sets for the common board sizes
-        case 1: launch_env_setup<1>(e->d, a, st); break;
-        case 2: launch_env_setup<2>(e->d, a, st); break;
-        case 3: launch_env_setup<3>(e->d, a, st); break;
-        case 4: launch_env_setup<4>(e->d, a, st); break;
-        default: launch_env_setup<kMaxW>(e->d, a, st); break;
-    }
+    dispatch_words(e->d.W, [&](auto wt) { launch_envs<&env_setup_kernel<decltype(wt)::value>>(e->d, st, a); });
     return check_launch();
 }
 
@@ -1149,19 +1095,10 @@ int hexgnn_env_observe(hexgnn_env* h, const int* node_off, const int* edge_off, 
     if (!h || !node_off || !edge_off || !x || !backmap || !edge_local || !edge_global || !rowptr || !col ||
         !invdeg || !batch_vec || e_total < 0)
         return HEXGNN_EINVAL;
-    Env* e = reinterpret_cast<Env*>(h);
-    static bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&env_observe_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        return true;
-    }();
-    (void)once;
-    StateSrc src;
-    src.nv = e->d.nv; src.W = e->d.W; src.K = e->d.K;
-    src.adj = e->d.adj; src.alive = e->d.alive; src.maker_turn = e->d.maker_turn; src.side_u8 = nullptr; src.index = nullptr;
-    env_observe_kernel<<<e->d.num_envs, 64, env_lds_bytes(e->d), (hipStream_t)stream_>>>(
-        src, node_off, edge_off, x, backmap, edge_local, edge_global, e_total, rowptr, col, invdeg, batch_vec, 1);
-    return check_launch();
+    const EnvDev& d = reinterpret_cast<Env*>(h)->d;
+    const StateSrc src = {d.nv, d.W, d.K, d.adj, d.alive, d.maker_turn, nullptr, nullptr};
+    return launch_observe(src, d.num_envs, node_off, edge_off, e_total, x, backmap, edge_local, edge_global, rowptr, col, invdeg,
+                          batch_vec, (hipStream_t)stream_);
 }
 
 int hexgnn_states_observe(int hex_size, int k, const uint64_t* adj, const uint8_t* alive, const uint8_t* side,
@@ -1174,20 +1111,9 @@ int hexgnn_states_observe(int hex_size, int k, const uint64_t* adj, const uint8_
     const int nv = hex_size * hex_size + 2, W = (nv + 63) / 64;
     if (W > kMaxW) return HEXGNN_EUNSUPPORTED;
     if (k == 0) return HEXGNN_OK;
-    static bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&env_observe_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        return true;
-    }();
-    (void)once;
-    EnvDev tmp;
-    tmp.nv = nv; tmp.W = W; tmp.K = (nv + 63) / 64;
-    StateSrc src;
-    src.nv = nv; src.W = W; src.K = tmp.K;
-    src.adj = adj; src.alive = alive; src.maker_turn = nullptr; src.side_u8 = side; src.index = index;
-    env_observe_kernel<<<k, 64, env_lds_bytes(tmp), (hipStream_t)stream_>>>(
-        src, node_off, edge_off, x, backmap, edge_local, edge_global, e_total, rowptr, col, invdeg, batch_vec, 1);
-    return check_launch();
+    const StateSrc src = {nv, W, (nv + 63) / 64, adj, alive, nullptr, side, index};
+    return launch_observe(src, k, node_off, edge_off, e_total, x, backmap, edge_local, edge_global, rowptr, col, invdeg,
+                          batch_vec, (hipStream_t)stream_);
 }
 
 int hexgnn_env_import(hexgnn_env* h, const uint64_t* adj, const uint8_t* alive, const int* maker_turn,

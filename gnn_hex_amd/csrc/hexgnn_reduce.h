@@ -50,6 +50,24 @@ __device__ __forceinline__ void graph_first_max(const float* q, int r0, int r1, 
     }
 }
 
+// The epsilon-greedy pick on top of graph_first_max's arg, for a graph of rows [r0, r1): the greedy node's rank inside the graph
+// (-1: graph without a legal move), or, when the graph's pair of uniforms u[0..1] is given (null: greedy only) and u[0] < eps,
+// the exploring rank 2 + min((int)(u[1] * nact), nact - 1) over its nact = r1 - r0 - 2 non-terminal rows, exploratory set.
+// No wave operation: select_actions_kernel calls it on lane 0, rollout_ply_kernel on every lane; one fp32 comparison, one
+// fp32 product, one truncation and the clamp, so both give the same bits.
+__device__ __forceinline__ int eps_greedy_rank(int arg, int r0, int r1, float eps, const float* u, unsigned char& exploratory) {
+    int rank = arg == 0x7fffffff ? -1 : arg - r0;
+    exploratory = 0;
+    const int nact = r1 - r0 - 2;
+    if (u && nact > 0 && u[0] < eps) {
+        int k = (int)(u[1] * (float)nact);
+        if (k >= nact) k = nact - 1;
+        rank = 2 + k;
+        exploratory = 1;
+    }
+    return rank;
+}
+
 // One wave: pick a node of a graph from its non-terminal rows [r0 + 2, r1) of q (nact = r1 - r0 - 2 of them).  Returns the node's
 // rank inside the graph (>= 2) in every lane; -1 for a graph without such a row, 2 for a graph with exactly one (in every mode,
 // GN0/RainbowDQN/evaluate_elo.py:255-257).  HEXGNN_PICK_*:

@@ -157,7 +157,7 @@ def _import_positions(hexref, mgr, size, k, maker):
 
 
 @pytest.mark.parametrize("maker", [True, False], ids=["maker", "breaker"])
-@pytest.mark.parametrize("size", [5, 7, 11, 13])
+@pytest.mark.parametrize("size", [5, 7, 11, 13, 14, 16])     # W = 1, 1, 2, 3, 4 and the generic instantiation
 def test_ply_kernel_equals_select_and_step_on_a_twin(hexref, size, maker):
     from gnn_hex_amd import _lib, ops
     from gnn_hex_amd.multi_env_manager import Env_manager

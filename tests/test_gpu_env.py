@@ -24,6 +24,18 @@ def _assert_env_equals_oracle(st, i, game):
     assert int(st["total_moves"][i]) == game.total_num_moves
 
 
+def _assert_responses_equal_oracle(st, i, game):
+    """Both response sets of env i (int16 [nv], -1 = none) against the oracle's; a game restarted by the step has none."""
+    want = np.full((2, game.nv), -1, dtype=np.int16)
+    for v in range(game.nv):
+        for row, for_maker in ((0, True), (1, False)):
+            r = game.get_response(v, for_maker)
+            if r is not None:
+                want[row, v] = r
+    assert np.array_equal(st["resp_maker"][i], want[0]), "maker response set differs (env %d)" % i
+    assert np.array_equal(st["resp_breaker"][i], want[1]), "breaker response set differs (env %d)" % i
+
+
 @pytest.mark.parametrize("size,num_envs,steps", [(5, 16, 40), (7, 32, 60), (11, 64, 80), (13, 8, 60), (15, 4, 170), (17, 3, 220),
                                                  (19, 2, 300), (25, 2, 520), (6, 8, 40), (3, 5, 12)])
 def test_lockstep_random_play_bit_exact(hexref, size, num_envs, steps):
@@ -48,6 +60,8 @@ def test_lockstep_random_play_bit_exact(hexref, size, num_envs, steps):
         st = mgr._state()
         for i in range(num_envs):
             _assert_env_equals_oracle(st, i, ref.envs[i])
+            if done[i] or t % 4 == 3 or t == steps - 1:     # every restarted game, every fourth step, the last one
+                _assert_responses_equal_oracle(st, i, ref.envs[i])
             if done[i]:
                 finished += 1
                 for k in ("return", "discounted_return", "length"):

@@ -84,7 +84,8 @@ def _assert_plies_equal(a, b, tag):
 
 @pytest.mark.parametrize("e", [0.0, 0.5, 1.0], ids=["greedy", "eps-half", "eps-one"])
 @pytest.mark.parametrize("k", [3, 70])
-@pytest.mark.parametrize("hex_size,nv,words", [(5, 27, 1), (8, 66, 2), (12, 146, 3)], ids=["hex5-W1", "hex8-W2", "hex12-W3"])
+@pytest.mark.parametrize("hex_size,nv,words", [(5, 27, 1), (8, 66, 2), (12, 146, 3), (14, 198, 4), (16, 258, 5)],
+                         ids=["hex5-W1", "hex8-W2", "hex12-W3", "hex14-W4", "hex16-generic"])
 def test_one_launch_equals_select_step_export(hex_size, nv, words, k, e):
     from gnn_hex_amd import _lib, ops
     from gnn_hex_amd.multi_env_manager import EpsSchedule

@@ -206,6 +206,13 @@ __device__ __forceinline__ void csr_grouped_body(int n, int e, int b, const int6
         ee = ok ? (int)a1 : 0;
     } else {
         csr_lower_bound2_256(dst, e, r0, r1, eb, ee);
+        // The searched ranges must tile [0, e) like the given ones, or an edge is seen by no workgroup and never validated: an
+        // edge with dst >= n behind the last graph's edges (dst < 0 in front of the first one's) lay outside every range and
+        // raised no status bit.  The result for a target depends on the target alone, so the ranges chain (ee of g == eb of
+        // g + 1); with both ends pinned they cover [0, e) unless one of them is reversed, which a grouped list never gives.
+        if (g == 0) eb = 0;
+        if (g == b - 1) ee = e;
+        if (ee < eb && tid == 0) atomicOr(status, 4);
     }
     const int ne = ee - eb;
     const bool in_lds = ne <= kCsrLdsEdges;

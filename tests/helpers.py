@@ -1425,3 +1425,19 @@ def policy_ref_run(inp, swap_allowed, dtype):
     if swap_allowed:
         d_ss = torch.zeros_like(ss) if ss.grad is None else ss.grad.detach().clone()
     return dict(pi=pi.detach(), gi=gi, ptr=optr, d_raw=raw.grad.detach().clone(), d_ss=d_ss)
+
+
+# ---- graph-structure kernels (csr.hip): the numpy reference of a sorted CSR + transpose ------------------------------------
+
+def csr_reference(src, dst, n):
+    """(rowptr, col, rowptr_t, col_t, invdeg) of the edge list src -> dst over n nodes, numpy only: row r of (rowptr, col) holds
+    the sources of the edges INTO r, ascending; (rowptr_t, col_t) the targets of the edges OUT OF r; invdeg = 1 / max(in-degree, 1)
+    in float32.  Multi-edges and self loops are kept, so the sorted result is unique and every comparison is array_equal."""
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    deg = np.bincount(dst, minlength=n).astype(np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    col = src[np.lexsort((src, dst))]
+    rowptr_t = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))]).astype(np.int64)
+    col_t = dst[np.lexsort((dst, src))]
+    invdeg = np.float32(1) / np.maximum(deg, 1).astype(np.float32)
+    return rowptr, col, rowptr_t, col_t, invdeg

@@ -3,11 +3,16 @@
     python examples/arena_eval.py --hex-size 11 --layers 15 --hidden 110            # two random-init (sharpened) GNN-L
     python examples/arena_eval.py --hex-size 7 --checkpoint a.pt b.pt --games 56     # two RainbowDQN checkpoints
     python examples/arena_eval.py --hex-size 11 --layers 15 --hidden 110 --compare 3 # arena vs the step loop, alternating
+    python examples/arena_eval.py --hex-size 7 --checkpoint a.pt b.pt --mc 16,64,256  # rate model A on a ladder of playout players
 
 The match is ``gnn_hex_amd.arena.Elo_handler.play_some_games``: two legs over the shuffled unique opening moves, the first
 model always playing maker.  ``--step-loop`` plays the same match with the calls that existed before the arena did
 (``Env_manager.observe`` -> model -> ``select_actions`` -> ``step``, one read-back per ply, the first finish of every env
 counted), which is what a user had to write by hand; at temperature 0 both give the same statistics.
+
+``--mc R[,R...]`` rates the first model against a ladder of Monte-Carlo playout players (``gnn_hex_amd.playouts.MonteCarloPlayer``,
+R playouts per move) beside ``random``: the ladder is rated first, from ``random`` = 0 upwards by each rung's match against the
+rung below, then the model gets its performance rating against all of them.
 """
 import argparse
 import os
@@ -125,6 +130,30 @@ def play_one(args, handler, models, mgrs, step_loop):
     return wins, 2 * per_leg, plies
 
 
+def rate_on_ladder(args, handler, model):
+    """``--mc``: the rating table of ``random``, the playout players and the model."""
+    from gnn_hex_amd.playouts import MonteCarloPlayer
+    rungs = sorted({int(r) for r in args.mc.split(",")})
+    handler.add_player("random", model="random", simple=True, set_rating=0, rating_fixed=True, uses_empty_model=False)
+    below = "random"
+    for i, r in enumerate(rungs):
+        name = "mc%d" % r
+        handler.add_player(name, model=MonteCarloPlayer(r, seed=args.seed + i), uses_empty_model=False)
+        stats = [handler.play_some_games(name, below, args.games, 0, progress=True),
+                 handler.play_some_games(below, name, args.games, 0, progress=True)]
+        handler.score_some_statistics(stats)            # an unrated player gets its performance rating
+        handler.players[name]["rating_fixed"] = True
+        below = name
+    handler.add_player("model", model=model, uses_empty_model=False)
+    stats = []
+    for name in ["random"] + ["mc%d" % r for r in rungs]:
+        stats.append(handler.play_some_games("model", name, args.games, args.temperature, progress=True))
+        stats.append(handler.play_some_games(name, "model", args.games, args.temperature, progress=True))
+    handler.score_some_statistics(stats)
+    for name, rating in handler.get_rating_table()[1]:
+        print("%-10s %8.1f" % (name, rating))
+
+
 def report(tag, wins, games, plies, dt):
     print("%-9s %s  %d games in %.3f s: %.1f games/s, %.1f plies/s" % (tag, wins, games, dt, games / dt, plies / dt), flush=True)
 
@@ -142,6 +171,8 @@ def main():
     ap.add_argument("--step-loop", action="store_true", help="play with observe / model / select_actions / step instead")
     ap.add_argument("--compare", type=int, default=0, metavar="N",
                     help="after a warm-up match of each, alternate arena and step loop N times and print every timing")
+    ap.add_argument("--mc", default=None, metavar="R[,R...]",
+                    help="rate the first model against Monte-Carlo playout players of R playouts per move, beside random")
     ap.add_argument("--matches", type=int, default=1, help="matches per timed window (a window should last a good part of a second)")
     ap.add_argument("--repeat", type=int, default=1, help="timed windows to play (the first one includes graph capture)")
     args = ap.parse_args()
@@ -150,6 +181,9 @@ def main():
     models = make_models(args)
     handler = Elo_handler(args.hex_size)
     mgrs = {}
+    if args.mc:
+        rate_on_ladder(args, handler, models[0])
+        return
     if args.compare:
         for step_loop in (False, True):
             report("warm-up", *play_match(args, handler, models, mgrs, step_loop))

@@ -83,6 +83,15 @@ class SetupCall(C.Structure):
                 + _fields(vp, "stones count result applied adj_out alive_out side_out sizes_out"))
 
 
+class PlayoutCall(C.Structure):
+    """``hexgnn_playout_call`` of include/hexgnn.h, field for field (tests/test_playout_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "b playouts max_nodes maker_to_move") + _fields(C.c_uint32, "seed")
+                + _fields(vp, "gptr rowptr col counter scores value tables wins status"))
+
+
+PLAYOUT_MAX_NODES = 640      # HEXGNN_PLAYOUT_MAX_NODES
+
+
 STONE_COLOURS = {"b": 0, "m": 1, "turn": 2}      # HEXGNN_STONE's colour field
 
 
@@ -194,6 +203,7 @@ _SIGS = {
     "hexgnn_frames_add": (ci, [vp, C.c_int64, vp]),
     "hexgnn_env_setup": (ci, [vp, C.POINTER(SetupCall), vp]),
     "hexgnn_board_values": (ci, [ci, ci, vp, vp, vp, C.c_float, vp, vp, vp]),
+    "hexgnn_playout_values": (ci, [C.POINTER(PlayoutCall), vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_forward_backward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

@@ -890,6 +890,53 @@ int hexgnn_env_setup(hexgnn_env* env, const hexgnn_setup_call* call, hexgnn_stre
 int hexgnn_board_values(int b, int hex_size, const int* gptr, const float* q, const int64_t* backmap, float fill,
                         float* board /*[b][hex_size^2]*/, int* best /*[b] or NULL*/, hexgnn_stream_t stream);
 
+/* ---- Monte-Carlo playout values (entry point added to ABI 8, nothing existing changes).
+ *      Flat Monte-Carlo with all-moves-as-first statistics on the batched observation's CSR alone (no env handle): a non-neural
+ *      opponent of tunable strength for match play, where the reference's strong anchor is an external program
+ *      (GN0/RainbowDQN/mohex_communicator.py).  A random playout of the Shannon node-switching game needs no move-by-move
+ *      simulation: the side to move ends up owning a uniformly random ceil(m / 2) of the m free rows, and the maker wins iff
+ *      terminal 0 reaches terminal 1 inside {0, 1} + the maker's rows of the current reduced graph.
+ *   Input per graph g: its rows [gptr[g], gptr[g + 1]) of a symmetric sorted CSR (rowptr / col with global row indices), rows 0
+ *     and 1 of the graph being the terminals; maker_to_move is one flag for the whole batch.
+ *   The rule, all arithmetic mod 2^32 -- the contract, bit for bit, whatever the kernel's mapping:
+ *     h(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     base = h(h(seed + 0x9e3779b9 * counter) + g), counter = the low 32 bits of *counter (NULL: 0); playout p has
+ *     key = h(base + p).  With n rows, m = n - 2 and left = ceil(m / 2), for i = 0 .. m - 1 in order: r = h(key + i); row i + 2
+ *     goes to the mover iff umulhi(r, m - i) < left, and left is then decremented (selection sampling: exactly ceil(m / 2)
+ *     rows).  Maker's rows = the mover's if maker_to_move, else the other free rows.  The maker wins iff row 1 is reachable
+ *     from row 0 through edges whose two ends lie in {0, 1} + maker's rows (n = 2: the adjacency of the terminals decides).
+ *   Outputs: wins[g] = playouts the mover wins; per row r >= 2 tables[r] = (own, won): the playouts in which the mover owns r,
+ *     and those of them the mover wins.  scores[r] = (float)(2 won - own) / (float) max(own, 1) for r >= 2 and
+ *     (float)(2 wins - playouts) / (float) playouts for the two terminal rows (their table entries are 0), one IEEE fp32
+ *     division each; value[g] is the terminal rows' score.  A graph with fewer than 2 rows gets nothing written; rows at or
+ *     behind gptr[b] are never read or written (capacity-sized observations).  A graph with more than max_nodes rows computes
+ *     nothing: NaN scores and value, -1 in its integer outputs, and bit 1 ORed into *status; bit 2: a column index that
+ *     leaves its graph was dropped.  status is never cleared here.
+ * One launch on `stream`, one workgroup per graph, nothing read back (capturable).  Checked on the host before the launch, in
+ * this order: a NULL descriptor or a struct_bytes of another size, playouts outside 1 .. HEXGNN_PLAYOUT_MAX_PLAYOUTS, max_nodes
+ * < 2 or b < 0: HEXGNN_EINVAL; max_nodes > HEXGNN_PLAYOUT_MAX_NODES: HEXGNN_EUNSUPPORTED; b == 0: HEXGNN_OK without a
+ * launch; gptr, rowptr, col, scores or status NULL: HEXGNN_EINVAL.  counter, value, tables and wins may be NULL. */
+#define HEXGNN_PLAYOUT_MAX_NODES 640
+#define HEXGNN_PLAYOUT_MAX_PLAYOUTS (1 << 24)
+typedef struct hexgnn_playout_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_playout_call), else HEXGNN_EINVAL */
+    int b;                   /* graphs */
+    int playouts;            /* R */
+    int max_nodes;           /* no graph of the batch has more rows; sizes the workgroup's LDS */
+    int maker_to_move;
+    uint32_t seed;
+    const int* gptr;         /* [b + 1] */
+    const int* rowptr;
+    const int* col;
+    const int64_t* counter;  /* [1] on the device, or NULL */
+    float* scores;           /* [N] */
+    float* value;            /* [b] */
+    int* tables;             /* [N][2] */
+    int* wins;               /* [b] */
+    int* status;             /* [1] */
+} hexgnn_playout_call;
+int hexgnn_playout_values(const hexgnn_playout_call* call, hexgnn_stream_t stream);
+
 /* ---- layout helpers (host tensors <-> padded layout) ---------------------------------------- */
 /* dst[n][HP] <- src[n][hidden] (row stride src_stride floats), pad columns zeroed; and back. */
 int hexgnn_pad_rows(int n, int hidden, const float* src, int src_stride, float* dst, hexgnn_stream_t stream);

@@ -4,6 +4,7 @@
     python examples/arena_eval.py --hex-size 7 --checkpoint a.pt b.pt --games 56     # two RainbowDQN checkpoints
     python examples/arena_eval.py --hex-size 11 --layers 15 --hidden 110 --compare 3 # arena vs the step loop, alternating
     python examples/arena_eval.py --hex-size 7 --checkpoint a.pt b.pt --mc 16,64,256  # rate model A on a ladder of playout players
+    python examples/arena_eval.py --hex-size 7 --layers 10 --hidden 35 --search 32    # the model with a 32-simulation search vs itself
 
 The match is ``gnn_hex_amd.arena.Elo_handler.play_some_games``: two legs over the shuffled unique opening moves, the first
 model always playing maker.  ``--step-loop`` plays the same match with the calls that existed before the arena did
@@ -13,6 +14,9 @@ counted), which is what a user had to write by hand; at temperature 0 both give 
 ``--mc R[,R...]`` rates the first model against a ladder of Monte-Carlo playout players (``gnn_hex_amd.playouts.MonteCarloPlayer``,
 R playouts per move) beside ``random``: the ladder is rated first, from ``random`` = 0 upwards by each rung's match against the
 rung below, then the model gets its performance rating against all of them.
+
+``--search SIMS`` plays the first model behind a PUCT tree search (``gnn_hex_amd.search.SearchPlayer`` over ``QEvaluator``, SIMS
+simulations per move, a fresh tree per ply) against the same model's greedy play, as maker and as breaker.
 """
 import argparse
 import os
@@ -154,6 +158,19 @@ def rate_on_ladder(args, handler, model):
         print("%-10s %8.1f" % (name, rating))
 
 
+def search_match(args, handler, model):
+    """``--search``: the model searching ``SIMS`` simulations per move (``QEvaluator`` -> ``SearchPlayer``) against the same
+    model playing its greedy move, both ways round."""
+    from gnn_hex_amd.search import QEvaluator, SearchPlayer
+    handler.add_player("search%d" % args.search, model=SearchPlayer(QEvaluator(model), args.search), uses_empty_model=False)
+    handler.add_player("greedy", model=model, uses_empty_model=False)
+    for maker, breaker in (("search%d" % args.search, "greedy"), ("greedy", "search%d" % args.search)):
+        t0 = time.perf_counter()
+        wins = handler.play_some_games(maker, breaker, args.games, args.temperature, progress=True)
+        torch.cuda.synchronize()
+        print("%s (maker) vs %s: %s in %.2f s" % (maker, breaker, wins, time.perf_counter() - t0), flush=True)
+
+
 def report(tag, wins, games, plies, dt):
     print("%-9s %s  %d games in %.3f s: %.1f games/s, %.1f plies/s" % (tag, wins, games, dt, games / dt, plies / dt), flush=True)
 
@@ -173,6 +190,8 @@ def main():
                     help="after a warm-up match of each, alternate arena and step loop N times and print every timing")
     ap.add_argument("--mc", default=None, metavar="R[,R...]",
                     help="rate the first model against Monte-Carlo playout players of R playouts per move, beside random")
+    ap.add_argument("--search", type=int, default=0, metavar="SIMS",
+                    help="play the first model with a PUCT search of SIMS simulations per move against its own greedy play")
     ap.add_argument("--matches", type=int, default=1, help="matches per timed window (a window should last a good part of a second)")
     ap.add_argument("--repeat", type=int, default=1, help="timed windows to play (the first one includes graph capture)")
     args = ap.parse_args()
@@ -183,6 +202,9 @@ def main():
     mgrs = {}
     if args.mc:
         rate_on_ladder(args, handler, models[0])
+        return
+    if args.search:
+        search_match(args, handler, models[0])
         return
     if args.compare:
         for step_loop in (False, True):

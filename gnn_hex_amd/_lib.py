@@ -92,6 +92,18 @@ class PlayoutCall(C.Structure):
 PLAYOUT_MAX_NODES = 640      # HEXGNN_PLAYOUT_MAX_NODES
 
 
+class SearchCall(C.Structure):
+    """``hexgnn_search_call`` of include/hexgnn.h, field for field (tests/test_search_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "num_games hex_size max_sims skip")
+                + _fields(C.c_float, "c_puct temperature fill") + _fields(vp, "workspace") + _fields(sz, "workspace_bytes")
+                + _fields(vp, "status active path leaf result logits offsets value gptr scores counts q best"))
+
+
+SEARCH_MAX_SIMS = 65535                                       # HEXGNN_SEARCH_MAX_SIMS
+SEARCH_REC = 5                                                # HEXGNN_SEARCH_REC: kind, side, path length, terminal value, moves
+SEARCH_LEAF, SEARCH_TERMINAL, SEARCH_SKIPPED = 0, 1, 2        # HEXGNN_SEARCH_*
+
+
 STONE_COLOURS = {"b": 0, "m": 1, "turn": 2}      # HEXGNN_STONE's colour field
 
 
@@ -204,6 +216,11 @@ _SIGS = {
     "hexgnn_env_setup": (ci, [vp, C.POINTER(SetupCall), vp]),
     "hexgnn_board_values": (ci, [ci, ci, vp, vp, vp, C.c_float, vp, vp, vp]),
     "hexgnn_playout_values": (ci, [C.POINTER(PlayoutCall), vp]),
+    "hexgnn_search_workspace_bytes": (sz, [ci, ci, ci]),
+    "hexgnn_search_reset": (ci, [C.POINTER(SearchCall), vp]),
+    "hexgnn_search_descend": (ci, [vp, vp, C.POINTER(SearchCall), vp]),
+    "hexgnn_search_backup": (ci, [C.POINTER(SearchCall), vp]),
+    "hexgnn_search_root": (ci, [C.POINTER(SearchCall), vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_forward_backward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

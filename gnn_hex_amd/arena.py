@@ -10,6 +10,13 @@ signatures, the same two-leg match over the shuffled unique opening moves, the s
 Finished games rest in place (their env restarts and its side flag keeps flipping with everyone else's, so the batched
 observation stays uniform); they still pass through the forward until the last game of the batch ends.  There is no CPU
 fallback: CNN / Gao / MoHex players, SGF export and ``CachedGraphNorm`` models are refused.
+
+A player with a ``search_scores(env_handle, obs, active)`` method (``gnn_hex_amd.search.SearchPlayer``) takes the place of the
+forward: it gets the root env handle, the root observation and the int32 mask of undecided games (computed on the device from
+the game records) and returns one score per observation row -- the root visit counts of a PUCT tree search -- from which
+``hexgnn_arena_ply`` picks as from a model's output: the most visited move by first maximum, or at ``temperature`` T > 0 a
+draw from softmax(count / T) (not count ** (1 / T)).  A search reads leaf sizes back inside a ply, so it needs
+``DeviceArena(graph=False)``; with ``graph=True``, ``play`` raises ``ValueError``.  Every ply searches a fresh tree.
 """
 from __future__ import annotations
 
@@ -47,6 +54,10 @@ class ArenaResult:
 
 def _is_random(player) -> bool:
     return isinstance(player, str) and player == "random"
+
+
+def _is_search(player) -> bool:
+    return hasattr(player, "search_scores")
 
 
 class DeviceArena:
@@ -88,7 +99,7 @@ class DeviceArena:
     # -- pieces ----------------------------------------------------------------------------------------
     @staticmethod
     def _check_player(player):
-        if _is_random(player):
+        if _is_random(player) or _is_search(player):
             return False
         if not callable(player):
             raise TypeError("a player is a model from get_pre_defined or the string \"random\", not %r" % (player,))
@@ -114,7 +125,10 @@ class DeviceArena:
             obs.observe_env(h)
             (player, live_norm), mode = players[0 if maker else 1], modes[0 if maker else 1]
             q = None
-            if mode != PICK_UNIFORM:            # the built-in random player needs no forward
+            if _is_search(player):              # a tree search from the root env: the root visit counts are its scores
+                active = ((self.game[:, 0] < 0) & (self.game[:, 3] == 0)).to(torch.int32)
+                q = player.search_scores(h, obs, active)
+            elif mode != PICK_UNIFORM:          # the built-in random player needs no forward
                 q = acting_forward(player, obs, maker, self.mgr._nv, live_norm).reshape(-1)
                 if q.dtype != torch.float32 or not q.is_contiguous():
                     q = q.float().contiguous()
@@ -141,6 +155,8 @@ class DeviceArena:
         if not temperature >= 0.0 or temperature == float("inf"):
             raise ValueError("temperature must be finite and >= 0")
         k = self.num_games
+        if self.use_graph and (_is_search(maker_player) or _is_search(breaker_player)):
+            raise ValueError("a search player reads sizes back inside a ply and cannot be captured: DeviceArena(graph=False)")
         players = tuple((p, self._check_player(p)) for p in (maker_player, breaker_player))
         modes = tuple(PICK_UNIFORM if _is_random(p) else (PICK_SOFTMAX if temperature > 0 else PICK_GREEDY)
                       for p in (maker_player, breaker_player))
@@ -264,10 +280,10 @@ class Elo_handler:
             raise ValueError("player %r has no model (roundrobin loads checkpoints of uses_empty_model players)" % name)
         return p["model"]
 
-    def _arena(self, games) -> DeviceArena:
-        key = (self.size, games)
+    def _arena(self, games, graph: bool = True) -> DeviceArena:
+        key = (self.size, games) if graph else (self.size, games, False)
         if key not in self._arenas:
-            self._arenas[key] = DeviceArena(self.size, games, device=self.device)
+            self._arenas[key] = DeviceArena(self.size, games, device=self.device, graph=graph)
         return self._arenas[key]
 
     def _match_plan(self, num_games, random_first_move):
@@ -299,7 +315,7 @@ class Elo_handler:
         wins = {maker: 0, breaker: 0}
         lengths = []
         if per_leg > 0:
-            arena = self._arena(per_leg)
+            arena = self._arena(per_leg, graph=not (_is_search(pm) or _is_search(pb)))     # a search player is not capturable
             for leg, first in enumerate(("m", "b")):
                 res = arena.play(pm, pb, first=first, openings=openings[leg], temperature=temperature)
                 wins[maker] += res.maker_wins

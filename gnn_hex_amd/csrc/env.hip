@@ -14,7 +14,7 @@
 // clique" / "find the twin" are per-lane tests combined with wave ballots.  Integer/bit work: no MFMA, bound by LDS
 // latency; results are bit-exact against oracle/env_ref.c (same canonical ascending order).
 //
-// The per-env kernels (env_step_kernel, arena_ply_kernel, rollout_ply_kernel, env_setup_kernel) are built from one copy of each
+// The per-env kernels (env_step_kernel, arena_ply_kernel, rollout_ply_kernel, env_setup_kernel, search_descend_kernel) are built from one copy of each
 // piece: load_game / store_game (write_game: the env and, for the rollout and the set-up, a snapshot), play_vertex, play_move
 // (legality, the move, the restart of a decided game, the counts), restart_game, put_result; the rollout's pick is
 // eps_greedy_rank of hexgnn_reduce.h, the one select_actions_kernel makes.  A kernel holds what is its own: the arena's resting
@@ -25,6 +25,7 @@
 #include <type_traits>
 #include <vector>
 #include "hexgnn_reduce.h"
+#include "search_tree.h"
 
 namespace hexgnn {
 
@@ -728,6 +729,110 @@ __global__ __launch_bounds__(64) void env_setup_kernel(EnvDev d, SetupArgs a) {
     }
 }
 
+// One simulation's descent of the PUCT search (include/hexgnn.h: hexgnn_search_descend; the tree: search_tree.h).  The root game
+// is loaded into LDS and walked down its tree, every step through play_vertex with dead/captured removal; the position reached
+// is stored into the LEAF env.  play_vertex writes the response tables straight to global memory, so they are the leaf env's rows
+// (filled from the root's first) and never the root's: the root env is only read.  The tree is only read too -- the expansion and
+// every count belong to search_backup_kernel -- a few hundred bytes per level from global memory; LDS holds the game alone.
+// The pick is graph_first_max on the scores the lanes have just written to the game's scratch row (lane l writes and reads
+// entries l, l + 64, ..: its own).  node, the pick and the winner are uniform over the wave, so every barrier is taken by all lanes.
+struct DescendArgs {
+    SearchTree t;
+    EnvDev leaf;
+    const int* active;           // [G] or null
+    float c_puct;
+    int max_sims;
+    int* path;                   // [G][C]
+    int* rec;                    // [G][HEXGNN_SEARCH_REC]
+    int* result;                 // [G][5]
+    int* status;
+};
+
+template <int WT>
+__global__ __launch_bounds__(64) void search_descend_kernel(EnvDev root, DescendArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int env = blockIdx.x, lane = threadIdx.x;
+    const SearchTree& t = a.t;
+    GameT<WT> g;
+    load_game(g, root, env, lds);
+    short* rm = a.leaf.resp_maker + (size_t)env * root.nv;
+    short* rb = a.leaf.resp_breaker + (size_t)env * root.nv;
+    const short* root_rm = root.resp_maker + (size_t)env * root.nv;
+    const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
+    for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
+    const int root_mt = root.maker_turn[env], root_moves = root.total_moves[env];
+    int mt = root_mt, moves = root_moves, kind = kSearchLeaf, len = 0, tval = 0, node = 0;
+    int* path = a.path + (size_t)env * t.C;
+    if (a.active && !a.active[env]) {
+        kind = kSearchSkipped;                                // a resting game: no tree change, leaf = root
+    } else if (t.cnt[2 * env + 1] >= a.max_sims) {
+        kind = kSearchSkipped;
+        if (lane == 0) atomicOr(a.status, 1);
+    } else {
+        float* sc = t.score + (size_t)env * t.A;
+        while (true) {
+            const int ns = t.ns[t.node(env, node)];
+            if (ns == 0) break;                               // not expanded: the leaf
+            const int ne = t.ne[t.node(env, node)];
+            if (ne < 1 || ne > t.A || len >= t.C) { kind = kSearchSkipped; break; }     // no tree this search has built
+            const size_t e0 = t.edge(env, node);
+            const float sq = __fsqrt_rn((float)ns);
+            for (int e = lane; e < ne; e += 64) {             // every operation rounded on its own: no contraction
+                const int n = t.N[e0 + e];
+                const float q = n > 0 ? __fdiv_rn(t.W[e0 + e], (float)n) : 0.f;
+                const float u = __fdiv_rn(__fmul_rn(__fmul_rn(a.c_puct, t.P[e0 + e]), sq), (float)(1 + n));
+                sc[e] = __fadd_rn(q, u);
+            }
+            float best;
+            int arg;
+            graph_first_max(sc, -2, ne, lane, best, arg);     // rows [r0 + 2, r1) = entries [0, ne)
+            if (arg == 0x7fffffff) { kind = kSearchSkipped; break; }
+            const int v = t.vertex[e0 + arg];
+            if (v < 2 || v >= root.nv || !g.alive[v]) { kind = kSearchSkipped; break; }
+            if (lane == 0) path[len] = node * t.A + arg;
+            ++len;
+            ++moves;
+            const int winner = play_vertex(g, v, mt, true, rm, rb);
+            if (winner >= 0) {                                // decided: the side to move there has won or lost
+                kind = kSearchTerminal;
+                tval = winner == (mt ? 0 : 1) ? 1 : -1;
+                break;
+            }
+            const int child = t.child[e0 + arg];
+            if (child < 0) break;                             // no child yet: the leaf
+            if (child >= t.C) { kind = kSearchSkipped; break; }
+            node = child;
+        }
+    }
+    const int leaf_side = mt;
+    int n_moves = 0;
+    if (kind != kSearchLeaf) {                                // the leaf env gets a copy of the root position
+        __syncthreads();
+        load_game(g, root, env, lds);
+        for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
+        mt = root_mt;
+        moves = root_moves;
+        if (kind == kSearchSkipped) len = 0;
+    } else {                                                  // the leaf's legal moves, ascending, for its expansion
+        uint16_t* mv = t.moves + (size_t)env * t.A;
+        for (int k = 0; k < g.K; ++k) {
+            const int x = lane + 64 * k;
+            const bool al = x >= 2 && x < root.nv && g.alive[x];
+            const uint64_t bal = __ballot(al);
+            if (al) mv[n_moves + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)x;
+            n_moves += __popcll(bal);
+        }
+    }
+    Move m = {-1, moves, 0, mt, moves, 0, 0};
+    count_game(g, &m.n_alive, &m.n_dir_edges);
+    store_game(g, a.leaf, env);
+    if (lane == 0) {
+        put_result(a.leaf, env, a.result, m);
+        int* rec = a.rec + HEXGNN_SEARCH_REC * env;
+        rec[0] = kind; rec[1] = kind == kSearchSkipped ? root_mt : leaf_side; rec[2] = len; rec[3] = tval; rec[4] = n_moves;
+    }
+}
+
 // Observation of every env into batched buffers (convert_graph.py:77-122, old_style=True; Batch.from_data_list):
 //   x [N][3] = (degree, is_terminal, maker_to_move);  backmap [N] rank -> vertex id (int64)
 //   edge_local [2][E]: per graph, first the E_g/2 edges (s > t, sorted by (s,t)) then the flipped copies, LOCAL ranks
@@ -1080,6 +1185,25 @@ int hexgnn_env_setup(hexgnn_env* h, const hexgnn_setup_call* c, hexgnn_stream_t 
     a.stones = c->stones; a.count = c->count; a.result = c->result; a.applied = c->applied;
     a.adj_out = c->adj_out; a.alive_out = c->alive_out; a.side_out = c->side_out; a.sizes_out = c->sizes_out;
     dispatch_words(e->d.W, [&](auto wt) { launch_envs<&env_setup_kernel<decltype(wt)::value>>(e->d, st, a); });
+    return check_launch();
+}
+
+int hexgnn_search_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_call* c, hexgnn_stream_t stream_) {
+    bool done;
+    const int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    if (!root_ || !leaf_ || root_ == leaf_) return HEXGNN_EINVAL;
+    const EnvDev& root = reinterpret_cast<const Env*>(root_)->d;
+    const EnvDev& leaf = reinterpret_cast<const Env*>(leaf_)->d;
+    if (root.size != c->hex_size || leaf.size != c->hex_size || root.num_envs != c->num_games || leaf.num_envs != c->num_games)
+        return HEXGNN_EINVAL;
+    if (!(c->c_puct >= 0.f && c->c_puct < INFINITY)) return HEXGNN_EINVAL;
+    if (!c->path || !c->leaf || !c->result) return HEXGNN_EINVAL;
+    DescendArgs a;
+    a.t = search_tree(c->num_games, root.nv, c->max_sims, c->workspace);
+    a.leaf = leaf; a.active = c->active; a.c_puct = c->c_puct; a.max_sims = c->max_sims;
+    a.path = c->path; a.rec = c->leaf; a.result = c->result; a.status = c->status;
+    dispatch_words(root.W, [&](auto wt) { launch_envs<&search_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a); });
     return check_launch();
 }
 

@@ -1,0 +1,210 @@
+// The tree-only kernels of the batched PUCT search (include/hexgnn.h: hexgnn_search_*; the layout: search_tree.h): reset, the
+// expansion + backup of one simulation, and the root read-out.  The descent, which needs the game, is search_descend_kernel of
+// env.hip.  One 64-lane workgroup per game, edge loops strided over the lanes, the tree in global memory; latency kernels like
+// hexgnn_arena_ply, nothing here is bound by anything but the launch.  A game's kernels touch that game's slices only, and every
+// index read from memory (path entries, edge counts, offsets) is checked against the layout before it is used.
+// This file needs hipcc's correctly rounded fp32 division (its default; no fast-math flag here).
+#include "hexgnn_reduce.h"
+#include "search_tree.h"
+
+namespace hexgnn {
+
+__global__ __launch_bounds__(64) void search_reset_kernel(SearchTree t) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    for (int n = lane; n < t.C; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
+    if (lane == 0) { t.cnt[2 * g] = 1; t.cnt[2 * g + 1] = 0; }
+}
+
+struct BackupArgs {
+    SearchTree t;
+    const int* path;             // [G][C]
+    const int* rec;              // [G][HEXGNN_SEARCH_REC]
+    const float* logits;
+    const int* offsets;          // [G + 1]
+    const float* value;          // [G]
+    int skip;
+    float temperature;
+    int* status;
+};
+
+__global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const SearchTree& t = a.t;
+    const int* rec = a.rec + HEXGNN_SEARCH_REC * g;
+    const int kind = rec[0], len = rec[2];
+    if (kind != kSearchLeaf && kind != kSearchTerminal) return;
+    if (len < 0 || len > t.C) return;
+    const int* path = a.path + (size_t)g * t.C;
+    bool inside = true;                                       // every step of the path is an edge slot of this game
+    for (int d = lane; d < len; d += 64) inside &= path[d] >= 0 && path[d] < t.C * t.A;
+    if (!__all(inside)) return;
+    float v;
+    if (kind == kSearchTerminal) {
+        v = (float)rec[3];
+    } else {
+        const int ne = rec[4];
+        const int base = a.offsets[g] + a.skip;
+        if (ne < 1 || ne > t.A || a.offsets[g + 1] - base < ne) {     // fewer logits than legal moves: nothing is read
+            if (lane == 0) atomicOr(a.status, 4);
+            return;
+        }
+        // the maximum logit: the softmax's shift and, without a value array, the leaf's value max_a Q(s, a) clamped to [-1, 1]
+        float m;
+        int arg;
+        graph_first_max(a.logits, base - 2, base + ne, lane, m, arg);
+        v = a.value ? a.value[g] : fminf(fmaxf(m, -1.f), 1.f);
+        bool finite = v - v == 0.f;
+        for (int e = lane; e < ne; e += 64) { const float l = a.logits[base + e]; finite &= l - l == 0.f; }
+        if (!__all(finite)) {                                 // drops this game's simulation
+            if (lane == 0) atomicOr(a.status, 2);
+            return;
+        }
+        const int used = t.cnt[2 * g];
+        const int node = len == 0 ? 0 : used;
+        if (node >= t.C || used < 1) {
+            if (lane == 0) atomicOr(a.status, 1);
+            return;
+        }
+        // a record that was backed up before: the root is expanded already / the edge has its child
+        if (len == 0 ? t.ns[t.node(g, 0)] != 0 : t.child[t.edge(g, 0) + path[len - 1]] >= 0) return;
+        // P = softmax(logit / T): the sum in the order of graph_pick's SOFTMAX
+        float S = 0.f;
+        for (int c0 = 0; c0 < ne; c0 += 64) {
+            const int e = c0 + lane;
+            float s = e < ne ? expf((a.logits[base + e] - m) / a.temperature) : 0.f;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float up = __shfl_up(s, off);
+                if (lane >= off) s += up;
+            }
+            s += S;
+            S = __shfl(s, 63);
+        }
+        const size_t e0 = t.edge(g, node);
+        const uint16_t* mv = t.moves + (size_t)g * t.A;
+        for (int e = lane; e < ne; e += 64) {
+            t.P[e0 + e] = __fdiv_rn(expf((a.logits[base + e] - m) / a.temperature), S);
+            t.W[e0 + e] = 0.f;
+            t.N[e0 + e] = 0;
+            t.child[e0 + e] = -1;
+            t.vertex[e0 + e] = mv[e];
+        }
+        if (lane == 0) {
+            t.ns[t.node(g, node)] = 1;
+            t.ne[t.node(g, node)] = ne;
+            if (len > 0) {
+                t.child[t.edge(g, 0) + path[len - 1]] = node;
+                t.cnt[2 * g] = used + 1;
+            }
+        }
+    }
+    // step d of the path receives the leaf's value with len - d sign changes (a negation is exact: any order gives these bits);
+    // a path visits every node once, so no two lanes meet on a word
+    for (int d = lane; d < len; d += 64) {
+        const int pe = path[d];
+        const float vd = ((len - d) & 1) ? -v : v;
+        const size_t e = t.edge(g, 0) + pe;
+        t.N[e] += 1;
+        t.W[e] += vd;
+        t.ns[t.node(g, pe / t.A)] += 1;
+    }
+    if (lane == 0) t.cnt[2 * g + 1] += 1;
+}
+
+struct RootArgs {
+    SearchTree t;
+    int cells;                   // hex_size^2
+    float fill;
+    const int* gptr;             // [G + 1]
+    float* scores;
+    float* counts;               // [G][cells] or null
+    float* q;                    // [G][cells] or null
+    int* best;                   // [G] or null
+};
+
+__global__ __launch_bounds__(64) void search_root_kernel(RootArgs a) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const SearchTree& t = a.t;
+    const int r0 = a.gptr[g], r1 = a.gptr[g + 1];
+    const int rows = r1 - r0 - 2;
+    const int ns = t.ns[t.node(g, 0)];
+    int ne = ns > 0 ? t.ne[t.node(g, 0)] : 0;
+    if (ne > t.A) ne = 0;
+    const size_t e0 = t.edge(g, 0);
+    if (a.counts) for (int c = lane; c < a.cells; c += 64) a.counts[(size_t)g * a.cells + c] = a.fill;
+    if (a.q) for (int c = lane; c < a.cells; c += 64) a.q[(size_t)g * a.cells + c] = a.fill;
+    __syncthreads();                                          // the fills are done before an edge's cell is written
+    float w = 0.f;
+    for (int e = lane; e < ne; e += 64) {
+        const int n = t.N[e0 + e];
+        w += t.W[e0 + e];
+        const int cell = (int)t.vertex[e0 + e] - 2;
+        if (cell >= 0 && cell < a.cells) {
+            if (a.counts) a.counts[(size_t)g * a.cells + cell] = (float)n;
+            if (a.q) a.q[(size_t)g * a.cells + cell] = n > 0 ? __fdiv_rn(t.W[e0 + e], (float)n) : 0.f;
+        }
+    }
+    w = wave_sum(w);
+    const float mean = ns > 1 ? __fdiv_rn(w, (float)(ns - 1)) : 0.f;
+    // the rows of the root observation: lane l writes rows l, l + 64, .., the ones graph_first_max then reads on it
+    for (int i = lane; i < rows; i += 64) a.scores[r0 + 2 + i] = i < ne ? (float)t.N[e0 + i] : 0.f;
+    if (lane < 2 && r0 + lane < r1) a.scores[r0 + lane] = mean;
+    if (a.best) {
+        float bestv;
+        int arg = 0x7fffffff;
+        const int top = rows < ne ? rows : ne;
+        if (top > 0) graph_first_max(a.scores, r0, r0 + 2 + top, lane, bestv, arg);
+        if (lane == 0) a.best[g] = arg == 0x7fffffff ? -1 : (int)t.vertex[e0 + (arg - r0 - 2)];
+    }
+}
+
+}  // namespace hexgnn
+
+using namespace hexgnn;
+
+extern "C" {
+
+size_t hexgnn_search_workspace_bytes(int num_games, int hex_size, int max_sims) {
+    if (num_games < 0 || hex_size < 2 || hex_size > 25 || max_sims < 1 || max_sims > HEXGNN_SEARCH_MAX_SIMS) return 0;
+    return search_tree(num_games, hex_size * hex_size + 2, max_sims, nullptr).bytes;
+}
+
+int hexgnn_search_reset(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
+    bool done;
+    const int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    const SearchTree t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    search_reset_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(t);
+    return check_launch();
+}
+
+int hexgnn_search_backup(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
+    bool done;
+    const int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    if (!(c->temperature > 0.f && c->temperature < INFINITY)) return HEXGNN_EINVAL;
+    if (c->skip != 0 && c->skip != 2) return HEXGNN_EINVAL;
+    if (!c->path || !c->leaf) return HEXGNN_EINVAL;
+    if (!c->logits || !c->offsets) return HEXGNN_EINVAL;
+    BackupArgs a;
+    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    a.path = c->path; a.rec = c->leaf; a.logits = c->logits; a.offsets = c->offsets; a.value = c->value;
+    a.skip = c->skip; a.temperature = c->temperature; a.status = c->status;
+    search_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
+    return check_launch();
+}
+
+int hexgnn_search_root(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
+    bool done;
+    const int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    if (!c->gptr || !c->scores) return HEXGNN_EINVAL;
+    RootArgs a;
+    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    a.cells = c->hex_size * c->hex_size; a.fill = c->fill;
+    a.gptr = c->gptr; a.scores = c->scores; a.counts = c->counts; a.q = c->q; a.best = c->best;
+    search_root_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
+    return check_launch();
+}
+
+}  // extern "C"

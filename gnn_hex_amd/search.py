@@ -1,0 +1,282 @@
+"""Batched PUCT tree search on the device: ``run_many_mcts`` of GN0/alpha_zero/MCTS.py as a closed device loop.
+
+G trees for G games, one leaf per game per simulation, the leaves of all games through ONE evaluator call.  Per simulation:
+``hexgnn_search_descend`` (select down the tree with the env kernels' move routine, store the leaf position into the search's own
+leaf env) -> the leaf observation (``hexgnn_env_offsets`` / ``hexgnn_env_observe``, unchanged) -> the evaluator ->
+``hexgnn_search_backup`` (expand the leaf with softmax(logit / T) priors, back its value up).  ``hexgnn_search_root`` reads the
+root visit counts out in the layout of the root observation, so ``hexgnn_arena_ply`` picks from them like from any model's output.
+The rule is restated in include/hexgnn.h and on the host in tests/search_oracle.py.  A tree, not the reference's hash-keyed DAG:
+transpositions are not merged; no tree reuse between plies, no Dirichlet noise, one leaf per game per round, no swap rule.
+
+``TreeSearch``             the trees, the leaf env and the simulation loop.
+``PolicyValueEvaluator``   leaves through a ``SAGE_torch_script`` policy / value network (the HexAra network).
+``QEvaluator``             leaves through a ``get_pre_defined`` Q-network or a ``MonteCarloPlayer``: scores as logits, the maximum
+                           score as value; one forward per side, so two per simulation.
+``UniformEvaluator``       uniform priors, value 0: plain UCT on terminal results alone, no network.
+``SearchPlayer``           a player for ``DeviceArena.play`` / ``Elo_handler.add_player(model=...)``.
+
+There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .multi_env_manager import Env_manager
+from .observation import ObsTarget, live_norm_of
+
+
+def tree_layout(num_games: int, hex_size: int, max_sims: int):
+    """The workspace of include/hexgnn.h as ``({name: (byte offset, dtype, shape)}, tree bytes, total bytes)``: the sections in
+    the header's order, each aligned to 256 bytes; ``score`` and ``moves`` are scratch behind the tree."""
+    G, Cn, A = int(num_games), int(max_sims) + 1, int(hex_size) ** 2
+    out, off, tree = {}, 0, 0
+    for name, dt, shape in (("ns", np.int32, (G, Cn)), ("ne", np.int32, (G, Cn)), ("cnt", np.int32, (G, 2)),
+                            ("P", np.float32, (G, Cn, A)), ("W", np.float32, (G, Cn, A)), ("N", np.int32, (G, Cn, A)),
+                            ("child", np.int32, (G, Cn, A)), ("vertex", np.uint16, (G, Cn, A)),
+                            ("score", np.float32, (G, A)), ("moves", np.uint16, (G, A))):
+        if name == "score":
+            tree = off
+        out[name] = (off, dt, shape)
+        off += -(-int(np.prod(shape)) * np.dtype(dt).itemsize // 256) * 256
+    return out, tree, off
+
+
+class TreeSearch:
+    """``num_games`` search trees of at most ``max_sims`` simulations each over Hex ``hex_size`` positions.  Owns the leaf env,
+    the tree workspace, the path / leaf record / status tensors and a capacity-sized leaf observation.  ``c_puct`` and
+    ``temperature`` (of the prior's softmax) are the rule's two constants."""
+
+    def __init__(self, hex_size: int, num_games: int, max_sims: int, c_puct: float = 1.5, temperature: float = 1.0, device=None):
+        if num_games < 1 or not 1 <= int(max_sims) <= _lib.SEARCH_MAX_SIMS:
+            raise ValueError("num_games >= 1 and 1 <= max_sims <= %d" % _lib.SEARCH_MAX_SIMS)
+        if not (c_puct >= 0 and math.isfinite(c_puct)) or not (temperature > 0 and math.isfinite(temperature)):
+            raise ValueError("c_puct is finite and >= 0, temperature finite and > 0")
+        self.hex_size, self.num_games, self.max_sims = int(hex_size), int(num_games), int(max_sims)
+        self.c_puct, self.temperature = float(c_puct), float(temperature)
+        self._leaf_mgr = mgr = Env_manager(num_games, hex_size, device=device)     # the leaf env the search owns
+        mgr.record_snapshots = False
+        dev = self.device = mgr.device
+        self.leaf_handle, self.nv = mgr._h, mgr._nv
+        L = _lib.lib()
+        self.workspace_bytes = int(L.hexgnn_search_workspace_bytes(num_games, hex_size, max_sims))
+        if self.workspace_bytes == 0:
+            raise _lib.HexGnnError("hexgnn_search_workspace_bytes refuses Hex-%d" % hex_size)
+        self.workspace = torch.zeros(self.workspace_bytes, dtype=torch.uint8, device=dev)
+        G = num_games
+        self.path = torch.zeros((G, max_sims + 1), dtype=torch.int32, device=dev)
+        self.leaf = torch.zeros((G, _lib.SEARCH_REC), dtype=torch.int32, device=dev)
+        self.result = torch.zeros((G, 5), dtype=torch.int32, device=dev)
+        self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        dev = self.device = self._status.device               # with its index, as every tensor handed in carries it
+        # The maker's rewiring can leave a position with MORE edges than the start position (Hex-7: 125 against 122 after one
+        # move), and a search puts every game one maker move deep at once: the leaf observation holds twice the start
+        # position's edges per game, and leaf_offsets() guards the total.
+        self.e_max = 2 * int(mgr._base_sizes[0, 1])
+        self.obs = ObsTarget.capacity(G, self.nv, self.e_max, dev, zeroed=True, tail_clear=True)
+        self.reset()
+
+    # -- the four kernel calls --------------------------------------------------------------------------
+    def _call(self, **kw):
+        return _lib.SearchCall(struct_bytes=C.sizeof(_lib.SearchCall), num_games=self.num_games, hex_size=self.hex_size,
+                               max_sims=self.max_sims, c_puct=self.c_puct, temperature=self.temperature,
+                               workspace=self.workspace.data_ptr(), workspace_bytes=self.workspace_bytes,
+                               status=self._status.data_ptr(), path=self.path.data_ptr(), leaf=self.leaf.data_ptr(),
+                               result=self.result.data_ptr(), **kw)
+
+    def reset(self) -> None:
+        """Every tree becomes one unexpanded root."""
+        _lib.check(_lib.lib().hexgnn_search_reset(C.byref(self._call()), ops._stream()), "hexgnn_search_reset")
+
+    def descend(self, root_handle, active=None) -> None:
+        """One descent per game from the positions of ``root_handle`` (read only); ``active``: int32 [G] on the device, 0 = the
+        game rests.  Fills ``path``, ``leaf``, ``result`` and the leaf env."""
+        if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != self.num_games
+                                   or active.device != self.device):
+            raise ValueError("active: a contiguous int32 [%d] tensor on %s" % (self.num_games, self.device))
+        call = self._call(active=active.data_ptr() if active is not None else None)
+        _lib.check(_lib.lib().hexgnn_search_descend(root_handle, self.leaf_handle, C.byref(call), ops._stream()),
+                   "hexgnn_search_descend")
+
+    def backup(self, logits, offsets, skip: int, value=None) -> None:
+        """Expand and back up: ``logits`` float32 placed by the int32 ``offsets [G + 1]`` and ``skip`` (0 / 2), ``value``
+        float32 [G] or None (the maximum logit clamped to [-1, 1])."""
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or offsets.dtype != torch.int32 \
+                or not offsets.is_contiguous() or offsets.numel() != self.num_games + 1:
+            raise ValueError("logits: contiguous float32; offsets: contiguous int32 [%d]" % (self.num_games + 1))
+        if value is not None and (value.dtype != torch.float32 or not value.is_contiguous() or value.numel() != self.num_games):
+            raise ValueError("value: a contiguous float32 [%d] tensor" % self.num_games)
+        call = self._call(skip=int(skip), logits=logits.data_ptr(), offsets=offsets.data_ptr(),
+                          value=value.data_ptr() if value is not None else None)
+        _lib.check(_lib.lib().hexgnn_search_backup(C.byref(call), ops._stream()), "hexgnn_search_backup")
+
+    def root(self, obs, boards: bool = False, fill: float = 0.0):
+        """The read-out in the layout of the root observation ``obs`` (an ``ObsTarget`` or ``ObsList`` of the root env):
+        ``scores`` float32 [N], the visit count of every legal move on rows 2.. of its graph and the root's mean value on the
+        two terminal rows.  ``boards=True``: ``(scores, counts [G, hex_size ** 2], q [G, hex_size ** 2], best int32 [G])`` with
+        ``fill`` on cells without an edge and ``best`` the most visited vertex (first maximum; -1: root not expanded)."""
+        from .positions import _gptr32
+        dev, G, cells = self.device, self.num_games, self.hex_size ** 2
+        gptr = _gptr32(obs)
+        scores = torch.zeros(int(obs.x.shape[0]), dtype=torch.float32, device=dev)
+        counts = q = best = None
+        if boards:
+            counts = torch.empty((G, cells), dtype=torch.float32, device=dev)
+            q = torch.empty((G, cells), dtype=torch.float32, device=dev)
+            best = torch.empty(G, dtype=torch.int32, device=dev)
+        call = self._call(fill=float(fill), gptr=gptr.data_ptr(), scores=scores.data_ptr(),
+                          counts=counts.data_ptr() if boards else None, q=q.data_ptr() if boards else None,
+                          best=best.data_ptr() if boards else None)
+        _lib.check(_lib.lib().hexgnn_search_root(C.byref(call), ops._stream()), "hexgnn_search_root")
+        return (scores, counts, q, best) if boards else scores
+
+    # -- the loop -------------------------------------------------------------------------------------------
+    def leaf_offsets(self) -> None:
+        """The leaf observation's offsets from the sizes the last descent reported, on the device.  Should the leaves hold more
+        edges than the observation has columns, the edge offsets become zeros -- every graph then lands inside the storage,
+        the simulation evaluates garbage -- and bit 8 of the status word makes ``status()`` raise: nothing is written out of
+        bounds and nothing is read back."""
+        obs, k = self.obs, self.num_games
+        _lib.check(_lib.lib().hexgnn_env_offsets(k, self.result.data_ptr(), obs.node_off.data_ptr(), obs.edge_off.data_ptr(),
+                                                 ops._stream()), "hexgnn_env_offsets")
+        over = obs.edge_off[k] > obs.E
+        self._status.bitwise_or_(over.to(torch.int32) * 8)
+        obs.edge_off.mul_((~over).to(torch.int32))
+
+    def simulate(self, root_handle, evaluator, sims: int, active=None, trace=None) -> None:
+        """``sims`` simulations per game: descend -> ``evaluator.evaluate(self)`` -> backup.  ``trace``: a list that receives per
+        simulation a dict of host copies: ``path``, ``leaf``, ``logits``, ``offsets``, ``skip``, ``value`` (None: the maximum
+        logit rule)."""
+        for _ in range(int(sims)):
+            self.descend(root_handle, active)
+            logits, offsets, skip, value = evaluator.evaluate(self)
+            if trace is not None:
+                trace.append(dict(path=self.path.cpu().numpy(), leaf=self.leaf.cpu().numpy(), logits=logits.cpu().numpy(),
+                                  offsets=offsets.cpu().numpy(), skip=skip,
+                                  value=value.cpu().numpy() if value is not None else None))
+            self.backup(logits, offsets, skip, value)
+
+    def status(self) -> None:
+        """Raise if a call since the last check met a limit (reads the device word: synchronises)."""
+        code = int(self._status.item())
+        if code:
+            self._status.zero_()
+            raise _lib.HexGnnError("TreeSearch (status=%d): 1 = a simulation beyond max_sims=%d was not run, 2 = a non-finite "
+                                   "logit or value dropped a simulation, 4 = a leaf got fewer logits than it has legal moves, "
+                                   "8 = the leaves held more edges than the leaf observation" % (code, self.max_sims))
+
+    def tree(self):
+        """Host copies of the tree's arrays by name (``tree_layout``): for tests and inspection."""
+        raw = self.workspace.cpu().numpy()
+        lay, _, _ = tree_layout(self.num_games, self.hex_size, self.max_sims)
+        return {name: raw[off:off + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape).copy()
+                for name, (off, dt, shape) in lay.items()}
+
+
+class UniformEvaluator:
+    """Uniform priors and value 0 at every leaf: plain UCT that learns from decided games alone.  No network, no observation."""
+
+    def __init__(self):
+        self._zeros = None
+
+    def evaluate(self, search: TreeSearch):
+        search.leaf_offsets()
+        n = search.num_games * search.nv
+        if self._zeros is None or self._zeros[0].numel() != n or self._zeros[0].device != search.device:
+            self._zeros = (torch.zeros(n, dtype=torch.float32, device=search.device),
+                           torch.zeros(search.num_games, dtype=torch.float32, device=search.device))
+        return self._zeros[0], search.obs.node_off, 2, self._zeros[1]
+
+
+class QEvaluator:
+    """Leaves through a ``get_pre_defined`` Q-network or a ``MonteCarloPlayer``: the scores of a leaf's rows are its logits
+    (``skip = 2``) and its value is their maximum over the legal rows, clamped to [-1, 1].  These evaluate one side per batch
+    (models.py: the head is chosen once per call) and the leaves' sides are mixed, as in the reference (MCTS.py:213-230), so
+    the capacity-sized leaf observation goes through the model once per side with the side as the hint, and every row takes
+    the output of its own side (``x[:, 2]``): TWO forwards per simulation.  Models with a norm are refused: a whole-batch norm
+    ties the graphs of a batch together."""
+
+    def __init__(self, model_or_player, value: str = "max"):
+        if value != "max":
+            raise NotImplementedError("QEvaluator: value=\"max\" (max_a Q(s, a)) is the one rule")
+        if not callable(model_or_player):
+            raise TypeError("QEvaluator takes a model of get_pre_defined or a MonteCarloPlayer")
+        if live_norm_of(model_or_player):
+            raise NotImplementedError("QEvaluator: a whole-batch norm ties the leaves of a batch together")
+        self.model = model_or_player
+
+    def side_scores(self, search: TreeSearch, is_maker: bool) -> torch.Tensor:
+        """The model's full Q of every row of the leaf observation with the batch declared ``is_maker``'s."""
+        obs = search.obs
+        x, ei = obs.inputs(is_maker, search.nv)
+        with torch.no_grad():
+            q = self.model(x, ei, obs.batch_vec, obs.node_off).reshape(-1)
+        return q if q.dtype == torch.float32 else q.float()
+
+    def evaluate(self, search: TreeSearch):
+        search.leaf_offsets()
+        obs = search.obs
+        obs.observe_env(search.leaf_handle)
+        if search.nv > 128:
+            obs.clear_tail()
+        qm, qb = self.side_scores(search, True), self.side_scores(search, False)
+        q = torch.where(obs.x[:, 2] == 1, qm, qb).contiguous()
+        return q, obs.node_off, 2, None
+
+
+class PolicyValueEvaluator:
+    """Leaves through a ``SAGE_torch_script`` policy / value network without the swap output: logits = its log-policy in its
+    compacted layout (``skip = 0``), value = its tanh value.  The leaves' sides are mixed, which is this network's normal input.
+    The leaf observation is built exact-sized from the sizes the descent reports: one small read-back per simulation (the
+    model's own forward reads back as well)."""
+
+    def __init__(self, model):
+        from .torch_script_models import SAGE_torch_script
+        if not isinstance(model, SAGE_torch_script) or model.swap_allowed:
+            raise NotImplementedError("PolicyValueEvaluator takes a SAGE_torch_script with swap_allowed=False")
+        self.model = model
+
+    def evaluate(self, search: TreeSearch):
+        sizes = search.result[:, 2:4].cpu().numpy().astype(np.int64)
+        t = ObsTarget.exact(sizes, search.device, with_ptr=True)
+        t.observe_env(search.leaf_handle)
+        with torch.no_grad():
+            pi, value, _, out_ptr = self.model(t.x, t.edge_global, t.batch_vec, t.ptr)
+        return pi.float().contiguous(), out_ptr.to(torch.int32).contiguous(), 0, value.float().contiguous()
+
+
+class SearchPlayer:
+    """A player that searches ``sims`` simulations per move with a fresh tree per ply.  ``DeviceArena.play`` (``graph=False``)
+    hands it the root env, the root observation and the mask of undecided games; it answers with the root visit counts in the
+    observation's row layout, from which ``hexgnn_arena_ply`` picks: the most visited move by first maximum at temperature 0,
+    else a draw from softmax(count / T) -- NOT the count ** (1 / T) of AlphaZero's move selection."""
+
+    def __init__(self, evaluator, sims: int, c_puct: float = 1.5, prior_temperature: float = 1.0):
+        if not hasattr(evaluator, "evaluate"):
+            raise TypeError("SearchPlayer takes an evaluator (PolicyValueEvaluator, QEvaluator, UniformEvaluator)")
+        if int(sims) < 1:
+            raise ValueError("sims must be positive")
+        self.evaluator, self.sims, self.c_puct, self.prior_temperature = evaluator, int(sims), float(c_puct), float(prior_temperature)
+        self._search = None
+
+    def search_for(self, env_handle, num_games: int, device) -> TreeSearch:
+        nv = _lib.lib().hexgnn_env_num_vertices(env_handle)
+        size = math.isqrt(nv - 2)
+        s = self._search
+        if s is None or (s.hex_size, s.num_games, s.device) != (size, num_games, torch.device(device)):
+            s = self._search = TreeSearch(size, num_games, self.sims, self.c_puct, self.prior_temperature, device=device)
+        return s
+
+    def search_scores(self, env_handle, obs, active) -> torch.Tensor:
+        s = self.search_for(env_handle, obs.k, obs.x.device)
+        s.reset()
+        s.simulate(env_handle, self.evaluator, self.sims, active=active)
+        return s.root(obs)
+
+    def status(self) -> None:
+        if self._search is not None:
+            self._search.status()

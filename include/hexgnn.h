@@ -937,6 +937,96 @@ typedef struct hexgnn_playout_call {
 } hexgnn_playout_call;
 int hexgnn_playout_values(const hexgnn_playout_call* call, hexgnn_stream_t stream);
 
+/* ---- Batched PUCT tree search (entry points added to ABI 8, nothing existing changes).
+ *      run_many_mcts of GN0/alpha_zero/MCTS.py:53-123,185-260 as a closed device loop: G trees for G games, one 64-lane workgroup
+ *      per game, one leaf per game per simulation, the leaves of all games through one evaluator call.  A TREE, not the
+ *      reference's hash-keyed DAG: transpositions are not merged.  Values are in [-1, 1] seen from the side to move at the node
+ *      (the reference's [0, 1] and 1 - v under v' = 2 v - 1; its 0.5 for an unvisited edge is 0 here).
+ *   Two env handles of equal board size and game count: the ROOT env holds the positions to search and is only read; the LEAF
+ *   env belongs to the search, which stores there the position every simulation reaches.
+ *   The rule.  A node holds the legal moves of its position as edges in ascending vertex id (the order of the observation's rows
+ *     2.. and of get_actions); an edge holds the vertex, the prior P (fp32), the visit count N (int32), the value sum W (fp32) and
+ *     its child (none yet, or a node); a node holds Ns (int32), set to 1 when it is expanded.
+ *     Selection at an expanded node, fp32, every operation rounded on its own, in this order:
+ *       Q(e) = N(e) > 0 ? W(e) / (float) N(e) : 0;  score(e) = Q(e) + ((c_puct * P(e)) * sqrtf((float) Ns)) / (float)(1 + N(e));
+ *       the first maximum in edge order wins (hexgnn_select_actions' comparison; a NaN is never picked).
+ *     Descent from the root: select, play the edge's vertex with dead-and-captured removal (the move routine of every ply
+ *       kernel); stop when the move decides the game -- a TERMINAL, never expanded, its value for the side to move there is -1 if
+ *       that side lost and +1 otherwise -- or when the edge has no child yet: a LEAF, which becomes a node.  A root that is not
+ *       expanded is the leaf of an empty path.
+ *     Expansion of a leaf: P = softmax(logit / temperature) over its legal moves: m = the maximum logit, w_j = expf((l_j - m) /
+ *       temperature), S = the sum of the w_j in the order of HEXGNN_PICK_SOFTMAX (inclusive scans over chunks of 64 consecutive
+ *       edges plus the running carry), P_j = w_j / S; N = W = 0; Ns = 1.  The leaf's value v comes from the evaluator.
+ *     Backup along the path from the leaf upwards: v = -v; N(e) += 1; W(e) += v; Ns(node) += 1.
+ *   Workspace (hexgnn_search_workspace_bytes; C = max_sims + 1 node slots per game, slot 0 the root, A = hex_size^2 edge slots per
+ *     node), sections in this order, each aligned to 256 bytes: int32 Ns [G][C] (0 = not expanded), int32 edges-of-node [G][C],
+ *     int32 [G][2] (node slots in use, simulations applied), fp32 P [G][C][A], fp32 W [G][C][A], int32 N [G][C][A], int32 child
+ *     [G][C][A] (-1 = none), uint16 vertex [G][C][A]; behind the tree two scratch sections that carry one simulation from the
+ *     descent to the backup: fp32 scores [G][A], uint16 leaf moves [G][A].  Every simulation adds at most one node, so the tree
+ *     never fills: a descent of a game whose max_sims simulations are applied leaves the tree as it is, reports SKIPPED and ORs
+ *     bit 1 into *status.  A non-finite logit or value at a leaf drops that game's simulation -- no expansion, no backup -- and
+ *     ORs bit 2; bit 4: the offsets leave a leaf fewer logits than it has legal moves (dropped as well, nothing is read; more are
+ *     allowed: a layout with a fixed stride per game).  status is never cleared here.
+ *   hexgnn_search_reset    every tree becomes one unexpanded root.  Reads num_games, hex_size, max_sims, workspace, status.
+ *   hexgnn_search_descend  loads the root game, points the move routine's response tables at the LEAF env (side flag, move count
+ *     and both tables are copied from the root first), walks the tree, stores the position reached into the leaf env and writes
+ *     path [G][max_sims + 1] (entry d = node * A + edge of step d), the leaf record leaf [G][HEXGNN_SEARCH_REC] = (kind, side to
+ *     move at the leaf 1 = maker, path length, the terminal's value or 0, legal moves of a LEAF), and result [G][5] in
+ *     hexgnn_env_step's format for the leaf env (hexgnn_env_offsets / hexgnn_env_observe run on it unchanged).  A TERMINAL, a
+ *     SKIPPED simulation and a game with active[g] == 0 (active may be NULL; such a game is SKIPPED with an empty path and no
+ *     tree change) store a COPY OF THE ROOT POSITION as the leaf.  The tree is only read; the root env is never written.
+ *   hexgnn_search_backup   expands the LEAFs and backs every non-skipped simulation up.  Game g's logits, one per legal move in edge order, start at logits[offsets[g] +
+ *     skip] and end before offsets[g + 1]: skip = 2 is the observation's row layout (the two terminal rows first), skip = 0 the compacted
+ *     layout of the HexAra policy; value [G], or NULL: a leaf's value is then its maximum logit clamped to [-1, 1] (max_a Q(s, a)
+ *     of a Q-network).  TERMINALs read neither array.
+ *   hexgnn_search_root     the read-out, placed by the root observation's gptr [G + 1]: scores[r] = (float) N(e) on rows 2.. of
+ *     each graph and, on its two terminal rows, the root's mean value sum_e W(e) / (float)(Ns - 1) (0 while Ns < 2; fp32, lane
+ *     l sums edges l, l + 64, .. in order, then an xor butterfly over the lanes 32 .. 1); an unexpanded root gives zeros.
+ *     Optional: counts / q [G][hex_size^2] on the board by vertex - 2 with `fill` on cells without an edge (q = Q(e)); best [G]
+ *     the vertex of the first maximum of the counts, -1 for an unexpanded root.
+ * Latency kernels, one wave per game, one launch each on `stream`, nothing read back.  Checked on the host before any launch, in
+ * this order.  All four: a NULL descriptor or a struct_bytes of another size: HEXGNN_EINVAL; num_games < 0, hex_size < 2,
+ * max_sims outside 1 .. HEXGNN_SEARCH_MAX_SIMS: HEXGNN_EINVAL; hex_size > 25: HEXGNN_EUNSUPPORTED; num_games == 0: HEXGNN_OK
+ * without a launch; workspace or status NULL, workspace_bytes below hexgnn_search_workspace_bytes(...): HEXGNN_EINVAL.  Then
+ * descend: a NULL handle, root == leaf, a handle of another board size or game count; c_puct negative or not finite; path, leaf
+ * or result NULL.  backup: temperature not > 0 or not finite; skip other than 0 / 2; path or leaf NULL; logits or offsets NULL.
+ * root: gptr or scores NULL (counts, q and best may each be NULL).  All HEXGNN_EINVAL. */
+#define HEXGNN_SEARCH_MAX_SIMS 65535
+#define HEXGNN_SEARCH_REC 5
+#define HEXGNN_SEARCH_LEAF 0
+#define HEXGNN_SEARCH_TERMINAL 1
+#define HEXGNN_SEARCH_SKIPPED 2
+typedef struct hexgnn_search_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_search_call), else HEXGNN_EINVAL */
+    int num_games;           /* G */
+    int hex_size;
+    int max_sims;
+    int skip;                /* backup */
+    float c_puct;            /* descend */
+    float temperature;       /* backup */
+    float fill;              /* root */
+    void* workspace;
+    size_t workspace_bytes;
+    int* status;             /* [1] */
+    const int* active;       /* descend: [G] or NULL */
+    int* path;               /* descend writes, backup reads: [G][max_sims + 1] */
+    int* leaf;               /* descend writes, backup reads: [G][HEXGNN_SEARCH_REC] */
+    int* result;             /* descend: [G][5] */
+    const float* logits;     /* backup */
+    const int* offsets;      /* backup: [G + 1] */
+    const float* value;      /* backup: [G] or NULL */
+    const int* gptr;         /* root: [G + 1] */
+    float* scores;           /* root: [N] */
+    float* counts;           /* root: [G][hex_size^2] or NULL */
+    float* q;                /* root: [G][hex_size^2] or NULL */
+    int* best;               /* root: [G] or NULL */
+} hexgnn_search_call;
+size_t hexgnn_search_workspace_bytes(int num_games, int hex_size, int max_sims);   /* 0 for arguments the calls refuse */
+int hexgnn_search_reset(const hexgnn_search_call* call, hexgnn_stream_t stream);
+int hexgnn_search_descend(const hexgnn_env* root, hexgnn_env* leaf, const hexgnn_search_call* call, hexgnn_stream_t stream);
+int hexgnn_search_backup(const hexgnn_search_call* call, hexgnn_stream_t stream);
+int hexgnn_search_root(const hexgnn_search_call* call, hexgnn_stream_t stream);
+
 /* ---- layout helpers (host tensors <-> padded layout) ---------------------------------------- */
 /* dst[n][HP] <- src[n][hidden] (row stride src_stride floats), pad columns zeroed; and back. */
 int hexgnn_pad_rows(int n, int hidden, const float* src, int src_stride, float* dst, hexgnn_stream_t stream);

@@ -99,6 +99,19 @@ class SearchCall(C.Structure):
                 + _fields(vp, "status active path leaf result logits offsets value gptr scores counts q best"))
 
 
+class RecordCall(C.Structure):
+    """``hexgnn_record_call`` of include/hexgnn.h, field for field (tests/test_search_selfplay_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "capacity ply pick_mode")
+                + _fields(vp, "head recorded u pick policy root_q z adj alive side sizes meta"))
+
+
+class PVLossCall(C.Structure):
+    """``hexgnn_pv_loss_call`` of include/hexgnn.h, field for field (tests/test_search_selfplay_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "b n m hex_size capacity")
+                + _fields(C.c_float, "q_ratio val_factor pol_factor")
+                + _fields(vp, "logp out_ptr gptr backmap value policy z root_q index loss d_logp d_value per_graph status"))
+
+
 SEARCH_MAX_SIMS = 65535                                       # HEXGNN_SEARCH_MAX_SIMS
 SEARCH_REC = 5                                                # HEXGNN_SEARCH_REC: kind, side, path length, terminal value, moves
 SEARCH_LEAF, SEARCH_TERMINAL, SEARCH_SKIPPED = 0, 1, 2        # HEXGNN_SEARCH_*
@@ -221,6 +234,10 @@ _SIGS = {
     "hexgnn_search_descend": (ci, [vp, vp, C.POINTER(SearchCall), vp]),
     "hexgnn_search_backup": (ci, [C.POINTER(SearchCall), vp]),
     "hexgnn_search_root": (ci, [C.POINTER(SearchCall), vp]),
+    "hexgnn_search_root_noise": (ci, [C.POINTER(SearchCall), C.c_float, vp, vp]),
+    "hexgnn_search_record": (ci, [vp, C.POINTER(SearchCall), C.POINTER(RecordCall), vp]),
+    "hexgnn_samples_finish": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "hexgnn_pv_loss": (ci, [C.POINTER(PVLossCall), vp]),
     "hexgnn_td_loss_forward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_backward": (ci, [ci, ci, vp, vp, vp, ci, vp, vp, vp]),
     "hexgnn_td_loss_forward_backward": (ci, [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),

@@ -24,28 +24,13 @@
 // (dispatch_words) and one launcher raises the LDS limit and launches (launch_boards), for these kernels and the observation.
 #include <type_traits>
 #include <vector>
+#include "env_state.h"
 #include "hexgnn_reduce.h"
 #include "search_tree.h"
 
 namespace hexgnn {
 
 constexpr int kMaxW = 10;   // up to 640 vertices (Hex-25 = 627)
-
-struct EnvDev {
-    int num_envs, size, nv, W, K;
-    uint64_t* adj;        // [num_envs][nv][W]
-    uint8_t* alive;       // [num_envs][nv]
-    int* maker_turn;      // [num_envs]
-    int* total_moves;     // [num_envs]
-    short* resp_maker;    // [num_envs][nv]  (-1 = none)
-    short* resp_breaker;  // [num_envs][nv]
-    const uint64_t* start_adj;   // [nv][W]
-};
-
-struct Env {   // host handle
-    EnvDev d;
-    void* blob;
-};
 
 // WT = compile-time number of 64-bit words per vertex set.  WT < kMaxW instantiations are launched only for boards with
 // exactly W == WT words (dispatch_words), so Wr() is the constant WT there (register-resident sets, row strides
@@ -409,14 +394,6 @@ __device__ __forceinline__ void load_game(G& g, const EnvDev& d, int env, char* 
     for (int i = threadIdx.x; i < d.nv; i += 64) g.alive[i] = d.alive[(size_t)env * d.nv + i];
     __syncthreads();
 }
-// the LDS game written to adj [nv][W] / alive [nv] and, where given, to a second pair: one pass, every LDS word read once
-template <class G>
-__device__ __forceinline__ void write_game(const G& g, uint64_t* adj, uint8_t* alive, uint64_t* adj2 = nullptr,
-                                           uint8_t* alive2 = nullptr) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < g.nv * g.W; i += 64) { const uint64_t w = g.adj[i]; adj[i] = w; if (adj2) adj2[i] = w; }
-    for (int i = threadIdx.x; i < g.nv; i += 64) { const uint8_t al = g.alive[i]; alive[i] = al; if (alive2) alive2[i] = al; }
-}
 // the game back into its env and, where given, into a snapshot slot snap_adj [nv][W] / snap_alive [nv]
 template <class G>
 __device__ __forceinline__ void store_game(const G& g, const EnvDev& d, int env, uint64_t* snap_adj = nullptr,
@@ -437,21 +414,6 @@ __device__ __forceinline__ void restart_game(G& g, const EnvDev& d, short* rm, s
     reset_game_lds(g, d);
     for (int i = threadIdx.x; i < d.nv; i += 64) { rm[i] = -1; rb[i] = -1; }
 }
-// alive count and directed edge count (uniform)
-template <class G>
-__device__ __forceinline__ void count_game(const G& g, int* n_alive, int* n_dir_edges) {
-    int a = 0, e = 0;
-    for (int k = 0; k < g.K; ++k) {
-        const int x = g.lane + 64 * k;
-        if (x < g.nv && g.alive[x]) {
-            ++a;
-            for (int w = 0; w < g.W; ++w) e += __popcll(g.adj[x * g.W + w]);
-        }
-    }
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); e += __shfl_xor(e, off); }
-    *n_alive = a; *n_dir_edges = e;
-}
-
 // make_move(v) of the side `mt` on the LDS-resident game (the maker's rewiring, v's removal, dead/captured removal over what the
 // move touched), the side flag flipped, who_won returned.  Called by play_move for the side on turn and by env_setup_kernel's
 // stone loop with forced colours.

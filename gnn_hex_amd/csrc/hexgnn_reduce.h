@@ -12,6 +12,28 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// integer sum over the 64 lanes of a wave (xor butterfly 32 .. 1); every lane receives the total
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One chunk of the inclusive scan HEXGNN_PICK_SOFTMAX fixes (graph_pick below states the contract): lane l holds entry l of 64
+// consecutive entries (0 behind the end); shift-and-add over distances 1, 2, .. 32, then the carry of the chunks before.  Returns
+// the lane's inclusive prefix; carry becomes the total so far (lane 63's prefix) in every lane.  float or int.
+template <class T>
+__device__ __forceinline__ T chunk_inclusive_scan(T s, T& carry, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T up = __shfl_up(s, off);
+        if (lane >= off) s += up;
+    }
+    s += carry;
+    carry = __shfl(s, 63);
+    return s;
+}
+
 // sum over a 256-thread block: wave butterflies + the four partials in wave order; every thread receives the total
 __device__ __forceinline__ float block_sum_256(float v, float* s4) {
     v = wave_sum(v);
@@ -33,6 +55,17 @@ __device__ __forceinline__ float tree_mean_256(float acc, float* red, int count)
     return red[0] / (float)(count > 0 ? count : 1);
 }
 
+// The wave step of a first maximum: every lane brings its (value, index) candidate, every lane receives the greatest value and,
+// among equal values, the lowest index (xor butterfly 32 .. 1)
+__device__ __forceinline__ void wave_first_max(float& best, int& arg) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oa = __shfl_xor(arg, off);
+        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    }
+}
+
 // One wave: first row attaining the maximum of q over a graph's non-terminal rows [r0 + 2, r1) (torch.argmax tie rule: among
 // equal values the lowest index).  Every lane receives best / arg; a graph without such a row leaves arg = 0x7fffffff.
 __device__ __forceinline__ void graph_first_max(const float* q, int r0, int r1, int lane, float& best, int& arg) {
@@ -42,12 +75,7 @@ __device__ __forceinline__ void graph_first_max(const float* q, int r0, int r1, 
         const float v = q[i];
         if (v > best || (v == best && i < arg)) { best = v; arg = i; }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(arg, off);
-        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-    }
+    wave_first_max(best, arg);
 }
 
 // The epsilon-greedy pick on top of graph_first_max's arg, for a graph of rows [r0, r1): the greedy node's rank inside the graph
@@ -112,14 +140,7 @@ __device__ __forceinline__ int graph_pick(const float* q, int r0, int r1, int la
         for (int base = r0 + 2; base < r1; base += 64) {
             const int i = base + lane;
             const float w = i < r1 ? expf((q[i] - m) / temperature) : 0.f;
-            float s = w;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float t = __shfl_up(s, off);
-                if (lane >= off) s += t;
-            }
-            s += carry;
-            carry = __shfl(s, 63);
+            const float s = chunk_inclusive_scan(w, carry, lane);
             if (pass == 1) {
                 const uint64_t hit = __ballot(i < r1 && s > thr), pos = __ballot(w > 0.f);
                 if (pos) last = base + 63 - __builtin_clzll(pos);

@@ -71,14 +71,7 @@ __global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
         float S = 0.f;
         for (int c0 = 0; c0 < ne; c0 += 64) {
             const int e = c0 + lane;
-            float s = e < ne ? expf((a.logits[base + e] - m) / a.temperature) : 0.f;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float up = __shfl_up(s, off);
-                if (lane >= off) s += up;
-            }
-            s += S;
-            S = __shfl(s, 63);
+            chunk_inclusive_scan(e < ne ? expf((a.logits[base + e] - m) / a.temperature) : 0.f, S, lane);
         }
         const size_t e0 = t.edge(g, node);
         const uint16_t* mv = t.moves + (size_t)g * t.A;

@@ -1495,6 +1495,65 @@ def td_loss(q: torch.Tensor, sel: torch.Tensor, target: torch.Tensor, weights: O
     return out
 
 
+class PolicyValueLossFn(torch.autograd.Function):
+    """The policy/value update's loss over ``hexgnn_pv_loss`` (include/hexgnn.h): ``val_factor * sum_g (value_g - y_g) ** 2 +
+    pol_factor * sum_g sum_j -t_gj * logp_j`` with ``y = (1 - q_ratio) z + q_ratio root_q`` and the targets ``t`` read from the
+    sample ring's ``policy`` rows by board cell -- the reference's ``MSELoss * B + SoftCrossEntropy`` of
+    rl_loop/trainer_agent_pytorch.py.  ``logp [M]`` / ``out_ptr [b + 1]``: the network's compacted log-policy; ``gptr`` int32
+    ``[b + 1]`` / ``backmap``: the batch's observation; ``index`` int32 ``[b]``: the drawn slots; ``status``: int32 [1], bit 64.
+    Returns ``(loss [], per_graph [b, 4])`` with ``per_graph = (ce, se, policy argmax hit, value sign hit)``; the one call
+    also produces both gradients, and the backward scales them by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, logp, value, out_ptr, gptr, backmap, policy, z, root_q, index, hex_size: int, q_ratio: float,
+                val_factor: float, pol_factor: float, status):
+        dev = logp.device
+        _require_cuda(logp, "logp")
+        lp, v = _f32c(logp.reshape(-1)), _f32c(value.reshape(-1))
+        b, m, n = int(v.numel()), int(lp.numel()), int(backmap.numel())
+        if out_ptr.dtype != torch.int64 or gptr.dtype != torch.int32 or index.dtype != torch.int32 or backmap.dtype != torch.int64:
+            raise ValueError("out_ptr / backmap int64, gptr / index int32")
+        if out_ptr.numel() != b + 1 or gptr.numel() != b + 1 or index.numel() != b:
+            raise ValueError("out_ptr and gptr hold b + 1 = %d entries, index b" % (b + 1))
+        if policy.dtype != torch.float32 or policy.dim() != 2 or policy.shape[1] != hex_size * hex_size or not policy.is_contiguous():
+            raise ValueError("policy: the ring's contiguous float32 [capacity, %d]" % (hex_size * hex_size))
+        cap = int(policy.shape[0])
+        for name, t in (("z", z), ("root_q", root_q)):
+            if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < cap or not t.is_contiguous():
+                raise ValueError("%s: the ring's contiguous float32 [capacity = %d]" % (name, cap))
+        if status.dtype != torch.int32 or status.numel() < 1 or not status.is_contiguous():
+            raise ValueError("status: an int32 [1] tensor")
+        for name, t in (("out_ptr", out_ptr), ("gptr", gptr), ("backmap", backmap), ("index", index)):
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        for name, t in (("value", v), ("out_ptr", out_ptr), ("gptr", gptr), ("backmap", backmap), ("policy", policy), ("z", z),
+                        ("root_q", root_q), ("index", index), ("status", status)):
+            if t.device != dev:
+                raise ValueError("%s is on %s, logp on %s" % (name, t.device, dev))
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        d_logp = torch.empty(m, dtype=torch.float32, device=dev)
+        d_value = torch.empty(b, dtype=torch.float32, device=dev)
+        per_graph = torch.empty((b, 4), dtype=torch.float32, device=dev)
+        call = _lib.PVLossCall(struct_bytes=C.sizeof(_lib.PVLossCall), b=b, n=n, m=m, hex_size=int(hex_size),
+                               capacity=cap, q_ratio=float(q_ratio), val_factor=float(val_factor),
+                               pol_factor=float(pol_factor), logp=lp.data_ptr(), out_ptr=out_ptr.data_ptr(),
+                               gptr=gptr.data_ptr(), backmap=backmap.data_ptr(), value=v.data_ptr(), policy=policy.data_ptr(),
+                               z=z.data_ptr(), root_q=root_q.data_ptr(), index=index.data_ptr(), loss=loss.data_ptr(),
+                               d_logp=d_logp.data_ptr(), d_value=d_value.data_ptr(), per_graph=per_graph.data_ptr(),
+                               status=status.data_ptr())
+        _lib.check(_lib.lib().hexgnn_pv_loss(C.byref(call), _stream()), "hexgnn_pv_loss")
+        ctx.save_for_backward(d_logp, d_value)
+        ctx.shapes = (logp.shape, value.shape)
+        ctx.mark_non_differentiable(per_graph)
+        return loss, per_graph
+
+    @staticmethod
+    def backward(ctx, gloss, _gpg):
+        d_logp, d_value = ctx.saved_tensors
+        g = gloss.reshape(()).float()
+        return ((d_logp * g).view(ctx.shapes[0]), (d_value * g).view(ctx.shapes[1])) + (None,) * 12
+
+
 def backward(loss: torch.Tensor) -> None:
     """``loss.backward()`` for a loss returned by ``td_loss`` without the two launches autograd adds around it: the
     ``ones_like(loss)`` fill that seeds the pass, and the scaling scatter of ``d loss / d Q`` (the fused forward launch

@@ -6,7 +6,9 @@ leaf env) -> the leaf observation (``hexgnn_env_offsets`` / ``hexgnn_env_observe
 ``hexgnn_search_backup`` (expand the leaf with softmax(logit / T) priors, back its value up).  ``hexgnn_search_root`` reads the
 root visit counts out in the layout of the root observation, so ``hexgnn_arena_ply`` picks from them like from any model's output.
 The rule is restated in include/hexgnn.h and on the host in tests/search_oracle.py.  A tree, not the reference's hash-keyed DAG:
-transpositions are not merged; no tree reuse between plies, no Dirichlet noise, one leaf per game per round, no swap rule.
+transpositions are not merged; no tree reuse between plies, one leaf per game per round, no swap rule.  Dirichlet noise on the
+root priors is ``TreeSearch.add_root_noise`` / ``simulate(root_noise=...)`` (``hexgnn_search_root_noise``); the self-play loop
+that uses it, the sample ring and the policy/value update are gnn_hex_amd/search_selfplay.py.
 
 ``TreeSearch``             the trees, the leaf env and the simulation loop.
 ``PolicyValueEvaluator``   leaves through a ``SAGE_torch_script`` policy / value network (the HexAra network).
@@ -147,11 +149,36 @@ class TreeSearch:
         self._status.bitwise_or_(over.to(torch.int32) * 8)
         obs.edge_off.mul_((~over).to(torch.int32))
 
-    def simulate(self, root_handle, evaluator, sims: int, active=None, trace=None) -> None:
+    def add_root_noise(self, eps: float, alpha: float, active=None, generator=None) -> torch.Tensor:
+        """Dirichlet(alpha) noise on the priors of every expanded root (of the games with ``active[g] != 0``):
+        ``P = (1 - eps) P + eps * noise / sum(noise)`` over the root's edges (``hexgnn_search_root_noise``; the reference's
+        Dirichlet_Epsilon / Dirichlet_Alpha, main/options.cpp:49-53).  The Gamma(alpha) draws are ``torch._standard_gamma`` on
+        the device from ``generator``; returned (float32 [G, hex_size ** 2]) so that a test can restate the rule."""
+        if not 0.0 <= float(eps) <= 1.0 or not (alpha > 0 and math.isfinite(alpha)):
+            raise ValueError("eps in [0, 1], alpha finite and > 0")
+        G, A = self.num_games, self.hex_size ** 2
+        noise = torch._standard_gamma(torch.full((G, A), float(alpha), dtype=torch.float32, device=self.device), generator=generator)
+        self.apply_root_noise(eps, noise, active)
+        return noise
+
+    def apply_root_noise(self, eps: float, noise, active=None) -> None:
+        """``hexgnn_search_root_noise`` with the caller's ``noise`` (contiguous float32 [G, hex_size ** 2] on the device)."""
+        G, A = self.num_games, self.hex_size ** 2
+        if noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (G, A) or noise.device != self.device:
+            raise ValueError("noise: a contiguous float32 [%d, %d] tensor on %s" % (G, A, self.device))
+        if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != G
+                                   or active.device != self.device):
+            raise ValueError("active: a contiguous int32 [%d] tensor on %s" % (G, self.device))
+        call = self._call(active=active.data_ptr() if active is not None else None)
+        _lib.check(_lib.lib().hexgnn_search_root_noise(C.byref(call), float(eps), noise.data_ptr(), ops._stream()),
+                   "hexgnn_search_root_noise")
+
+    def simulate(self, root_handle, evaluator, sims: int, active=None, trace=None, root_noise=None, generator=None) -> None:
         """``sims`` simulations per game: descend -> ``evaluator.evaluate(self)`` -> backup.  ``trace``: a list that receives per
         simulation a dict of host copies: ``path``, ``leaf``, ``logits``, ``offsets``, ``skip``, ``value`` (None: the maximum
-        logit rule)."""
-        for _ in range(int(sims)):
+        logit rule).  ``root_noise = (eps, alpha)``: ``add_root_noise`` (draws from ``generator``) once, behind the first
+        simulation of the call -- on a fresh tree the one that expands the root."""
+        for i in range(int(sims)):
             self.descend(root_handle, active)
             logits, offsets, skip, value = evaluator.evaluate(self)
             if trace is not None:
@@ -159,6 +186,8 @@ class TreeSearch:
                                   offsets=offsets.cpu().numpy(), skip=skip,
                                   value=value.cpu().numpy() if value is not None else None))
             self.backup(logits, offsets, skip, value)
+            if i == 0 and root_noise is not None:
+                self.add_root_noise(root_noise[0], root_noise[1], active=active, generator=generator)
 
     def status(self) -> None:
         """Raise if a call since the last check met a limit (reads the device word: synchronises)."""
@@ -167,7 +196,8 @@ class TreeSearch:
             self._status.zero_()
             raise _lib.HexGnnError("TreeSearch (status=%d): 1 = a simulation beyond max_sims=%d was not run, 2 = a non-finite "
                                    "logit or value dropped a simulation, 4 = a leaf got fewer logits than it has legal moves, "
-                                   "8 = the leaves held more edges than the leaf observation" % (code, self.max_sims))
+                                   "8 = the leaves held more edges than the leaf observation, 16 = root noise that is negative, not "
+                                   "finite or sums to nothing was not applied" % (code, self.max_sims))
 
     def tree(self):
         """Host copies of the tree's arrays by name (``tree_layout``): for tests and inspection."""

@@ -1027,6 +1027,114 @@ int hexgnn_search_descend(const hexgnn_env* root, hexgnn_env* leaf, const hexgnn
 int hexgnn_search_backup(const hexgnn_search_call* call, hexgnn_stream_t stream);
 int hexgnn_search_root(const hexgnn_search_call* call, hexgnn_stream_t stream);
 
+/* ---- Search self-play: training samples and the policy/value loss (entry points added to ABI 8, nothing existing changes).
+ *      The AlphaZero pipeline of the reference's CrazyAra engine on top of the search above: Dirichlet noise on the root priors
+ *      and a move drawn in proportion to the visit counts (cpp_hex/CrazyAra/rl/selfplay.cpp, main/options.cpp:49-53,71-76), one
+ *      sample per move = the position, the visit distribution, the game result as +-1 for the side to move and the root's Q
+ *      (rl/traindataexporter.cpp:58-88,196-230), the value target (1 - q_value_ratio) z + q_value_ratio q
+ *      (rl_loop/dataset_loader.py:74) and the loss val_loss_factor MSE B + policy_loss_factor sum(-target log_policy)
+ *      (rl_loop/trainer_agent_pytorch.py:245-275,326-337).  Scope: no swap rule; the move is the most visited one or a draw
+ *      proportional to the counts (no other temperature exponent, no temperature decay); one match at a time fills the ring's
+ *      tail.  Not part of this: a captured update, tree reuse, transposition merging.
+ *   hexgnn_search_root_noise  acts on every game with active[g] != 0 (active NULL: all) whose root is expanded, ne its edges:
+ *     S = the sum of noise[g][0 .. ne) in the order of HEXGNN_PICK_SOFTMAX (inclusive scans over chunks of 64 consecutive
+ *     entries plus the running carry), then P(e_j) = (1 - eps) P(e_j) + eps (noise[g][j] / S) in fp32, every operation (the
+ *     subtraction, the division, both products, the sum) rounded on its own, no fused multiply-add.  noise is [G][A], A =
+ *     hex_size^2: the caller's Gamma(alpha) draws (normalised here they are Dirichlet(alpha)); the kernel holds no generator and
+ *     no transcendental.  An unexpanded root is left alone.  A noise entry of the game that is negative or not finite, or an S
+ *     that is not finite or not > 0, leaves the game's priors untouched and ORs bit 16 into *status.  Reads num_games,
+ *     hex_size, max_sims, workspace, status, active of the descriptor.
+ *   hexgnn_search_record  one training sample and one move choice per game from the finished search of this ply.  Game g is
+ *     RECORDED iff active[g] != 0 (NULL: all), its root is expanded and T = Ns(root) - 1 > 0.  Its rank r = the number of
+ *     recorded games of lower index, its slot = (*head + r) mod capacity (head int64 [1] on the device, read); a second
+ *     one-wave launch inside the call then makes *head += recorded and recorded[0] = the count, in stream order.  The slot
+ *     receives: policy[slot][c] = 0 for all A cells and policy[slot][vertex(e) - 2] = (float) N(e) / (float) T for every root
+ *     edge, one IEEE division each; root_q[slot] = sum_e W(e) / (float) T with exactly hexgnn_search_root's summation (lane l
+ *     sums edges l, l + 64, .., xor butterfly 32 .. 1) and division; adj[slot][nv][words] / alive[slot][nv] = the board of root
+ *     env g in hexgnn_env_export's layout, side[slot] (1 = maker to move) and sizes[slot] = (nodes, directed edges) -- the
+ *     arrays hexgnn_states_observe takes --; meta[slot] = (g, ply); z[slot] = 0.  The root env is only read.
+ *     pick[g], a vertex, shaped to be hexgnn_arena_ply's `forced`: pick_mode 0: the vertex of the first maximum of the counts
+ *     (best of hexgnn_search_root); pick_mode 1, proportional to the counts, integers only: t = (uint32)(u[g] * 16777216.0f)
+ *     (u in [0, 1) as torch.rand gives it: the product is exact; anything else is clamped into 0 .. 2^24 - 1),
+ *     k = (uint32)(((uint64) t * T) >> 24), the pick is the first edge in edge order whose inclusive running sum of N exceeds
+ *     k.  A game that is not recorded gets pick[g] = -1 and nothing of the ring is written for it.  No write ever lands outside
+ *     the capacity slots, whatever *head holds.
+ *   hexgnn_samples_finish  the labels of the match just played: for i < count, slot = (first + i) mod capacity, g =
+ *     meta[slot][0], w = game[g][0] of hexgnn_arena_ply's record: w >= 0: z[slot] = ((w == 0) == (side[slot] == 1)) ? 1 : -1,
+ *     the result seen from the side to move at the sample (winner 0 is the maker: the search's own value convention);
+ *     w < 0, or a g outside 0 .. num_games - 1: z[slot] = NaN and bit 32 is ORed into *status.
+ *   hexgnn_pv_loss  loss and both gradients of one update.  Graph g of the batch (b graphs drawn from the ring, slot
+ *     index[g]): its log-policy rows are logp[out_ptr[g] .. out_ptr[g + 1]) (the network's compacted layout); compacted row j is
+ *     observation row gptr[g] + 2 + j and its board cell backmap[that row] - 2.  t_gj = policy[index[g]][cell];
+ *     y_g = (1 - q_ratio) z + q_ratio root_q;  ce_g = sum_j -t_gj logp_j (lane l sums rows l, l + 64, .., xor butterfly);
+ *     se_g = (value_g - y_g)^2;  loss[0] = val_factor sum_g se_g + pol_factor sum_g ce_g, both sums in that same lane-stride +
+ *     butterfly order over the graphs (a second one-wave launch).  d_logp [M] = -pol_factor t, d_value [b] =
+ *     2 val_factor (value - y), per_graph [b][4] = (ce_g, se_g, 1 if the first maximum of logp and the first maximum of t fall
+ *     on the same row else 0, 1 if sign(value) == sign(y) else 0; sign(0) = 0).  A row whose cell lies outside the board
+ *     contributes nothing (d_logp 0).  A graph whose row count gptr[g + 1] - gptr[g] - 2 differs from out_ptr[g + 1] -
+ *     out_ptr[g], whose rows leave [0, n) / [0, m) or whose index leaves the ring ORs bit 64 into *status and contributes zeros
+ *     everywhere.  d_logp is cleared (one memset node) before the first launch.  Same inputs, same bits.
+ * Latency kernels like the search's: one wave per game / graph, nothing read back, plain vector stores, no performance claim.
+ * status is never cleared here.  Checked on the host before any launch, in this order.
+ *   root_noise, record: the checks of hexgnn_search_* above, up to and including workspace_bytes (num_games == 0 returns
+ *     HEXGNN_OK there).  Then root_noise: eps outside [0, 1] (a NaN included) or noise NULL: HEXGNN_EINVAL.  record: a NULL root
+ *     handle, or one of another board size or game count; a NULL record descriptor or a struct_bytes of another size; capacity <
+ *     num_games * hex_size^2, ply < 0, pick_mode outside 0 .. 1; head, recorded, pick, policy, root_q, z, adj, alive, side,
+ *     sizes or meta NULL, or u NULL with pick_mode 1: all HEXGNN_EINVAL.
+ *   samples_finish: count < 0, capacity < 1, num_games < 0, first outside 0 .. capacity - 1 or count > capacity: HEXGNN_EINVAL;
+ *     count == 0: HEXGNN_OK without a launch; meta, side, z, game or status NULL: HEXGNN_EINVAL.
+ *   pv_loss: a NULL descriptor or a struct_bytes of another size; b, n or m negative, hex_size < 2, capacity < 1:
+ *     HEXGNN_EINVAL; hex_size > 25: HEXGNN_EUNSUPPORTED; b == 0: HEXGNN_OK without a launch; any pointer NULL: HEXGNN_EINVAL. */
+typedef struct hexgnn_record_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_record_call), else HEXGNN_EINVAL */
+    int capacity;            /* slots of the ring, >= num_games * hex_size^2: a whole match fits */
+    int ply;
+    int pick_mode;           /* 0 = most visited, 1 = proportional to the counts */
+    int64_t* head;           /* [1] on the device: samples recorded so far */
+    int* recorded;           /* [1] */
+    const float* u;          /* [G], pick_mode 1 */
+    int* pick;               /* [G] */
+    float* policy;           /* [capacity][hex_size^2] */
+    float* root_q;           /* [capacity] */
+    float* z;                /* [capacity] */
+    uint64_t* adj;           /* [capacity][nv][words] */
+    uint8_t* alive;          /* [capacity][nv] */
+    uint8_t* side;           /* [capacity] */
+    int* sizes;              /* [capacity][2] */
+    int* meta;               /* [capacity][2] */
+} hexgnn_record_call;
+typedef struct hexgnn_pv_loss_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_pv_loss_call), else HEXGNN_EINVAL */
+    int b;                   /* graphs */
+    int n;                   /* observation rows (backmap) */
+    int m;                   /* log-policy rows (logp, d_logp) */
+    int hex_size;
+    int capacity;
+    float q_ratio;
+    float val_factor;
+    float pol_factor;
+    const float* logp;       /* [m] */
+    const int64_t* out_ptr;  /* [b + 1] */
+    const int* gptr;         /* [b + 1] */
+    const int64_t* backmap;  /* [n] */
+    const float* value;      /* [b] */
+    const float* policy;     /* the ring's [capacity][hex_size^2] */
+    const float* z;          /* [capacity] */
+    const float* root_q;     /* [capacity] */
+    const int* index;        /* [b] slots */
+    float* loss;             /* [1] */
+    float* d_logp;           /* [m] */
+    float* d_value;          /* [b] */
+    float* per_graph;        /* [b][4] */
+    int* status;             /* [1] */
+} hexgnn_pv_loss_call;
+int hexgnn_search_root_noise(const hexgnn_search_call* call, float eps, const float* noise, hexgnn_stream_t stream);
+int hexgnn_search_record(const hexgnn_env* root, const hexgnn_search_call* call, const hexgnn_record_call* record,
+                         hexgnn_stream_t stream);
+int hexgnn_samples_finish(int first, int count, int capacity, int num_games, const int* meta, const uint8_t* side, float* z,
+                          const int* game, int* status, hexgnn_stream_t stream);
+int hexgnn_pv_loss(const hexgnn_pv_loss_call* call, hexgnn_stream_t stream);
+
 /* ---- layout helpers (host tensors <-> padded layout) ---------------------------------------- */
 /* dst[n][HP] <- src[n][hidden] (row stride src_stride floats), pad columns zeroed; and back. */
 int hexgnn_pad_rows(int n, int hidden, const float* src, int src_stride, float* dst, hexgnn_stream_t stream);

@@ -162,7 +162,8 @@ def search_match(args, handler, model):
     """``--search``: the model searching ``SIMS`` simulations per move (``QEvaluator`` -> ``SearchPlayer``) against the same
     model playing its greedy move, both ways round."""
     from gnn_hex_amd.search import QEvaluator, SearchPlayer
-    handler.add_player("search%d" % args.search, model=SearchPlayer(QEvaluator(model), args.search), uses_empty_model=False)
+    handler.add_player("search%d" % args.search, model=SearchPlayer(QEvaluator(model), args.search, leaves=args.leaves,
+                                                                   virtual_loss=args.virtual_loss), uses_empty_model=False)
     handler.add_player("greedy", model=model, uses_empty_model=False)
     for maker, breaker in (("search%d" % args.search, "greedy"), ("greedy", "search%d" % args.search)):
         t0 = time.perf_counter()
@@ -192,6 +193,9 @@ def main():
                     help="rate the first model against Monte-Carlo playout players of R playouts per move, beside random")
     ap.add_argument("--search", type=int, default=0, metavar="SIMS",
                     help="play the first model with a PUCT search of SIMS simulations per move against its own greedy play")
+    ap.add_argument("--leaves", type=int, default=1,
+                    help="--search: leaves per game per round under virtual loss (1: one leaf per round; else < SIMS)")
+    ap.add_argument("--virtual-loss", type=int, default=1, help="--search: the virtual loss of a round of several leaves")
     ap.add_argument("--matches", type=int, default=1, help="matches per timed window (a window should last a good part of a second)")
     ap.add_argument("--repeat", type=int, default=1, help="timed windows to play (the first one includes graph capture)")
     args = ap.parse_args()

@@ -99,6 +99,11 @@ class SearchCall(C.Structure):
                 + _fields(vp, "status active path leaf result logits offsets value gptr scores counts q best"))
 
 
+class SearchRoundCall(C.Structure):
+    """``hexgnn_search_round_call`` of include/hexgnn.h, field for field (tests/test_search_round_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + [("call", SearchCall)] + _fields(ci, "leaves round_leaves virtual_loss"))
+
+
 class RecordCall(C.Structure):
     """``hexgnn_record_call`` of include/hexgnn.h, field for field (tests/test_search_selfplay_host.py compares the two)."""
     _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "capacity ply pick_mode")
@@ -115,6 +120,9 @@ class PVLossCall(C.Structure):
 SEARCH_MAX_SIMS = 65535                                       # HEXGNN_SEARCH_MAX_SIMS
 SEARCH_REC = 5                                                # HEXGNN_SEARCH_REC: kind, side, path length, terminal value, moves
 SEARCH_LEAF, SEARCH_TERMINAL, SEARCH_SKIPPED = 0, 1, 2        # HEXGNN_SEARCH_*
+SEARCH_COLLISION = 3                                          # HEXGNN_SEARCH_COLLISION: a descent of a round of several leaves
+SEARCH_MAX_LEAVES = 64                                        # HEXGNN_SEARCH_MAX_LEAVES
+SEARCH_MAX_VIRTUAL_LOSS = 1024                                # HEXGNN_SEARCH_MAX_VIRTUAL_LOSS
 
 
 STONE_COLOURS = {"b": 0, "m": 1, "turn": 2}      # HEXGNN_STONE's colour field
@@ -234,6 +242,9 @@ _SIGS = {
     "hexgnn_search_descend": (ci, [vp, vp, C.POINTER(SearchCall), vp]),
     "hexgnn_search_backup": (ci, [C.POINTER(SearchCall), vp]),
     "hexgnn_search_root": (ci, [C.POINTER(SearchCall), vp]),
+    "hexgnn_search_round_workspace_bytes": (sz, [ci, ci, ci, ci]),
+    "hexgnn_search_round_descend": (ci, [vp, vp, C.POINTER(SearchRoundCall), vp]),
+    "hexgnn_search_round_backup": (ci, [C.POINTER(SearchRoundCall), vp]),
     "hexgnn_search_root_noise": (ci, [C.POINTER(SearchCall), C.c_float, vp, vp]),
     "hexgnn_search_record": (ci, [vp, C.POINTER(SearchCall), C.POINTER(RecordCall), vp]),
     "hexgnn_samples_finish": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),

@@ -14,7 +14,7 @@
 // clique" / "find the twin" are per-lane tests combined with wave ballots.  Integer/bit work: no MFMA, bound by LDS
 // latency; results are bit-exact against oracle/env_ref.c (same canonical ascending order).
 //
-// The per-env kernels (env_step_kernel, arena_ply_kernel, rollout_ply_kernel, env_setup_kernel, search_descend_kernel) are built from one copy of each
+// The per-env kernels (env_step_kernel, arena_ply_kernel, rollout_ply_kernel, env_setup_kernel, search_descend_kernel, search_round_descend_kernel) are built from one copy of each
 // piece: load_game / store_game (write_game: the env and, for the rollout and the set-up, a snapshot), play_vertex, play_move
 // (legality, the move, the restart of a decided game, the counts), restart_game, put_result; the rollout's pick is
 // eps_greedy_rank of hexgnn_reduce.h, the one select_actions_kernel makes.  A kernel holds what is its own: the arena's resting
@@ -710,6 +710,106 @@ struct DescendArgs {
     int* status;
 };
 
+// Where a descent stands: its kind, the steps walked, a terminal's value, the side to move and the move count there.
+struct Descent { int kind, len, tval, mt, moves; };
+
+// The walk of one descent from the root, the one copy behind search_descend_kernel and search_round_descend_kernel.  g holds the
+// root game, d starts as (LEAF, 0, 0, the root's side, the root's move count).  ROUND: selection under the in-flight counts
+// I(e) of the running round with the virtual loss vl (include/hexgnn.h; with every I = 0 the one-leaf expressions, bit for bit), an
+// edge without a child on which an earlier descent waits ends the walk as a COLLISION, and so does an unexpanded root once
+// root_waits says that an earlier descent of the round took it as its leaf.  Only the scratch row sc and path are written.
+template <int WT, bool ROUND>
+__device__ __forceinline__ void search_walk(GameT<WT>& g, const SearchTree& t, int nv, int env, int lane, float c_puct, int vl,
+                                            bool root_waits, float* sc, int* path, short* rm, short* rb, Descent& d) {
+    int node = 0;
+    while (true) {
+        const int ns = t.ns[t.node(env, node)];
+        if (ns == 0) {                                        // not expanded: the leaf (only the root is ever met this way)
+            if (ROUND && root_waits) d.kind = kSearchCollision;
+            break;
+        }
+        const int ne = t.ne[t.node(env, node)];
+        if (ne < 1 || ne > t.A || d.len >= t.C) { d.kind = kSearchSkipped; break; }     // no tree this search has built
+        const size_t e0 = t.edge(env, node);
+        int ns_adj = ns;
+        if (ROUND) {                                          // Ns' = Ns + vl * sum_e I(e): integers, any order
+            int inf = 0;
+            for (int e = lane; e < ne; e += 64) inf += t.inflight[e0 + e];
+            ns_adj = ns + vl * wave_sum_int(inf);
+        }
+        const float sq = __fsqrt_rn((float)ns_adj);
+        for (int e = lane; e < ne; e += 64) {                 // every operation rounded on its own: no contraction
+            int n = t.N[e0 + e];
+            float w = t.W[e0 + e];
+            if (ROUND) {
+                const int iv = vl * t.inflight[e0 + e];
+                n += iv;
+                w = __fsub_rn(w, (float)iv);
+            }
+            const float q = n > 0 ? __fdiv_rn(w, (float)n) : 0.f;
+            const float u = __fdiv_rn(__fmul_rn(__fmul_rn(c_puct, t.P[e0 + e]), sq), (float)(1 + n));
+            sc[e] = __fadd_rn(q, u);
+        }
+        float best;
+        int arg;
+        graph_first_max(sc, -2, ne, lane, best, arg);         // rows [r0 + 2, r1) = entries [0, ne)
+        if (arg == 0x7fffffff) { d.kind = kSearchSkipped; break; }
+        const int v = t.vertex[e0 + arg];
+        if (v < 2 || v >= nv || !g.alive[v]) { d.kind = kSearchSkipped; break; }
+        if (lane == 0) path[d.len] = node * t.A + arg;
+        ++d.len;
+        ++d.moves;
+        const int winner = play_vertex(g, v, d.mt, true, rm, rb);
+        if (winner >= 0) {                                    // decided: the side to move there has won or lost
+            d.kind = kSearchTerminal;
+            d.tval = winner == (d.mt ? 0 : 1) ? 1 : -1;
+            break;
+        }
+        const int child = t.child[e0 + arg];
+        if (child < 0) {                                      // no child yet: the leaf, unless a descent of this round waits on it
+            if (ROUND && t.inflight[e0 + arg] > 0) d.kind = kSearchCollision;
+            break;
+        }
+        if (child >= t.C) { d.kind = kSearchSkipped; break; }
+        node = child;
+    }
+}
+
+// The end of a descent, the one copy behind both descent kernels: the position reached (a LEAF) or a copy of the root position
+// (every other kind) goes into game `slot` of the leaf env with its result row, a LEAF's legal moves into mv, the record into rec.
+template <int WT>
+__device__ __forceinline__ void search_store_leaf(GameT<WT>& g, const EnvDev& root, const EnvDev& leaf, int env, int slot, int lane,
+                                                  char* lds, Descent d, short* rm, short* rb, uint16_t* mv, int* result, int* rec) {
+    const int root_mt = root.maker_turn[env], root_moves = root.total_moves[env];
+    const int leaf_side = d.mt;
+    int n_moves = 0;
+    if (d.kind != kSearchLeaf) {                              // the leaf env gets a copy of the root position
+        const short* root_rm = root.resp_maker + (size_t)env * root.nv;
+        const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
+        __syncthreads();
+        load_game(g, root, env, lds);
+        for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
+        d.mt = root_mt;
+        d.moves = root_moves;
+        if (d.kind == kSearchSkipped) d.len = 0;
+    } else {                                                  // the leaf's legal moves, ascending, for its expansion
+        for (int k = 0; k < g.K; ++k) {
+            const int x = lane + 64 * k;
+            const bool al = x >= 2 && x < root.nv && g.alive[x];
+            const uint64_t bal = __ballot(al);
+            if (al) mv[n_moves + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)x;
+            n_moves += __popcll(bal);
+        }
+    }
+    Move m = {-1, d.moves, 0, d.mt, d.moves, 0, 0};
+    count_game(g, &m.n_alive, &m.n_dir_edges);
+    store_game(g, leaf, slot);
+    if (lane == 0) {
+        put_result(leaf, slot, result, m);
+        rec[0] = d.kind; rec[1] = d.kind == kSearchSkipped ? root_mt : leaf_side; rec[2] = d.len; rec[3] = d.tval; rec[4] = n_moves;
+    }
+}
+
 template <int WT>
 __global__ __launch_bounds__(64) void search_descend_kernel(EnvDev root, DescendArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -722,76 +822,69 @@ __global__ __launch_bounds__(64) void search_descend_kernel(EnvDev root, Descend
     const short* root_rm = root.resp_maker + (size_t)env * root.nv;
     const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
     for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
-    const int root_mt = root.maker_turn[env], root_moves = root.total_moves[env];
-    int mt = root_mt, moves = root_moves, kind = kSearchLeaf, len = 0, tval = 0, node = 0;
-    int* path = a.path + (size_t)env * t.C;
+    Descent d = {kSearchLeaf, 0, 0, root.maker_turn[env], root.total_moves[env]};
     if (a.active && !a.active[env]) {
-        kind = kSearchSkipped;                                // a resting game: no tree change, leaf = root
+        d.kind = kSearchSkipped;                              // a resting game: no tree change, leaf = root
     } else if (t.cnt[2 * env + 1] >= a.max_sims) {
-        kind = kSearchSkipped;
+        d.kind = kSearchSkipped;
         if (lane == 0) atomicOr(a.status, 1);
     } else {
-        float* sc = t.score + (size_t)env * t.A;
-        while (true) {
-            const int ns = t.ns[t.node(env, node)];
-            if (ns == 0) break;                               // not expanded: the leaf
-            const int ne = t.ne[t.node(env, node)];
-            if (ne < 1 || ne > t.A || len >= t.C) { kind = kSearchSkipped; break; }     // no tree this search has built
-            const size_t e0 = t.edge(env, node);
-            const float sq = __fsqrt_rn((float)ns);
-            for (int e = lane; e < ne; e += 64) {             // every operation rounded on its own: no contraction
-                const int n = t.N[e0 + e];
-                const float q = n > 0 ? __fdiv_rn(t.W[e0 + e], (float)n) : 0.f;
-                const float u = __fdiv_rn(__fmul_rn(__fmul_rn(a.c_puct, t.P[e0 + e]), sq), (float)(1 + n));
-                sc[e] = __fadd_rn(q, u);
-            }
-            float best;
-            int arg;
-            graph_first_max(sc, -2, ne, lane, best, arg);     // rows [r0 + 2, r1) = entries [0, ne)
-            if (arg == 0x7fffffff) { kind = kSearchSkipped; break; }
-            const int v = t.vertex[e0 + arg];
-            if (v < 2 || v >= root.nv || !g.alive[v]) { kind = kSearchSkipped; break; }
-            if (lane == 0) path[len] = node * t.A + arg;
-            ++len;
-            ++moves;
-            const int winner = play_vertex(g, v, mt, true, rm, rb);
-            if (winner >= 0) {                                // decided: the side to move there has won or lost
-                kind = kSearchTerminal;
-                tval = winner == (mt ? 0 : 1) ? 1 : -1;
-                break;
-            }
-            const int child = t.child[e0 + arg];
-            if (child < 0) break;                             // no child yet: the leaf
-            if (child >= t.C) { kind = kSearchSkipped; break; }
-            node = child;
-        }
+        search_walk<WT, false>(g, t, root.nv, env, lane, a.c_puct, 0, false, t.score + (size_t)env * t.A,
+                               a.path + (size_t)env * t.C, rm, rb, d);
     }
-    const int leaf_side = mt;
-    int n_moves = 0;
-    if (kind != kSearchLeaf) {                                // the leaf env gets a copy of the root position
-        __syncthreads();
+    search_store_leaf(g, root, a.leaf, env, env, lane, lds, d, rm, rb, t.moves + (size_t)env * t.A, a.result,
+                      a.rec + HEXGNN_SEARCH_REC * env);
+}
+
+// A round of K = t.K descents per game (include/hexgnn.h: hexgnn_search_round_descend), one after the other by the game's
+// workgroup: descent k reloads the root game into LDS, walks under the in-flight counts of the descents before it, adds itself
+// to them and stores its leaf into game env * K + k of the leaf env.  The tree proper is only read.
+struct RoundArgs {
+    DescendArgs d;               // path [G][K][C], rec [G][K][HEXGNN_SEARCH_REC], result [G * K][5]
+    int round_leaves, vl;
+};
+
+template <int WT>
+__global__ __launch_bounds__(64) void search_round_descend_kernel(EnvDev root, RoundArgs ra) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int env = blockIdx.x, lane = threadIdx.x;
+    const DescendArgs& a = ra.d;
+    const SearchTree& t = a.t;
+    const short* root_rm = root.resp_maker + (size_t)env * root.nv;
+    const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
+    const int root_mt = root.maker_turn[env], root_moves = root.total_moves[env];
+    const bool rests = a.active && !a.active[env];
+    const int applied = t.cnt[2 * env + 1];
+    int simulations = 0;                                      // LEAF and TERMINAL descents of this round so far
+    bool root_waits = false;                                  // an earlier descent took the unexpanded root as its leaf
+    GameT<WT> g;
+    for (int k = 0; k < t.K; ++k) {
+        const int slot = env * t.K + k;
+        // Descent k - 1 added itself to the in-flight counts from some lanes and read the game in LDS from all of them; every
+        // lane of descent k reads those counts and overwrites that LDS: a workgroup barrier in between, not a wave's program order.
+        if (k) __syncthreads();
         load_game(g, root, env, lds);
+        short* rm = a.leaf.resp_maker + (size_t)slot * root.nv;
+        short* rb = a.leaf.resp_breaker + (size_t)slot * root.nv;
         for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
-        mt = root_mt;
-        moves = root_moves;
-        if (kind == kSearchSkipped) len = 0;
-    } else {                                                  // the leaf's legal moves, ascending, for its expansion
-        uint16_t* mv = t.moves + (size_t)env * t.A;
-        for (int k = 0; k < g.K; ++k) {
-            const int x = lane + 64 * k;
-            const bool al = x >= 2 && x < root.nv && g.alive[x];
-            const uint64_t bal = __ballot(al);
-            if (al) mv[n_moves + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)x;
-            n_moves += __popcll(bal);
+        int* path = a.path + (size_t)slot * t.C;
+        Descent d = {kSearchLeaf, 0, 0, root_mt, root_moves};
+        if (rests || k >= ra.round_leaves) {
+            d.kind = kSearchSkipped;
+        } else if (applied + simulations >= a.max_sims) {
+            d.kind = kSearchSkipped;
+            if (lane == 0) atomicOr(a.status, 1);
+        } else {
+            search_walk<WT, true>(g, t, root.nv, env, lane, a.c_puct, ra.vl, root_waits, t.score + (size_t)env * t.A, path, rm, rb, d);
         }
-    }
-    Move m = {-1, moves, 0, mt, moves, 0, 0};
-    count_game(g, &m.n_alive, &m.n_dir_edges);
-    store_game(g, a.leaf, env);
-    if (lane == 0) {
-        put_result(a.leaf, env, a.result, m);
-        int* rec = a.rec + HEXGNN_SEARCH_REC * env;
-        rec[0] = kind; rec[1] = kind == kSearchSkipped ? root_mt : leaf_side; rec[2] = len; rec[3] = tval; rec[4] = n_moves;
+        if (d.kind == kSearchLeaf || d.kind == kSearchTerminal) ++simulations;
+        if (d.kind == kSearchLeaf && d.len == 0) root_waits = true;
+        if (d.kind != kSearchSkipped) {                       // LEAF, TERMINAL and COLLISION alike: I(e) += 1 along the path
+            __syncthreads();                                  // lane 0 wrote the path, every lane reads it
+            for (int s = lane; s < d.len; s += 64) t.inflight[t.edge(env, 0) + path[s]] += 1;     // a path meets an edge once
+        }
+        search_store_leaf(g, root, a.leaf, env, slot, lane, lds, d, rm, rb, t.round_moves + (size_t)slot * t.A, a.result,
+                          a.rec + HEXGNN_SEARCH_REC * slot);
     }
 }
 
@@ -1166,6 +1259,30 @@ int hexgnn_search_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexg
     a.leaf = leaf; a.active = c->active; a.c_puct = c->c_puct; a.max_sims = c->max_sims;
     a.path = c->path; a.rec = c->leaf; a.result = c->result; a.status = c->status;
     dispatch_words(root.W, [&](auto wt) { launch_envs<&search_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a); });
+    return check_launch();
+}
+
+int hexgnn_search_round_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_round_call* r, hexgnn_stream_t stream_) {
+    if (!r || r->struct_bytes != sizeof(hexgnn_search_round_call)) return HEXGNN_EINVAL;
+    const hexgnn_search_call* c = &r->call;
+    bool done;
+    int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    if (!root_ || !leaf_ || root_ == leaf_) return HEXGNN_EINVAL;
+    const EnvDev& root = reinterpret_cast<const Env*>(root_)->d;
+    const EnvDev& leaf = reinterpret_cast<const Env*>(leaf_)->d;
+    if (root.size != c->hex_size || leaf.size != c->hex_size || root.num_envs != c->num_games ||
+        (long long)leaf.num_envs != (long long)c->num_games * r->leaves)
+        return HEXGNN_EINVAL;
+    if (!(c->c_puct >= 0.f && c->c_puct < INFINITY)) return HEXGNN_EINVAL;
+    rc = search_round_checks(r, true, false);
+    if (rc != HEXGNN_OK) return rc;
+    RoundArgs a;
+    a.d.t = search_tree(c->num_games, root.nv, c->max_sims, c->workspace, r->leaves);
+    a.d.leaf = leaf; a.d.active = c->active; a.d.c_puct = c->c_puct; a.d.max_sims = c->max_sims;
+    a.d.path = c->path; a.d.rec = c->leaf; a.d.result = c->result; a.d.status = c->status;
+    a.round_leaves = r->round_leaves; a.vl = r->virtual_loss;
+    dispatch_words(root.W, [&](auto wt) { launch_envs<&search_round_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a); });
     return check_launch();
 }
 

@@ -1,6 +1,6 @@
 // The tree-only kernels of the batched PUCT search (include/hexgnn.h: hexgnn_search_*; the layout: search_tree.h): reset, the
-// expansion + backup of one simulation, and the root read-out.  The descent, which needs the game, is search_descend_kernel of
-// env.hip.  One 64-lane workgroup per game, edge loops strided over the lanes, the tree in global memory; latency kernels like
+// expansion + backup of one simulation (and of a round of several per game), and the root read-out.  The descents, which need
+// the game, are search_descend_kernel and search_round_descend_kernel of env.hip.  One 64-lane workgroup per game, edge loops strided over the lanes, the tree in global memory; latency kernels like
 // hexgnn_arena_ply, nothing here is bound by anything but the launch.  A game's kernels touch that game's slices only, and every
 // index read from memory (path entries, edge counts, offsets) is checked against the layout before it is used.
 // This file needs hipcc's correctly rounded fp32 division (its default; no fast-math flag here).
@@ -9,9 +9,11 @@
 
 namespace hexgnn {
 
-__global__ __launch_bounds__(64) void search_reset_kernel(SearchTree t) {
+// clear_inflight: the workspace reaches behind the in-flight counts of a round (search_tree.h), which are cleared too
+__global__ __launch_bounds__(64) void search_reset_kernel(SearchTree t, int clear_inflight) {
     const int g = blockIdx.x, lane = threadIdx.x;
     for (int n = lane; n < t.C; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
+    if (clear_inflight) for (int e = lane; e < t.C * t.A; e += 64) t.inflight[t.edge(g, 0) + e] = 0;
     if (lane == 0) { t.cnt[2 * g] = 1; t.cnt[2 * g + 1] = 0; }
 }
 
@@ -27,14 +29,15 @@ struct BackupArgs {
     int* status;
 };
 
-__global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
-    const int g = blockIdx.x, lane = threadIdx.x;
+// The expansion + backup of ONE simulation of game g, the one copy behind search_backup_kernel and search_round_backup_kernel:
+// its record rec [HEXGNN_SEARCH_REC], its path [C], its legal moves mv [A] and entry i of offsets / value (the one-leaf call:
+// i = g; a round: i = g * K + k).  Called by all 64 lanes of the game's workgroup from uniform control flow.
+__device__ __forceinline__ void backup_one(const BackupArgs& a, int g, int lane, const int* rec, const int* path,
+                                           const uint16_t* mv, int i) {
     const SearchTree& t = a.t;
-    const int* rec = a.rec + HEXGNN_SEARCH_REC * g;
     const int kind = rec[0], len = rec[2];
     if (kind != kSearchLeaf && kind != kSearchTerminal) return;
     if (len < 0 || len > t.C) return;
-    const int* path = a.path + (size_t)g * t.C;
     bool inside = true;                                       // every step of the path is an edge slot of this game
     for (int d = lane; d < len; d += 64) inside &= path[d] >= 0 && path[d] < t.C * t.A;
     if (!__all(inside)) return;
@@ -43,8 +46,8 @@ __global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
         v = (float)rec[3];
     } else {
         const int ne = rec[4];
-        const int base = a.offsets[g] + a.skip;
-        if (ne < 1 || ne > t.A || a.offsets[g + 1] - base < ne) {     // fewer logits than legal moves: nothing is read
+        const int base = a.offsets[i] + a.skip;
+        if (ne < 1 || ne > t.A || a.offsets[i + 1] - base < ne) {     // fewer logits than legal moves: nothing is read
             if (lane == 0) atomicOr(a.status, 4);
             return;
         }
@@ -52,7 +55,7 @@ __global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
         float m;
         int arg;
         graph_first_max(a.logits, base - 2, base + ne, lane, m, arg);
-        v = a.value ? a.value[g] : fminf(fmaxf(m, -1.f), 1.f);
+        v = a.value ? a.value[i] : fminf(fmaxf(m, -1.f), 1.f);
         bool finite = v - v == 0.f;
         for (int e = lane; e < ne; e += 64) { const float l = a.logits[base + e]; finite &= l - l == 0.f; }
         if (!__all(finite)) {                                 // drops this game's simulation
@@ -74,7 +77,6 @@ __global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
             chunk_inclusive_scan(e < ne ? expf((a.logits[base + e] - m) / a.temperature) : 0.f, S, lane);
         }
         const size_t e0 = t.edge(g, node);
-        const uint16_t* mv = t.moves + (size_t)g * t.A;
         for (int e = lane; e < ne; e += 64) {
             t.P[e0 + e] = __fdiv_rn(expf((a.logits[base + e] - m) / a.temperature), S);
             t.W[e0 + e] = 0.f;
@@ -102,6 +104,33 @@ __global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
         t.ns[t.node(g, pe / t.A)] += 1;
     }
     if (lane == 0) t.cnt[2 * g + 1] += 1;
+}
+
+__global__ __launch_bounds__(64) void search_backup_kernel(BackupArgs a) {
+    const int g = blockIdx.x;
+    backup_one(a, g, threadIdx.x, a.rec + HEXGNN_SEARCH_REC * g, a.path + (size_t)g * a.t.C, a.t.moves + (size_t)g * a.t.A, g);
+}
+
+// The backup of a round of K descents per game (include/hexgnn.h: hexgnn_search_round_backup): backup_one for k = 0 .. K-1 in
+// this order, so node slots are handed out in k order; then the in-flight counts of the K paths are set to 0.
+__global__ __launch_bounds__(64) void search_round_backup_kernel(BackupArgs a) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const SearchTree& t = a.t;
+    for (int k = 0; k < t.K; ++k) {
+        const size_t i = (size_t)g * t.K + k;
+        // simulation k - 1 wrote counts, a child slot and the slot counter from some lanes; all lanes of simulation k read them
+        if (k) __syncthreads();
+        backup_one(a, g, lane, a.rec + HEXGNN_SEARCH_REC * i, a.path + i * t.C, t.round_moves + i * t.A, (int)i);
+    }
+    for (int k = 0; k < t.K; ++k) {
+        const size_t i = (size_t)g * t.K + k;
+        const int kind = a.rec[HEXGNN_SEARCH_REC * i], len = a.rec[HEXGNN_SEARCH_REC * i + 2];
+        if (kind == kSearchSkipped || len < 0 || len > t.C) continue;
+        for (int d = lane; d < len; d += 64) {
+            const int pe = a.path[i * t.C + d];
+            if (pe >= 0 && pe < t.C * t.A) t.inflight[t.edge(g, 0) + pe] = 0;     // set, not decremented: lanes may meet on a word
+        }
+    }
 }
 
 struct RootArgs {
@@ -167,7 +196,7 @@ int hexgnn_search_reset(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
     const int rc = search_common_checks(c, &done);
     if (rc != HEXGNN_OK || done) return rc;
     const SearchTree t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
-    search_reset_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(t);
+    search_reset_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(t, c->workspace_bytes >= t.inflight_end);
     return check_launch();
 }
 
@@ -184,6 +213,29 @@ int hexgnn_search_backup(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
     a.path = c->path; a.rec = c->leaf; a.logits = c->logits; a.offsets = c->offsets; a.value = c->value;
     a.skip = c->skip; a.temperature = c->temperature; a.status = c->status;
     search_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
+    return check_launch();
+}
+
+size_t hexgnn_search_round_workspace_bytes(int num_games, int hex_size, int max_sims, int leaves) {
+    if (hexgnn_search_workspace_bytes(num_games, hex_size, max_sims) == 0 || leaves < 1 || leaves > HEXGNN_SEARCH_MAX_LEAVES) return 0;
+    return search_tree(num_games, hex_size * hex_size + 2, max_sims, nullptr, leaves).round_bytes;
+}
+
+int hexgnn_search_round_backup(const hexgnn_search_round_call* r, hexgnn_stream_t stream_) {
+    if (!r || r->struct_bytes != sizeof(hexgnn_search_round_call)) return HEXGNN_EINVAL;
+    const hexgnn_search_call* c = &r->call;
+    bool done;
+    int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    if (!(c->temperature > 0.f && c->temperature < INFINITY)) return HEXGNN_EINVAL;
+    if (c->skip != 0 && c->skip != 2) return HEXGNN_EINVAL;
+    rc = search_round_checks(r, false, true);
+    if (rc != HEXGNN_OK) return rc;
+    BackupArgs a;
+    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace, r->leaves);
+    a.path = c->path; a.rec = c->leaf; a.logits = c->logits; a.offsets = c->offsets; a.value = c->value;
+    a.skip = c->skip; a.temperature = c->temperature; a.status = c->status;
+    search_round_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
     return check_launch();
 }
 

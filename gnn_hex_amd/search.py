@@ -6,7 +6,10 @@ leaf env) -> the leaf observation (``hexgnn_env_offsets`` / ``hexgnn_env_observe
 ``hexgnn_search_backup`` (expand the leaf with softmax(logit / T) priors, back its value up).  ``hexgnn_search_root`` reads the
 root visit counts out in the layout of the root observation, so ``hexgnn_arena_ply`` picks from them like from any model's output.
 The rule is restated in include/hexgnn.h and on the host in tests/search_oracle.py.  A tree, not the reference's hash-keyed DAG:
-transpositions are not merged; no tree reuse between plies, one leaf per game per round, no swap rule.  Dirichlet noise on the
+transpositions are not merged; no tree reuse between plies, no swap rule.  ``TreeSearch(leaves=K)`` makes a ROUND of K descents
+per game under a virtual loss (``hexgnn_search_round_descend`` / ``_backup``; the rule: include/hexgnn.h,
+tests/search_round_oracle.py): K times fewer rounds, K times larger evaluator batches; ``leaves=1`` is the one-leaf loop, call
+for call.  Dirichlet noise on the
 root priors is ``TreeSearch.add_root_noise`` / ``simulate(root_noise=...)`` (``hexgnn_search_root_noise``); the self-play loop
 that uses it, the sample ring and the policy/value update are gnn_hex_amd/search_selfplay.py.
 
@@ -32,15 +35,18 @@ from .multi_env_manager import Env_manager
 from .observation import ObsTarget, live_norm_of
 
 
-def tree_layout(num_games: int, hex_size: int, max_sims: int):
+def tree_layout(num_games: int, hex_size: int, max_sims: int, leaves=None):
     """The workspace of include/hexgnn.h as ``({name: (byte offset, dtype, shape)}, tree bytes, total bytes)``: the sections in
-    the header's order, each aligned to 256 bytes; ``score`` and ``moves`` are scratch behind the tree."""
+    the header's order, each aligned to 256 bytes; ``score`` and ``moves`` are scratch behind the tree.  ``leaves=K``: the
+    workspace of a round of K leaves per game (``hexgnn_search_round_workspace_bytes``), which keeps every offset and adds
+    ``inflight`` and ``round_moves`` at the end."""
     G, Cn, A = int(num_games), int(max_sims) + 1, int(hex_size) ** 2
     out, off, tree = {}, 0, 0
+    extra = () if leaves is None else (("inflight", np.int32, (G, Cn, A)), ("round_moves", np.uint16, (G, int(leaves), A)))
     for name, dt, shape in (("ns", np.int32, (G, Cn)), ("ne", np.int32, (G, Cn)), ("cnt", np.int32, (G, 2)),
                             ("P", np.float32, (G, Cn, A)), ("W", np.float32, (G, Cn, A)), ("N", np.int32, (G, Cn, A)),
                             ("child", np.int32, (G, Cn, A)), ("vertex", np.uint16, (G, Cn, A)),
-                            ("score", np.float32, (G, A)), ("moves", np.uint16, (G, A))):
+                            ("score", np.float32, (G, A)), ("moves", np.uint16, (G, A))) + extra:
         if name == "score":
             tree = off
         out[name] = (off, dt, shape)
@@ -51,35 +57,50 @@ def tree_layout(num_games: int, hex_size: int, max_sims: int):
 class TreeSearch:
     """``num_games`` search trees of at most ``max_sims`` simulations each over Hex ``hex_size`` positions.  Owns the leaf env,
     the tree workspace, the path / leaf record / status tensors and a capacity-sized leaf observation.  ``c_puct`` and
-    ``temperature`` (of the prior's softmax) are the rule's two constants."""
+    ``temperature`` (of the prior's softmax) are the rule's two constants.  ``leaves=K > 1``: every round makes K descents per
+    game under the integer ``virtual_loss`` and evaluates ``num_leaves = num_games * K`` leaves at once; ``path`` is then
+    [G, K, max_sims + 1], ``leaf`` [G, K, 5], ``result`` [G * K, 5] and leaf (g, k) is game ``g * K + k`` of the leaf env.
+    ``leaves=1`` (the default) issues the one-leaf calls with the one-leaf shapes, whatever ``virtual_loss`` says."""
 
-    def __init__(self, hex_size: int, num_games: int, max_sims: int, c_puct: float = 1.5, temperature: float = 1.0, device=None):
+    def __init__(self, hex_size: int, num_games: int, max_sims: int, c_puct: float = 1.5, temperature: float = 1.0, device=None,
+                 leaves: int = 1, virtual_loss: int = 1):
         if num_games < 1 or not 1 <= int(max_sims) <= _lib.SEARCH_MAX_SIMS:
             raise ValueError("num_games >= 1 and 1 <= max_sims <= %d" % _lib.SEARCH_MAX_SIMS)
         if not (c_puct >= 0 and math.isfinite(c_puct)) or not (temperature > 0 and math.isfinite(temperature)):
             raise ValueError("c_puct is finite and >= 0, temperature finite and > 0")
         self.hex_size, self.num_games, self.max_sims = int(hex_size), int(num_games), int(max_sims)
+        if int(leaves) != leaves or not 1 <= int(leaves) <= _lib.SEARCH_MAX_LEAVES:
+            raise ValueError("leaves is an integer in 1 .. %d" % _lib.SEARCH_MAX_LEAVES)
+        if int(virtual_loss) != virtual_loss or not 1 <= int(virtual_loss) <= _lib.SEARCH_MAX_VIRTUAL_LOSS:
+            raise ValueError("virtual_loss is an integer in 1 .. %d" % _lib.SEARCH_MAX_VIRTUAL_LOSS)
         self.c_puct, self.temperature = float(c_puct), float(temperature)
-        self._leaf_mgr = mgr = Env_manager(num_games, hex_size, device=device)     # the leaf env the search owns
+        K = self.leaves = int(leaves)
+        self.virtual_loss = int(virtual_loss)
+        self.num_leaves = int(num_games) * K                   # the games of the leaf env = the graphs of one evaluator call
+        self._leaf_mgr = mgr = Env_manager(self.num_leaves, hex_size, device=device)     # the leaf env the search owns
         mgr.record_snapshots = False
         dev = self.device = mgr.device
         self.leaf_handle, self.nv = mgr._h, mgr._nv
         L = _lib.lib()
-        self.workspace_bytes = int(L.hexgnn_search_workspace_bytes(num_games, hex_size, max_sims))
+        if K == 1:
+            self.workspace_bytes = int(L.hexgnn_search_workspace_bytes(num_games, hex_size, max_sims))
+        else:
+            self.workspace_bytes = int(L.hexgnn_search_round_workspace_bytes(num_games, hex_size, max_sims, K))
         if self.workspace_bytes == 0:
             raise _lib.HexGnnError("hexgnn_search_workspace_bytes refuses Hex-%d" % hex_size)
         self.workspace = torch.zeros(self.workspace_bytes, dtype=torch.uint8, device=dev)
         G = num_games
-        self.path = torch.zeros((G, max_sims + 1), dtype=torch.int32, device=dev)
-        self.leaf = torch.zeros((G, _lib.SEARCH_REC), dtype=torch.int32, device=dev)
-        self.result = torch.zeros((G, 5), dtype=torch.int32, device=dev)
+        per_game = (G,) if K == 1 else (G, K)
+        self.path = torch.zeros(per_game + (max_sims + 1,), dtype=torch.int32, device=dev)
+        self.leaf = torch.zeros(per_game + (_lib.SEARCH_REC,), dtype=torch.int32, device=dev)
+        self.result = torch.zeros((G * K, 5), dtype=torch.int32, device=dev)
         self._status = torch.zeros(1, dtype=torch.int32, device=dev)
         dev = self.device = self._status.device               # with its index, as every tensor handed in carries it
         # The maker's rewiring can leave a position with MORE edges than the start position (Hex-7: 125 against 122 after one
         # move), and a search puts every game one maker move deep at once: the leaf observation holds twice the start
         # position's edges per game, and leaf_offsets() guards the total.
         self.e_max = 2 * int(mgr._base_sizes[0, 1])
-        self.obs = ObsTarget.capacity(G, self.nv, self.e_max, dev, zeroed=True, tail_clear=True)
+        self.obs = ObsTarget.capacity(G * K, self.nv, self.e_max, dev, zeroed=True, tail_clear=True)
         self.reset()
 
     # -- the four kernel calls --------------------------------------------------------------------------
@@ -90,28 +111,46 @@ class TreeSearch:
                                status=self._status.data_ptr(), path=self.path.data_ptr(), leaf=self.leaf.data_ptr(),
                                result=self.result.data_ptr(), **kw)
 
+    def _round_call(self, round_leaves=None, **kw):
+        return _lib.SearchRoundCall(struct_bytes=C.sizeof(_lib.SearchRoundCall), call=self._call(**kw), leaves=self.leaves,
+                                    round_leaves=self.leaves if round_leaves is None else int(round_leaves),
+                                    virtual_loss=self.virtual_loss)
+
     def reset(self) -> None:
         """Every tree becomes one unexpanded root."""
         _lib.check(_lib.lib().hexgnn_search_reset(C.byref(self._call()), ops._stream()), "hexgnn_search_reset")
 
-    def descend(self, root_handle, active=None) -> None:
-        """One descent per game from the positions of ``root_handle`` (read only); ``active``: int32 [G] on the device, 0 = the
-        game rests.  Fills ``path``, ``leaf``, ``result`` and the leaf env."""
+    def descend(self, root_handle, active=None, round_leaves=None) -> None:
+        """One descent per game (``leaves`` > 1: one round of ``round_leaves`` <= ``leaves`` descents per game, None: all of
+        them) from the positions of ``root_handle`` (read only); ``active``: int32 [G] on the device, 0 = the game rests.
+        Fills ``path``, ``leaf``, ``result`` and the leaf env."""
         if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != self.num_games
                                    or active.device != self.device):
             raise ValueError("active: a contiguous int32 [%d] tensor on %s" % (self.num_games, self.device))
+        if self.leaves > 1:
+            call = self._round_call(round_leaves, active=active.data_ptr() if active is not None else None)
+            _lib.check(_lib.lib().hexgnn_search_round_descend(root_handle, self.leaf_handle, C.byref(call), ops._stream()),
+                       "hexgnn_search_round_descend")
+            return
+        if round_leaves not in (None, 1):
+            raise ValueError("round_leaves belongs to a search with leaves > 1")
         call = self._call(active=active.data_ptr() if active is not None else None)
         _lib.check(_lib.lib().hexgnn_search_descend(root_handle, self.leaf_handle, C.byref(call), ops._stream()),
                    "hexgnn_search_descend")
 
     def backup(self, logits, offsets, skip: int, value=None) -> None:
-        """Expand and back up: ``logits`` float32 placed by the int32 ``offsets [G + 1]`` and ``skip`` (0 / 2), ``value``
-        float32 [G] or None (the maximum logit clamped to [-1, 1])."""
+        """Expand and back up: ``logits`` float32 placed by the int32 ``offsets [num_leaves + 1]`` and ``skip`` (0 / 2),
+        ``value`` float32 [num_leaves] or None (the maximum logit clamped to [-1, 1])."""
         if logits.dtype != torch.float32 or not logits.is_contiguous() or offsets.dtype != torch.int32 \
-                or not offsets.is_contiguous() or offsets.numel() != self.num_games + 1:
-            raise ValueError("logits: contiguous float32; offsets: contiguous int32 [%d]" % (self.num_games + 1))
-        if value is not None and (value.dtype != torch.float32 or not value.is_contiguous() or value.numel() != self.num_games):
-            raise ValueError("value: a contiguous float32 [%d] tensor" % self.num_games)
+                or not offsets.is_contiguous() or offsets.numel() != self.num_leaves + 1:
+            raise ValueError("logits: contiguous float32; offsets: contiguous int32 [%d]" % (self.num_leaves + 1))
+        if value is not None and (value.dtype != torch.float32 or not value.is_contiguous() or value.numel() != self.num_leaves):
+            raise ValueError("value: a contiguous float32 [%d] tensor" % self.num_leaves)
+        if self.leaves > 1:
+            call = self._round_call(None, skip=int(skip), logits=logits.data_ptr(), offsets=offsets.data_ptr(),
+                                    value=value.data_ptr() if value is not None else None)
+            _lib.check(_lib.lib().hexgnn_search_round_backup(C.byref(call), ops._stream()), "hexgnn_search_round_backup")
+            return
         call = self._call(skip=int(skip), logits=logits.data_ptr(), offsets=offsets.data_ptr(),
                           value=value.data_ptr() if value is not None else None)
         _lib.check(_lib.lib().hexgnn_search_backup(C.byref(call), ops._stream()), "hexgnn_search_backup")
@@ -142,7 +181,7 @@ class TreeSearch:
         edges than the observation has columns, the edge offsets become zeros -- every graph then lands inside the storage,
         the simulation evaluates garbage -- and bit 8 of the status word makes ``status()`` raise: nothing is written out of
         bounds and nothing is read back."""
-        obs, k = self.obs, self.num_games
+        obs, k = self.obs, self.num_leaves
         _lib.check(_lib.lib().hexgnn_env_offsets(k, self.result.data_ptr(), obs.node_off.data_ptr(), obs.edge_off.data_ptr(),
                                                  ops._stream()), "hexgnn_env_offsets")
         over = obs.edge_off[k] > obs.E
@@ -177,7 +216,27 @@ class TreeSearch:
         """``sims`` simulations per game: descend -> ``evaluator.evaluate(self)`` -> backup.  ``trace``: a list that receives per
         simulation a dict of host copies: ``path``, ``leaf``, ``logits``, ``offsets``, ``skip``, ``value`` (None: the maximum
         logit rule).  ``root_noise = (eps, alpha)``: ``add_root_noise`` (draws from ``generator``) once, behind the first
-        simulation of the call -- on a fresh tree the one that expands the root."""
+        simulation of the call -- on a fresh tree the one that expands the root.
+        With ``leaves = K > 1`` these are ``ceil(sims / K)`` ROUNDS of ``min(K, sims left)`` descents per game, ``trace``
+        receives one dict per round (plus ``round_leaves``), and the noise comes behind the first round.  A descent that ends
+        on a leaf an earlier descent of its round already waits for is a COLLISION and applies nothing, so the simulations
+        applied (``applied()``) are then FEWER than ``sims``: on a fresh tree the whole first round but its first descent."""
+        if self.leaves > 1:
+            K, left, first = self.leaves, int(sims), True
+            while left > 0:
+                n = min(K, left)
+                self.descend(root_handle, active, round_leaves=n)
+                logits, offsets, skip, value = evaluator.evaluate(self)
+                if trace is not None:
+                    trace.append(dict(path=self.path.cpu().numpy(), leaf=self.leaf.cpu().numpy(), logits=logits.cpu().numpy(),
+                                      offsets=offsets.cpu().numpy(), skip=skip, round_leaves=n,
+                                      value=value.cpu().numpy() if value is not None else None))
+                self.backup(logits, offsets, skip, value)
+                if first and root_noise is not None:
+                    self.add_root_noise(root_noise[0], root_noise[1], active=active, generator=generator)
+                first = False
+                left -= n
+            return
         for i in range(int(sims)):
             self.descend(root_handle, active)
             logits, offsets, skip, value = evaluator.evaluate(self)
@@ -189,8 +248,16 @@ class TreeSearch:
             if i == 0 and root_noise is not None:
                 self.add_root_noise(root_noise[0], root_noise[1], active=active, generator=generator)
 
+    def applied(self) -> torch.Tensor:
+        """The simulations applied to every tree since ``reset``: int32 [G] on the device (LEAF and TERMINAL descents that
+        were not dropped; with ``leaves > 1`` collisions make it smaller than what ``simulate`` was asked for)."""
+        lay, _, _ = tree_layout(self.num_games, self.hex_size, self.max_sims)
+        off = lay["cnt"][0]
+        return self.workspace[off:off + 8 * self.num_games].view(torch.int32).view(self.num_games, 2)[:, 1].clone()
+
     def status(self) -> None:
-        """Raise if a call since the last check met a limit (reads the device word: synchronises)."""
+        """Raise if a call since the last check met a limit (reads the device word: synchronises).  The kinds of a descent in
+        ``leaf[..., 0]``: 0 = LEAF, 1 = TERMINAL, 2 = SKIPPED, 3 = COLLISION (``leaves > 1`` only)."""
         code = int(self._status.item())
         if code:
             self._status.zero_()
@@ -202,7 +269,7 @@ class TreeSearch:
     def tree(self):
         """Host copies of the tree's arrays by name (``tree_layout``): for tests and inspection."""
         raw = self.workspace.cpu().numpy()
-        lay, _, _ = tree_layout(self.num_games, self.hex_size, self.max_sims)
+        lay, _, _ = tree_layout(self.num_games, self.hex_size, self.max_sims, self.leaves if self.leaves > 1 else None)
         return {name: raw[off:off + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape).copy()
                 for name, (off, dt, shape) in lay.items()}
 
@@ -215,10 +282,10 @@ class UniformEvaluator:
 
     def evaluate(self, search: TreeSearch):
         search.leaf_offsets()
-        n = search.num_games * search.nv
+        n = search.num_leaves * search.nv
         if self._zeros is None or self._zeros[0].numel() != n or self._zeros[0].device != search.device:
             self._zeros = (torch.zeros(n, dtype=torch.float32, device=search.device),
-                           torch.zeros(search.num_games, dtype=torch.float32, device=search.device))
+                           torch.zeros(search.num_leaves, dtype=torch.float32, device=search.device))
         return self._zeros[0], search.obs.node_off, 2, self._zeros[1]
 
 
@@ -227,7 +294,7 @@ class QEvaluator:
     (``skip = 2``) and its value is their maximum over the legal rows, clamped to [-1, 1].  These evaluate one side per batch
     (models.py: the head is chosen once per call) and the leaves' sides are mixed, as in the reference (MCTS.py:213-230), so
     the capacity-sized leaf observation goes through the model once per side with the side as the hint, and every row takes
-    the output of its own side (``x[:, 2]``): TWO forwards per simulation.  Models with a norm are refused: a whole-batch norm
+    the output of its own side (``x[:, 2]``): TWO forwards per simulation (per round, over all ``num_leaves`` leaves).  Models with a norm are refused: a whole-batch norm
     ties the graphs of a batch together."""
 
     def __init__(self, model_or_player, value: str = "max"):
@@ -279,18 +346,34 @@ class PolicyValueEvaluator:
         return pi.float().contiguous(), out_ptr.to(torch.int32).contiguous(), 0, value.float().contiguous()
 
 
+def check_round_arguments(sims, leaves, virtual_loss) -> None:
+    """``leaves`` / ``virtual_loss`` of a player that searches ``sims`` simulations per move on a fresh tree: the ranges of
+    ``TreeSearch`` and, with ``leaves > 1``, ``sims > leaves`` -- the first round of a fresh tree only expands the root (one
+    LEAF, the rest collisions), and a root without a visit has no move to offer."""
+    if int(leaves) != leaves or not 1 <= int(leaves) <= _lib.SEARCH_MAX_LEAVES:
+        raise ValueError("leaves is an integer in 1 .. %d" % _lib.SEARCH_MAX_LEAVES)
+    if int(virtual_loss) != virtual_loss or not 1 <= int(virtual_loss) <= _lib.SEARCH_MAX_VIRTUAL_LOSS:
+        raise ValueError("virtual_loss is an integer in 1 .. %d" % _lib.SEARCH_MAX_VIRTUAL_LOSS)
+    if int(leaves) > 1 and int(sims) <= int(leaves):
+        raise ValueError("sims > leaves: the first round of a fresh tree only expands the root")
+
+
 class SearchPlayer:
-    """A player that searches ``sims`` simulations per move with a fresh tree per ply.  ``DeviceArena.play`` (``graph=False``)
+    """A player that searches ``sims`` simulations per move with a fresh tree per ply (``leaves`` / ``virtual_loss``: as
+    ``TreeSearch`` takes them; the simulations asked for, collisions included).  ``DeviceArena.play`` (``graph=False``)
     hands it the root env, the root observation and the mask of undecided games; it answers with the root visit counts in the
     observation's row layout, from which ``hexgnn_arena_ply`` picks: the most visited move by first maximum at temperature 0,
     else a draw from softmax(count / T) -- NOT the count ** (1 / T) of AlphaZero's move selection."""
 
-    def __init__(self, evaluator, sims: int, c_puct: float = 1.5, prior_temperature: float = 1.0):
+    def __init__(self, evaluator, sims: int, c_puct: float = 1.5, prior_temperature: float = 1.0, leaves: int = 1,
+                 virtual_loss: int = 1):
         if not hasattr(evaluator, "evaluate"):
             raise TypeError("SearchPlayer takes an evaluator (PolicyValueEvaluator, QEvaluator, UniformEvaluator)")
         if int(sims) < 1:
             raise ValueError("sims must be positive")
+        check_round_arguments(sims, leaves, virtual_loss)
         self.evaluator, self.sims, self.c_puct, self.prior_temperature = evaluator, int(sims), float(c_puct), float(prior_temperature)
+        self.leaves, self.virtual_loss = int(leaves), int(virtual_loss)
         self._search = None
 
     def search_for(self, env_handle, num_games: int, device) -> TreeSearch:
@@ -298,7 +381,8 @@ class SearchPlayer:
         size = math.isqrt(nv - 2)
         s = self._search
         if s is None or (s.hex_size, s.num_games, s.device) != (size, num_games, torch.device(device)):
-            s = self._search = TreeSearch(size, num_games, self.sims, self.c_puct, self.prior_temperature, device=device)
+            s = self._search = TreeSearch(size, num_games, self.sims, self.c_puct, self.prior_temperature, device=device,
+                                          leaves=self.leaves, virtual_loss=self.virtual_loss)
         return s
 
     def search_scores(self, env_handle, obs, active) -> torch.Tensor:

@@ -28,7 +28,7 @@ from . import _lib, ops
 from .arena import PICK_GREEDY, ArenaResult, DeviceArena
 from .data import Batch
 from .observation import ObsTarget
-from .search import TreeSearch
+from .search import TreeSearch, check_round_arguments
 
 
 class SearchSampleBuffer:
@@ -167,14 +167,17 @@ class SearchSelfPlay:
     searched position recorded into ``buffer``.  ``evaluator``: as ``SearchPlayer`` takes it.  ``root_noise = (eps, alpha)``:
     Dirichlet(alpha) noise mixed into the root priors with weight eps after the simulation that expands the root (None: no
     noise).  ``proportional_plies``: the plies of a match (0 ..) whose move is drawn in proportion to the visit counts; from
-    there on the most visited move is played (None: every ply is drawn)."""
+    there on the most visited move is played (None: every ply is drawn).  ``leaves`` / ``virtual_loss``: as ``TreeSearch`` takes
+    them (``sims`` is then what is asked for, collisions included; ``sims > leaves``)."""
 
     def __init__(self, hex_size: int, num_games: int, evaluator, sims: int, buffer: SearchSampleBuffer, c_puct: float = 1.5,
-                 root_noise=(0.25, 0.2), proportional_plies=None, prior_temperature: float = 1.0, device=None):
+                 root_noise=(0.25, 0.2), proportional_plies=None, prior_temperature: float = 1.0, device=None, leaves: int = 1,
+                 virtual_loss: int = 1):
         if not hasattr(evaluator, "evaluate"):
             raise TypeError("SearchSelfPlay takes an evaluator (PolicyValueEvaluator, QEvaluator, UniformEvaluator)")
         if int(sims) < 2:
             raise ValueError("sims >= 2: the first simulation only expands the root, and a root without a visit is no sample")
+        check_round_arguments(sims, leaves, virtual_loss)
         if buffer.hex_size != int(hex_size) or buffer.capacity < int(num_games) * int(hex_size) ** 2:
             raise ValueError("the buffer holds Hex-%d and needs capacity >= num_games * hex_size ** 2" % buffer.hex_size)
         if root_noise is not None and (not 0.0 <= float(root_noise[0]) <= 1.0 or not float(root_noise[1]) > 0):
@@ -184,7 +187,8 @@ class SearchSelfPlay:
         self.proportional_plies = proportional_plies
         self.arena = DeviceArena(hex_size, num_games, device=device if device is not None else buffer.device, graph=False)
         dev = self.device = self.arena.device
-        self.search = TreeSearch(hex_size, num_games, sims, c_puct, prior_temperature, device=dev)
+        self.search = TreeSearch(hex_size, num_games, sims, c_puct, prior_temperature, device=dev, leaves=leaves,
+                                 virtual_loss=virtual_loss)
         self._zeros = torch.zeros(num_games * self.arena.mgr._nv, dtype=torch.float32, device=dev)
         self._u = torch.zeros(num_games, dtype=torch.float32, device=dev)
 

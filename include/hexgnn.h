@@ -1027,6 +1027,67 @@ int hexgnn_search_descend(const hexgnn_env* root, hexgnn_env* leaf, const hexgnn
 int hexgnn_search_backup(const hexgnn_search_call* call, hexgnn_stream_t stream);
 int hexgnn_search_root(const hexgnn_search_call* call, hexgnn_stream_t stream);
 
+/* ---- Tree search: several leaves per game per round under virtual loss (entry points added to ABI 8, nothing existing changes).
+ *      The mini-batch of the reference's CrazyAra search thread (cpp_hex/CrazyAra/searchthread.cpp:179,232,306-385,
+ *      node.cpp:474-485,609-623): a ROUND is K = `leaves` descents per game, k = 0 .. K-1, made one after the other by the game's
+ *      workgroup under a virtual loss, then ONE evaluator call over all G*K leaves and one backup.  With K = 1 a round is one
+ *      simulation of hexgnn_search_descend / hexgnn_search_backup above and gives their bits for any virtual_loss.
+ *   In-flight counts I(e), int32 per edge slot, live in the workspace behind the sections of hexgnn_search_workspace_bytes; they
+ *     are zero outside a round.  A descent writes nothing of the tree proper (Ns, edges-of-node, the two counters, P, W, N, child,
+ *     vertex): only I, and the scratch sections.  The node's in-flight sum is not stored: every selection sums I over the node's
+ *     edges (integers, so the order does not matter).
+ *   Selection at an expanded node during a round, vl = virtual_loss >= 1 (an integer), fp32, every operation rounded on its own:
+ *       Iv(e) = vl * I(e);  N'(e) = N(e) + Iv(e);  W'(e) = W(e) - (float) Iv(e);  Ns' = Ns + vl * sum_e I(e);
+ *       Q(e) = N'(e) > 0 ? W'(e) / (float) N'(e) : 0;  score(e) = Q(e) + ((c_puct * P(e)) * sqrtf((float) Ns')) / (float)(1 + N'(e));
+ *       the first maximum in edge order wins.  With every I = 0 these are the expressions of the rule above, bit for bit.
+ *   Descent k walks like hexgnn_search_descend and ends as one of four kinds:
+ *       LEAF       the edge has no child and I(e) == 0 before this descent; an unexpanded root is the LEAF of an empty path for
+ *                  the first descent of the round that reaches it.
+ *       COLLISION  the edge has no child, the move did not decide the game, and an earlier descent of this round waits on it
+ *                  (I(e) > 0); every later descent of a round whose first found the root unexpanded is a COLLISION with an
+ *                  empty path.
+ *       TERMINAL   as above; several descents of a round may end on the same terminal, each is a full simulation.
+ *       SKIPPED    the game rests (active[g] == 0); or k >= round_leaves (silently: the last round of a move applies fewer); or
+ *                  simulations applied + the LEAF and TERMINAL descents of this round so far >= max_sims (ORs bit 1 into *status).
+ *     After descent k, I(e) += 1 on every edge of its path -- LEAF, TERMINAL and COLLISION alike: a collision keeps its virtual
+ *     loss to the end of the round, so the next descent is pushed elsewhere.  The tree does not change within a round, so no
+ *     path passes through a node made in that round.
+ *   Leaf (g, k) is game g * K + k of the LEAF env, which holds G*K games; TERMINAL, COLLISION and SKIPPED store a copy of the
+ *     root position there.  path [G][K][max_sims + 1], leaf [G][K][HEXGNN_SEARCH_REC] = (kind, side to move where the descent
+ *     stopped -- the root's for SKIPPED --, path length -- 0 for SKIPPED --, the terminal's value or 0, legal moves of a LEAF),
+ *     result [G*K][5].
+ *   Backup, per game in the order k = 0 .. K-1: a LEAF is expanded (the softmax priors with the summation order above; node slots
+ *     are handed out in k order) and backed up, a TERMINAL backed up, exactly as by hexgnn_search_backup, from the logits placed
+ *     by offsets [G*K + 1] and value [G*K] (or NULL) at index g * K + k; COLLISION and SKIPPED change nothing.  A non-finite
+ *     logit or value, or too few logits, drops that one simulation with status bits 2 / 4; its siblings are applied.  Then every I
+ *     word on the K paths is SET to 0 (not decremented: a repeated backup is harmless).
+ *   Workspace (hexgnn_search_round_workspace_bytes): the sections of hexgnn_search_workspace_bytes at their offsets, then int32
+ *     I [G][C][A], then uint16 leaf moves [G][K][A], each aligned to 256 bytes.  hexgnn_search_root, _root_noise, _record, _descend
+ *     and _backup run unchanged on such a workspace; hexgnn_search_reset clears I as well whenever workspace_bytes reaches the
+ *     end of the I section (which no workspace of the one-leaf size does).
+ * Latency kernels: one 64-lane workgroup per game, one launch each.  Checked on the host before any launch, in this order: a NULL
+ * descriptor or a struct_bytes of another size; then the checks of hexgnn_search_* above on `call` (up to and including
+ * workspace_bytes against the one-leaf size; num_games == 0: HEXGNN_OK without a launch); then descend: a NULL handle, root ==
+ * leaf, a handle of another board size, a root handle whose game count is not G or a leaf handle whose game count is not G *
+ * leaves; c_puct negative or not finite; backup: temperature not > 0 or not finite, skip other than 0 / 2; then both: leaves
+ * outside 1 .. HEXGNN_SEARCH_MAX_LEAVES or virtual_loss outside 1 .. HEXGNN_SEARCH_MAX_VIRTUAL_LOSS; round_leaves outside 0 ..
+ * leaves; path, leaf (and for descend result, for backup logits, offsets) NULL; workspace_bytes below
+ * hexgnn_search_round_workspace_bytes(...).  All HEXGNN_EINVAL. */
+#define HEXGNN_SEARCH_COLLISION 3
+#define HEXGNN_SEARCH_MAX_LEAVES 64
+#define HEXGNN_SEARCH_MAX_VIRTUAL_LOSS 1024
+typedef struct hexgnn_search_round_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_search_round_call), else HEXGNN_EINVAL */
+    hexgnn_search_call call; /* as above, call.struct_bytes = sizeof(hexgnn_search_call); path [G][K][max_sims + 1], leaf
+                                [G][K][HEXGNN_SEARCH_REC], result [G*K][5], offsets [G*K + 1], value [G*K] or NULL */
+    int leaves;              /* K */
+    int round_leaves;        /* descend: descents of this round, 0 .. K */
+    int virtual_loss;        /* descend: vl */
+} hexgnn_search_round_call;
+size_t hexgnn_search_round_workspace_bytes(int num_games, int hex_size, int max_sims, int leaves);   /* 0 for arguments the calls refuse */
+int hexgnn_search_round_descend(const hexgnn_env* root, hexgnn_env* leaf, const hexgnn_search_round_call* call, hexgnn_stream_t stream);
+int hexgnn_search_round_backup(const hexgnn_search_round_call* call, hexgnn_stream_t stream);
+
 /* ---- Search self-play: training samples and the policy/value loss (entry points added to ABI 8, nothing existing changes).
  *      The AlphaZero pipeline of the reference's CrazyAra engine on top of the search above: Dirichlet noise on the root priors
  *      and a move drawn in proportion to the visit counts (cpp_hex/CrazyAra/rl/selfplay.cpp, main/options.cpp:49-53,71-76), one

@@ -2,10 +2,13 @@
 
     python tools/time_search.py                      # GNN-S Hex-7, GNN-L Hex-11, HexAra Hex-11; G = 32 / 128, 16 / 64 sims
     python tools/time_search.py --games 32 --sims 16 --arena-games 0
+    python tools/time_search.py --leaves 1,2,4,8,16          # rounds of K leaves per game under virtual loss, equal total simulations
 
 Part 1: per model, game count G and simulation count S, ``TreeSearch.simulate`` of S simulations from G start positions (a fresh
 tree per call): simulations per second (G * S per call), microseconds per simulation round (one leaf per game), and the plain
 forward of the same model on G start positions as the yardstick (one forward; ``QEvaluator`` runs two per round, one per side).
+``--leaves K[,K...]``: ``TreeSearch(leaves=K, virtual_loss=--virtual-loss)``, the same S simulations ASKED FOR in ceil(S / K)
+rounds; the rate counts the simulations asked for, and ``applied`` is the share of them that were applied (collisions are not).
 Every point is warmed up once and then timed by the synchronised host clock over ``--repeats`` calls: the loop reads sizes back
 and is host-driven, so device events alone would miss what bounds it.
 Part 2: ``DeviceArena(graph=False)`` games per second of a ``SearchPlayer`` (as maker) against the built-in random player.
@@ -52,10 +55,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--arena-games", type=int, default=32, help="games per arena match (0: skip part 2)")
     ap.add_argument("--arena-sims", type=int, default=16)
+    ap.add_argument("--leaves", default="1", help="leaves per game per round, a list (1: the one-leaf search)")
+    ap.add_argument("--virtual-loss", type=int, default=1)
+    ap.add_argument("--models", default="0,1,2", help="which of the three models to time")
     args = ap.parse_args()
     torch.manual_seed(0)
     models = [("GNN-S 10 x 35", 7, q_net(10, 35, 0), QEvaluator), ("GNN-L 15 x 110", 11, q_net(15, 110, 1), QEvaluator),
               ("HexAra 60, 15+2+2", 11, get_current_model().cuda().eval(), PolicyValueEvaluator)]
+    models = [models[int(v)] for v in args.models.split(",")]
+    leaves = [int(v) for v in args.leaves.split(",")]
     print("TreeSearch.simulate from start positions, a fresh tree per call; forward = one plain forward of the model on G positions")
     for name, size, model, make in models:
         ev = make(model)
@@ -66,22 +74,26 @@ def main():
             with torch.no_grad():
                 fwd = host_timed(lambda: model(bt.x, bt.edge_index, bt.batch, bt.ptr), 20)
             for S in (int(v) for v in args.sims.split(",")):
-                search = TreeSearch(size, G, S)
+                for K in leaves:
+                    search = TreeSearch(size, G, S, leaves=K, virtual_loss=args.virtual_loss)
 
-                def run():
-                    search.reset()
-                    search.simulate(mgr._h, ev, S)
+                    def run():
+                        search.reset()
+                        search.simulate(mgr._h, ev, S)
 
-                sec = host_timed(run, args.repeats)
-                search.status()
-                print("%-18s Hex-%-2d G %3d sims %3d  %9.0f sims/s  %8.1f us/round  forward %7.1f us  (round / forward %.1f)"
-                      % (name, size, G, S, G * S / sec, 1e6 * sec / S, 1e6 * fwd, sec / S / fwd), flush=True)
+                    sec = host_timed(run, args.repeats)
+                    applied = float(search.applied().float().mean()) / S
+                    search.status()
+                    rounds = -(-S // K)
+                    print("%-18s Hex-%-2d G %3d sims %3d leaves %2d  %9.0f sims/s  %8.1f us/round  applied %.2f  forward %7.1f us  "
+                          "(round / forward %.1f)" % (name, size, G, S, K, G * S / sec, 1e6 * sec / rounds, applied, 1e6 * fwd,
+                                                      sec / rounds / fwd), flush=True)
     if args.arena_games > 0:
         G, S = args.arena_games, args.arena_sims
         print("DeviceArena(size, %d, graph=False): SearchPlayer(%d sims) as maker against \"random\", both first movers" % (G, S))
-        for name, size, model, make in models:
+        for name, size, model, make, K in [m + (K,) for m in models for K in leaves if K == 1 or K < S]:
             arena = DeviceArena(size, G, graph=False)
-            player = SearchPlayer(make(model), S)
+            player = SearchPlayer(make(model), S, leaves=K, virtual_loss=args.virtual_loss)
             arena.play(player, "random", first="m")          # first use
             torch.cuda.synchronize()
             t0, won, plies = time.perf_counter(), 0, 0
@@ -91,8 +103,8 @@ def main():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             player.status()
-            print("%-18s Hex-%-2d  %6.2f games/s  %6.1f plies/s  won %d of %d" % (name, size, 2 * G / dt, plies / dt, won, 2 * G),
-                  flush=True)
+            print("%-18s Hex-%-2d leaves %2d  %6.2f games/s  %6.1f plies/s  won %d of %d" % (name, size, K, 2 * G / dt, plies / dt, won,
+                                                                                        2 * G), flush=True)
 
 
 if __name__ == "__main__":

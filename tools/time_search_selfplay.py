@@ -2,6 +2,7 @@
 
     python tools/time_search_selfplay.py                    # HexAra 60, 15+2+2 on Hex-7 and Hex-11; G = 32 / 128; 16 simulations
     python tools/time_search_selfplay.py --sizes 7 --games 32 --repeats 1
+    python tools/time_search_selfplay.py --sizes 11 --games 128 --leaves 4     # rounds of 4 leaves per game under virtual loss
 
 Per board size and game count G: one ``SearchSelfPlay.play`` match (samples per second, plies), then ``--updates``
 ``PolicyValueUpdate.step`` calls on batches of G samples drawn from that match (updates per second, ``sample`` included), and one
@@ -31,11 +32,14 @@ def main():
     ap.add_argument("--sims", type=int, default=16)
     ap.add_argument("--repeats", type=int, default=1, help="timed matches per point")
     ap.add_argument("--updates", type=int, default=10)
+    ap.add_argument("--leaves", type=int, default=1, help="leaves per game per round (1: the one-leaf search; else < --sims)")
+    ap.add_argument("--virtual-loss", type=int, default=1)
     args = ap.parse_args()
     torch.manual_seed(0)
     gen = torch.Generator(device="cuda")
     gen.manual_seed(0)
-    print("HexAra 60, 15+2+2; %d simulations per move; forward = one plain forward of the model on G start positions" % args.sims)
+    print("HexAra 60, 15+2+2; %d simulations per move, %d leaves per round; forward = one plain forward of the model on G start "
+          "positions" % (args.sims, args.leaves))
     for size in (int(v) for v in args.sizes.split(",")):
         model = get_current_model().cuda()
         opt = torch.optim.Adam(model.parameters(), lr=1e-4)
@@ -54,7 +58,8 @@ def main():
                 torch.cuda.synchronize()
                 fwd = (time.perf_counter() - t0) / 20
             buf = SearchSampleBuffer(G * size * size, size, "cuda")
-            sp = SearchSelfPlay(size, G, PolicyValueEvaluator(model), args.sims, buf)
+            sp = SearchSelfPlay(size, G, PolicyValueEvaluator(model), args.sims, buf, leaves=args.leaves,
+                                virtual_loss=args.virtual_loss)
             sp.play(generator=gen)                          # first use
             torch.cuda.synchronize()
             t0, samples, plies = time.perf_counter(), 0, 0

@@ -197,6 +197,20 @@ def synthetic_evaluator(game_id, seed=0, uniform=False):
     return lambda game, moves: synthetic(game_id, moves, len(game.get_actions()), seed, uniform)
 
 
+def peaked(game_id, moves, num_actions, seed=0):
+    """The synthetic evaluation with +24 on logit ``path_key(game_id, moves, seed ^ 0x55) % num_actions`` (a multiple of 1 / 128
+    below 32: exact in fp32) and the value divided by 32 (a multiple of 1 / 8192 in [-1 / 32, 1 / 32): every W sum stays exact).
+    A prior this peaked under values this small makes PUCT follow one line and lengthen it by a ply per simulation: the tree
+    is a chain with side branches, as deep as the game is long."""
+    logits, value = synthetic(game_id, moves, num_actions, seed)
+    logits[path_key(game_id, moves, seed ^ 0x55) % num_actions] += np.float32(24.0)
+    return logits, np.float32(value / np.float32(32.0))
+
+
+def peaked_evaluator(game_id, seed=0):
+    return lambda game, moves: peaked(game_id, moves, len(game.get_actions()), seed)
+
+
 # ---- positions ------------------------------------------------------------------------------------------
 def response_tables(game):
     """(resp_maker, resp_breaker) int16 [nv] of a RefGame, -1 = none."""

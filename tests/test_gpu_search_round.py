@@ -34,11 +34,11 @@ class RoundRig:
     """A root env with oracle positions, a TreeSearch(leaves=K) whose workspace, path, leaf record and result are each followed
     by a poisoned guard, and one oracle tree per game."""
 
-    def __init__(self, hexref, size, G, K, max_sims, vl=1, c_puct=1.5, temperature=1.0):
+    def __init__(self, hexref, size, G, K, max_sims, vl=1, c_puct=1.5, temperature=1.0, games=None):
         from gnn_hex_amd.multi_env_manager import Env_manager
         from gnn_hex_amd.search import TreeSearch
         self.size, self.G, self.K, self.nv = size, G, K, size * size + 2
-        self.games = tgs._roots(hexref, size, G)
+        self.games = games if games is not None else tgs._roots(hexref, size, G)
         self.mgr = Env_manager(G, size)
         self.mgr.record_snapshots = False
         tgs._import(self.mgr, self.games)

@@ -4,7 +4,8 @@ teacher-forced, so the oracle tree is checked on the way) and the expectations a
 TreeSearch.tree(): the integers are exact and no share of cases needs leaving out.  Then the end-to-end loop: a self-play match
 whose samples are the replayed positions, a training run on one batch, and a search player after training.
 Boards: Hex-2 with 3 games (the smallest trees), Hex-3 with 1 (a single game), Hex-5 with 70 (ranks cross a 64-lane trip), Hex-9
-with 3 (81 edges: more than 64 lanes), Hex-12 with 3 (nv > 128, three words); 12 simulations each."""
+with 3 (81 edges: more than 64 lanes), Hex-12 with 3 (nv > 128, three words), Hex-14 with 3 (four words, 196 edges) and Hex-16
+with 2 (five words: the run-time word count; 256 edges, exactly four lane trips); 12 simulations each."""
 import numpy as np
 import pytest
 import torch
@@ -17,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 GUARD = 4096
-CASES = [(2, 3), (3, 1), (5, 70), (9, 3), (12, 3)]
+CASES = [(2, 3), (3, 1), (5, 70), (9, 3), (12, 3), (14, 3), (16, 2)]
 SIMS = 12
 POISON = 77
 _RIGS = {}

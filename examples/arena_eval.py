@@ -16,7 +16,8 @@ R playouts per move) beside ``random``: the ladder is rated first, from ``random
 rung below, then the model gets its performance rating against all of them.
 
 ``--search SIMS`` plays the first model behind a PUCT tree search (``gnn_hex_amd.search.SearchPlayer`` over ``QEvaluator``, SIMS
-simulations per move, a fresh tree per ply) against the same model's greedy play, as maker and as breaker.
+simulations per move, a fresh tree per ply; ``--reuse-tree``: the played move's subtree is kept) against the same model's greedy
+play, as maker and as breaker.
 """
 import argparse
 import os
@@ -163,7 +164,8 @@ def search_match(args, handler, model):
     model playing its greedy move, both ways round."""
     from gnn_hex_amd.search import QEvaluator, SearchPlayer
     handler.add_player("search%d" % args.search, model=SearchPlayer(QEvaluator(model), args.search, leaves=args.leaves,
-                                                                   virtual_loss=args.virtual_loss), uses_empty_model=False)
+                                                                   virtual_loss=args.virtual_loss, reuse_tree=args.reuse_tree),
+                       uses_empty_model=False)
     handler.add_player("greedy", model=model, uses_empty_model=False)
     for maker, breaker in (("search%d" % args.search, "greedy"), ("greedy", "search%d" % args.search)):
         t0 = time.perf_counter()
@@ -196,6 +198,8 @@ def main():
     ap.add_argument("--leaves", type=int, default=1,
                     help="--search: leaves per game per round under virtual loss (1: one leaf per round; else < SIMS)")
     ap.add_argument("--virtual-loss", type=int, default=1, help="--search: the virtual loss of a round of several leaves")
+    ap.add_argument("--reuse-tree", action="store_true",
+                    help="--search: keep the played move's subtree between plies (SIMS new simulations per move on top of it)")
     ap.add_argument("--matches", type=int, default=1, help="matches per timed window (a window should last a good part of a second)")
     ap.add_argument("--repeat", type=int, default=1, help="timed windows to play (the first one includes graph capture)")
     args = ap.parse_args()

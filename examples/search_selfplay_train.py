@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--c-puct", type=float, default=1.5)
     ap.add_argument("--leaves", type=int, default=1, help="leaves per game per search round under virtual loss (< --sims)")
     ap.add_argument("--virtual-loss", type=int, default=1)
+    ap.add_argument("--reuse-tree", action="store_true",
+                    help="keep the played move's subtree between plies, in self-play and in the evaluation player")
     ap.add_argument("--eval-every", type=int, default=5)
     ap.add_argument("--eval-games", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
@@ -61,11 +63,11 @@ def main():
     noise = (args.dirichlet_eps, args.dirichlet_alpha) if args.dirichlet_eps > 0 else None
     selfplay = SearchSelfPlay(size, args.games, PolicyValueEvaluator(model), args.sims, buf, c_puct=args.c_puct,
                               root_noise=noise, proportional_plies=args.proportional_plies, leaves=args.leaves,
-                              virtual_loss=args.virtual_loss)
+                              virtual_loss=args.virtual_loss, reuse_tree=args.reuse_tree)
     update = PolicyValueUpdate(model, optimizer, q_ratio=args.q_ratio, val_factor=args.val_factor, pol_factor=args.pol_factor)
     arena = DeviceArena(size, args.eval_games, graph=False)
     player = SearchPlayer(PolicyValueEvaluator(model), args.sims, c_puct=args.c_puct, leaves=args.leaves,
-                          virtual_loss=args.virtual_loss)
+                          virtual_loss=args.virtual_loss, reuse_tree=args.reuse_tree)
     for it in range(1, args.iterations + 1):
         model.eval()
         t0 = time.perf_counter()

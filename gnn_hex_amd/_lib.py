@@ -104,6 +104,12 @@ class SearchRoundCall(C.Structure):
     _fields_ = (_fields(sz, "struct_bytes") + [("call", SearchCall)] + _fields(ci, "leaves round_leaves virtual_loss"))
 
 
+class SearchAdvanceCall(C.Structure):
+    """``hexgnn_search_advance_call`` of include/hexgnn.h, field for field (tests/test_search_reuse_host.py compares the two)."""
+    _fields_ = (_fields(sz, "struct_bytes") + [("call", SearchCall)] + _fields(vp, "moves") + _fields(ci, "max_carry")
+                + _fields(vp, "remap carried"))
+
+
 class RecordCall(C.Structure):
     """``hexgnn_record_call`` of include/hexgnn.h, field for field (tests/test_search_selfplay_host.py compares the two)."""
     _fields_ = (_fields(sz, "struct_bytes") + _fields(ci, "capacity ply pick_mode")
@@ -245,6 +251,7 @@ _SIGS = {
     "hexgnn_search_round_workspace_bytes": (sz, [ci, ci, ci, ci]),
     "hexgnn_search_round_descend": (ci, [vp, vp, C.POINTER(SearchRoundCall), vp]),
     "hexgnn_search_round_backup": (ci, [C.POINTER(SearchRoundCall), vp]),
+    "hexgnn_search_advance": (ci, [C.POINTER(SearchAdvanceCall), vp]),
     "hexgnn_search_root_noise": (ci, [C.POINTER(SearchCall), C.c_float, vp, vp]),
     "hexgnn_search_record": (ci, [vp, C.POINTER(SearchCall), C.POINTER(RecordCall), vp]),
     "hexgnn_samples_finish": (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),

@@ -16,7 +16,9 @@ forward: it gets the root env handle, the root observation and the int32 mask of
 the game records) and returns one score per observation row -- the root visit counts of a PUCT tree search -- from which
 ``hexgnn_arena_ply`` picks as from a model's output: the most visited move by first maximum, or at ``temperature`` T > 0 a
 draw from softmax(count / T) (not count ** (1 / T)).  A search reads leaf sizes back inside a ply, so it needs
-``DeviceArena(graph=False)``; with ``graph=True``, ``play`` raises ``ValueError``.  Every ply searches a fresh tree.
+``DeviceArena(graph=False)``; with ``graph=True``, ``play`` raises ``ValueError``.  Every ply searches a fresh tree unless the
+player keeps the played move's subtree (``SearchPlayer(reuse_tree=True)``): a player with ``begin_match()`` and
+``observe_moves(moves)`` is told when a match begins and, after every ply, which vertex each game played (-1: the game rests).
 """
 from __future__ import annotations
 
@@ -58,6 +60,16 @@ def _is_random(player) -> bool:
 
 def _is_search(player) -> bool:
     return hasattr(player, "search_scores")
+
+
+def _observers(players):
+    """Of ``((player, live_norm), ..)``: the players that follow the match (``begin_match()`` / ``observe_moves(moves)``, e.g.
+    ``SearchPlayer(reuse_tree=True)``), each once even when it plays both sides."""
+    out = []
+    for p, _ in players:
+        if hasattr(p, "begin_match") and hasattr(p, "observe_moves") and not any(p is o for o in out):
+            out.append(p)
+    return out
 
 
 class DeviceArena:
@@ -105,8 +117,11 @@ class DeviceArena:
             raise TypeError("a player is a model from get_pre_defined or the string \"random\", not %r" % (player,))
         return live_norm_of(player)
 
-    def _prepare(self, maker_first: bool, forced: Optional[torch.Tensor]):
-        """All envs at the start position with ``first`` to move, every game undecided, the openings in place."""
+    def _prepare(self, maker_first: bool, forced: Optional[torch.Tensor], players=()):
+        """All envs at the start position with ``first`` to move, every game undecided, the openings in place; the players
+        that follow the match (``_observers``) are told that one begins."""
+        for p in _observers(players):
+            p.begin_match()
         _lib.check(_lib.lib().hexgnn_env_reset(self.mgr._h, None, int(maker_first), None, ops._stream()), "hexgnn_env_reset")
         self.obs.node_off.copy_(self._start_off[0])
         self.obs.edge_off.copy_(self._start_off[1])
@@ -140,6 +155,8 @@ class DeviceArena:
                                           self.live.data_ptr(), ops._stream()), "hexgnn_arena_ply")
             _lib.check(L.hexgnn_env_offsets(k, self.result.data_ptr(), obs.node_off.data_ptr(), obs.edge_off.data_ptr(),
                                             ops._stream()), "hexgnn_env_offsets")
+            for p in _observers(players):       # tree reuse: every such player sees its own move and the opponent's (-1: rests)
+                p.observe_moves(self.log_chunk[t])
             maker = not maker
 
     # -- public ----------------------------------------------------------------------------------------
@@ -176,12 +193,12 @@ class DeviceArena:
             ent = self._graphs.get(key)
             if ent is None:
                 from .graphs import GraphedStep
-                self._prepare(maker_first, None)        # the warm-up and the capture play real plies
+                self._prepare(maker_first, None, players)        # the warm-up and the capture play real plies
                 ent = (GraphedStep(lambda: self._body(players, maker_first, modes, temperature), warmup=1),
                        maker_player, breaker_player)    # keeps the models alive while their ids are a key
                 self._graphs[key] = ent
             step = ent[0]
-        self._prepare(maker_first, forced)
+        self._prepare(maker_first, forced, players)
         plies, live = 0, k
         while live > 0:
             if plies >= self.max_plies:

@@ -1,5 +1,6 @@
 // The tree-only kernels of the batched PUCT search (include/hexgnn.h: hexgnn_search_*; the layout: search_tree.h): reset, the
-// expansion + backup of one simulation (and of a round of several per game), and the root read-out.  The descents, which need
+// expansion + backup of one simulation (and of a round of several per game), the root read-out, and the re-rooting of a tree at
+// the move played (tree reuse between plies).  The descents, which need
 // the game, are search_descend_kernel and search_round_descend_kernel of env.hip.  One 64-lane workgroup per game, edge loops strided over the lanes, the tree in global memory; latency kernels like
 // hexgnn_arena_ply, nothing here is bound by anything but the launch.  A game's kernels touch that game's slices only, and every
 // index read from memory (path entries, edge counts, offsets) is checked against the layout before it is used.
@@ -180,6 +181,102 @@ __global__ __launch_bounds__(64) void search_root_kernel(RootArgs a) {
     }
 }
 
+struct AdvanceArgs {
+    SearchTree t;
+    const int* moves;            // [G] the vertex played, negative: none
+    int max_carry;
+    int* remap;                  // [G][C] scratch: old slot -> new slot, -1 = dropped
+    int* carried;                // [G]
+};
+
+// Re-root game g's tree at the child of the root edge that carries the move played (include/hexgnn.h: hexgnn_search_advance):
+// the subtree of that child c is compacted in place onto slots 0, 1, .. in ascending order of the old slots, so the slot order
+// stays the expansion order.  A game without such a subtree, or with one above max_carry, gets the tree of hexgnn_search_reset.
+// Two facts carry the design.
+//  (a) A child's slot is always greater than its parent's (a node takes the next free slot when it is expanded, and its parent
+//      was expanded before it).  So ONE ascending pass over the slots c .. used-1 decides who is kept: a kept node marks its
+//      children before the pass reaches them, and nothing below c belongs to the subtree.  The new slot m of old slot n is the
+//      number of kept slots below n, and since the old root (slot 0 < c) is never kept, m <= n - 1.  Order is preserved, so the
+//      new tree satisfies child > parent again.
+//  (b) The move is in place.  Nodes move one at a time in ascending order, all 64 lanes on one node: when node i (old slot n_i,
+//      new slot m_i) is written, the sources still unread are n_j > n_i >= m_i + 1 for j > i, so no write lands on a source that
+//      has not been read, and a source that IS overwritten later (m_j <= n_i for j > i) was read an iteration earlier.  One node
+//      in flight per workgroup and one wave per workgroup: moving several nodes at once, or with several waves, would need an
+//      ordering argument of its own.
+// Words written by some lanes and read by others -- the remap marks a node leaves for its children, a moved node against the next
+// one's source -- are separated by a barrier, as the in-flight words of a round are in search_round_backup_kernel.  The child
+// entries are rewritten through remap, which pass 2 only reads.  Every slot read from memory (a child entry, the slot counter,
+// the edge counts) is checked against the layout before it is used as an index.  The in-flight counts are zero outside a round:
+// they are neither read nor written.
+__global__ __launch_bounds__(64) void search_advance_kernel(AdvanceArgs a) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const SearchTree& t = a.t;
+    int* remap = a.remap + (size_t)g * t.C;
+    int used = t.cnt[2 * g];
+    used = used < 1 ? 1 : (used > t.C ? t.C : used);
+    const int mv = a.moves[g];
+    const size_t r0 = t.edge(g, 0);
+    int c = -1, nsc = 0;
+    if (t.ns[t.node(g, 0)] > 0 && mv >= 0) {
+        int ne0 = t.ne[t.node(g, 0)];
+        ne0 = ne0 < 0 ? 0 : (ne0 > t.A ? t.A : ne0);
+        int hit = -1;                                         // the vertices of a node ascend: at most one edge carries mv
+        for (int e = lane; e < ne0; e += 64) if ((int)t.vertex[r0 + e] == mv) hit = e;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(hit, off); hit = o > hit ? o : hit; }
+        if (hit >= 0) c = t.child[r0 + hit];
+        if (c < 1 || c >= used) c = -1;
+        if (c > 0) {
+            nsc = t.ns[t.node(g, c)];
+            if (nsc < 1 || nsc - 1 > a.max_carry) c = -1;
+        }
+    }
+    if (c < 0) {                                              // a fresh tree, word for word search_reset_kernel's
+        for (int n = lane; n < t.C; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
+        if (lane == 0) { t.cnt[2 * g] = 1; t.cnt[2 * g + 1] = 0; a.carried[g] = 0; }
+        return;
+    }
+    // pass 1, fact (a): remap[n] = the new slot of a kept node, -1 for a dropped one
+    for (int n = c + lane; n < used; n += 64) remap[n] = n == c ? 0 : -1;
+    __syncthreads();
+    int kept = 0;
+    for (int n = c; n < used; ++n) {
+        if (remap[n] < 0) continue;                           // uniform: every lane reads the same word
+        int ne = t.ne[t.node(g, n)];
+        ne = ne < 0 ? 0 : (ne > t.A ? t.A : ne);
+        const size_t e0 = t.edge(g, n);
+        for (int e = lane; e < ne; e += 64) {
+            const int ch = t.child[e0 + e];
+            if (ch > n && ch < used) remap[ch] = 0;           // a mark; the pass turns it into the slot when it gets there
+        }
+        if (lane == 0) remap[n] = kept;
+        ++kept;
+        __syncthreads();                                      // the marks and the slot, before any lane reads them
+    }
+    // pass 2, fact (b): node by node in ascending order
+    for (int n = c; n < used; ++n) {
+        const int m = remap[n];
+        if (m < 0) continue;
+        int ne = t.ne[t.node(g, n)];
+        const int ns = t.ns[t.node(g, n)];
+        const int live = ne < 0 ? 0 : (ne > t.A ? t.A : ne);
+        const size_t e0 = t.edge(g, n), d0 = t.edge(g, m);
+        for (int e = lane; e < live; e += 64) {
+            const int ch = t.child[e0 + e];
+            t.P[d0 + e] = t.P[e0 + e];
+            t.W[d0 + e] = t.W[e0 + e];
+            t.N[d0 + e] = t.N[e0 + e];
+            t.vertex[d0 + e] = t.vertex[e0 + e];
+            t.child[d0 + e] = ch < 0 ? ch : (ch > n && ch < used ? remap[ch] : -1);
+        }
+        if (lane == 0) { t.ns[t.node(g, m)] = ns; t.ne[t.node(g, m)] = ne; }
+        __syncthreads();                                      // node n has landed before the next source is read
+    }
+    __syncthreads();
+    for (int n = kept + lane; n < used; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
+    if (lane == 0) { t.cnt[2 * g] = kept; t.cnt[2 * g + 1] = nsc - 1; a.carried[g] = nsc; }
+}
+
 }  // namespace hexgnn
 
 using namespace hexgnn;
@@ -249,6 +346,21 @@ int hexgnn_search_root(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
     a.cells = c->hex_size * c->hex_size; a.fill = c->fill;
     a.gptr = c->gptr; a.scores = c->scores; a.counts = c->counts; a.q = c->q; a.best = c->best;
     search_root_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
+    return check_launch();
+}
+
+int hexgnn_search_advance(const hexgnn_search_advance_call* v, hexgnn_stream_t stream_) {
+    if (!v || v->struct_bytes != sizeof(hexgnn_search_advance_call)) return HEXGNN_EINVAL;
+    const hexgnn_search_call* c = &v->call;
+    bool done;
+    const int rc = search_common_checks(c, &done);
+    if (rc != HEXGNN_OK || done) return rc;
+    if (!v->moves || !v->remap || !v->carried) return HEXGNN_EINVAL;
+    if (v->max_carry < 0 || v->max_carry > c->max_sims) return HEXGNN_EINVAL;
+    AdvanceArgs a;
+    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    a.moves = v->moves; a.max_carry = v->max_carry; a.remap = v->remap; a.carried = v->carried;
+    search_advance_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
     return check_launch();
 }
 

@@ -6,8 +6,9 @@ leaf env) -> the leaf observation (``hexgnn_env_offsets`` / ``hexgnn_env_observe
 ``hexgnn_search_backup`` (expand the leaf with softmax(logit / T) priors, back its value up).  ``hexgnn_search_root`` reads the
 root visit counts out in the layout of the root observation, so ``hexgnn_arena_ply`` picks from them like from any model's output.
 The rule is restated in include/hexgnn.h and on the host in tests/search_oracle.py.  A tree, not the reference's hash-keyed DAG:
-transpositions are not merged; no tree reuse between plies, no swap rule.  ``TreeSearch(leaves=K)`` makes a ROUND of K descents
-per game under a virtual loss (``hexgnn_search_round_descend`` / ``_backup``; the rule: include/hexgnn.h,
+transpositions are not merged; no swap rule.  Tree reuse between plies is ``TreeSearch.advance`` (``hexgnn_search_advance``: the
+played move's subtree becomes the tree) and ``SearchPlayer(reuse_tree=True)``; off by default.  ``TreeSearch(leaves=K)`` makes a
+ROUND of K descents per game under a virtual loss (``hexgnn_search_round_descend`` / ``_backup``; the rule: include/hexgnn.h,
 tests/search_round_oracle.py): K times fewer rounds, K times larger evaluator batches; ``leaves=1`` is the one-leaf loop, call
 for call.  Dirichlet noise on the
 root priors is ``TreeSearch.add_root_noise`` / ``simulate(root_noise=...)`` (``hexgnn_search_root_noise``); the self-play loop
@@ -101,6 +102,7 @@ class TreeSearch:
         # position's edges per game, and leaf_offsets() guards the total.
         self.e_max = 2 * int(mgr._base_sizes[0, 1])
         self.obs = ObsTarget.capacity(G * K, self.nv, self.e_max, dev, zeroed=True, tail_clear=True)
+        self._remap = self._carried = None                     # advance()'s scratch and output, allocated on first use
         self.reset()
 
     # -- the four kernel calls --------------------------------------------------------------------------
@@ -118,7 +120,37 @@ class TreeSearch:
 
     def reset(self) -> None:
         """Every tree becomes one unexpanded root."""
+        self._advanced = False                                 # no tree holds a carried subtree
         _lib.check(_lib.lib().hexgnn_search_reset(C.byref(self._call()), ops._stream()), "hexgnn_search_reset")
+
+    def advance(self, moves, max_carry=None) -> torch.Tensor:
+        """Tree reuse between plies (``hexgnn_search_advance``): every game's tree is re-rooted at the child of the root edge
+        that carries ``moves[g]`` -- int32 [G] on the device, vertex ids (board cell + 2), negative: no move -- and the rest of
+        the tree is dropped; the kept nodes are compacted onto slots 0, 1, .. in their old order.  A game without such a
+        subtree, or whose subtree holds more than ``max_carry`` applied simulations (default ``max_sims``), gets a fresh tree as
+        by ``reset()``.  With ``max_carry = max_sims - s`` the next ``s`` simulations fit.  Call it between searches only.
+        Returns ``carried`` int32 [G] on the device (overwritten by the next call): the visit count Ns of each new root, 0 for
+        a fresh tree.  Nothing is read back."""
+        G = self.num_games
+        if not torch.is_tensor(moves) or moves.dtype != torch.int32 or not moves.is_contiguous() or moves.numel() != G \
+                or moves.device != self.device:
+            raise ValueError("moves: a contiguous int32 [%d] tensor on %s" % (G, self.device))
+        max_carry = self.max_sims if max_carry is None else max_carry
+        if int(max_carry) != max_carry or not 0 <= int(max_carry) <= self.max_sims:
+            raise ValueError("max_carry is an integer in 0 .. max_sims = %d" % self.max_sims)
+        if self._remap is None:
+            self._remap = torch.empty((G, self.max_sims + 1), dtype=torch.int32, device=self.device)
+            self._carried = torch.zeros(G, dtype=torch.int32, device=self.device)
+        call = _lib.SearchAdvanceCall(struct_bytes=C.sizeof(_lib.SearchAdvanceCall), call=self._call(), moves=moves.data_ptr(),
+                                      max_carry=int(max_carry), remap=self._remap.data_ptr(), carried=self._carried.data_ptr())
+        _lib.check(_lib.lib().hexgnn_search_advance(C.byref(call), ops._stream()), "hexgnn_search_advance")
+        self._advanced = True
+        return self._carried
+
+    def root_expanded(self) -> torch.Tensor:
+        """bool [G] on the device: the games whose root is expanded (``ns[:, 0] > 0``); nothing is read back."""
+        G, Cn = self.num_games, self.max_sims + 1
+        return self.workspace[:4 * G * Cn].view(torch.int32).view(G, Cn)[:, 0] > 0
 
     def descend(self, root_handle, active=None, round_leaves=None) -> None:
         """One descent per game (``leaves`` > 1: one round of ``round_leaves`` <= ``leaves`` descents per game, None: all of
@@ -216,11 +248,15 @@ class TreeSearch:
         """``sims`` simulations per game: descend -> ``evaluator.evaluate(self)`` -> backup.  ``trace``: a list that receives per
         simulation a dict of host copies: ``path``, ``leaf``, ``logits``, ``offsets``, ``skip``, ``value`` (None: the maximum
         logit rule).  ``root_noise = (eps, alpha)``: ``add_root_noise`` (draws from ``generator``) once, behind the first
-        simulation of the call -- on a fresh tree the one that expands the root.
+        simulation of the call -- on a fresh tree the one that expands the root.  After ``advance`` a root may be expanded
+        already: such a game's priors are noised before the first simulation instead, the others behind it, once per game.
         With ``leaves = K > 1`` these are ``ceil(sims / K)`` ROUNDS of ``min(K, sims left)`` descents per game, ``trace``
         receives one dict per round (plus ``round_leaves``), and the noise comes behind the first round.  A descent that ends
         on a leaf an earlier descent of its round already waits for is a COLLISION and applies nothing, so the simulations
         applied (``applied()``) are then FEWER than ``sims``: on a fresh tree the whole first round but its first descent."""
+        noise_behind = None
+        if root_noise is not None:
+            noise_behind = self._root_noise_plan(root_noise, active, generator)
         if self.leaves > 1:
             K, left, first = self.leaves, int(sims), True
             while left > 0:
@@ -232,8 +268,8 @@ class TreeSearch:
                                       offsets=offsets.cpu().numpy(), skip=skip, round_leaves=n,
                                       value=value.cpu().numpy() if value is not None else None))
                 self.backup(logits, offsets, skip, value)
-                if first and root_noise is not None:
-                    self.add_root_noise(root_noise[0], root_noise[1], active=active, generator=generator)
+                if first and noise_behind is not None:
+                    noise_behind()
                 first = False
                 left -= n
             return
@@ -245,8 +281,23 @@ class TreeSearch:
                                   offsets=offsets.cpu().numpy(), skip=skip,
                                   value=value.cpu().numpy() if value is not None else None))
             self.backup(logits, offsets, skip, value)
-            if i == 0 and root_noise is not None:
-                self.add_root_noise(root_noise[0], root_noise[1], active=active, generator=generator)
+            if i == 0 and noise_behind is not None:
+                noise_behind()
+
+    def _root_noise_plan(self, root_noise, active, generator):
+        """The root noise of one ``simulate`` call: what to run behind its first simulation (round).  Trees that ``reset()``
+        made: ``add_root_noise`` there, one call under the caller's mask.  Trees that went through ``advance`` may have an
+        expanded root already, whose priors are noised BEFORE the first simulation; the others follow behind it.  Both masks
+        are built on the device from ``ns[:, 0]``, every game is noised once, from one draw."""
+        eps, alpha = root_noise
+        if not self._advanced:
+            return lambda: self.add_root_noise(eps, alpha, active=active, generator=generator)
+        expanded = self.root_expanded()
+        on = expanded if active is None else expanded & (active != 0)
+        off = ~expanded if active is None else ~expanded & (active != 0)
+        behind = off.to(torch.int32)
+        noise = self.add_root_noise(eps, alpha, active=on.to(torch.int32), generator=generator)
+        return lambda: self.apply_root_noise(eps, noise, behind)
 
     def applied(self) -> torch.Tensor:
         """The simulations applied to every tree since ``reset``: int32 [G] on the device (LEAF and TERMINAL descents that
@@ -358,15 +409,37 @@ def check_round_arguments(sims, leaves, virtual_loss) -> None:
         raise ValueError("sims > leaves: the first round of a fresh tree only expands the root")
 
 
+def check_reuse_arguments(sims, reuse_tree, capacity) -> int:
+    """The simulations a player's trees hold: ``sims`` without tree reuse (``capacity`` must then be None), else ``capacity``
+    (default ``4 * sims``, capped at the search's limit), which must reach ``sims``: the new simulations of a ply have to fit
+    behind whatever was carried."""
+    if not reuse_tree:
+        if capacity is not None:
+            raise ValueError("capacity belongs to reuse_tree=True")
+        return int(sims)
+    if capacity is None:
+        capacity = min(4 * int(sims), _lib.SEARCH_MAX_SIMS)
+    if int(capacity) != capacity or not int(sims) <= int(capacity) <= _lib.SEARCH_MAX_SIMS:
+        raise ValueError("capacity is an integer in sims .. %d" % _lib.SEARCH_MAX_SIMS)
+    return int(capacity)
+
+
 class SearchPlayer:
     """A player that searches ``sims`` simulations per move with a fresh tree per ply (``leaves`` / ``virtual_loss``: as
     ``TreeSearch`` takes them; the simulations asked for, collisions included).  ``DeviceArena.play`` (``graph=False``)
     hands it the root env, the root observation and the mask of undecided games; it answers with the root visit counts in the
     observation's row layout, from which ``hexgnn_arena_ply`` picks: the most visited move by first maximum at temperature 0,
-    else a draw from softmax(count / T) -- NOT the count ** (1 / T) of AlphaZero's move selection."""
+    else a draw from softmax(count / T) -- NOT the count ** (1 / T) of AlphaZero's move selection.
+
+    ``reuse_tree=True`` keeps the played move's subtree between plies (the reference's Reuse_Tree): the trees hold ``capacity``
+    simulations (default ``4 * sims``, at least ``sims``), ``search_scores`` runs ``sims`` NEW simulations on whatever tree is
+    there, ``begin_match()`` resets the trees and ``observe_moves(moves)`` -- called by the arena after every ply, the
+    player's own and the opponent's -- re-roots them at the moves played (``TreeSearch.advance`` with ``max_carry = capacity -
+    sims``, so the new simulations always fit; a subtree above that, a move the tree does not hold and a resting game's -1 give
+    a fresh tree).  ``on_carried``: an optional callable that receives each ``advance``'s ``carried`` tensor."""
 
     def __init__(self, evaluator, sims: int, c_puct: float = 1.5, prior_temperature: float = 1.0, leaves: int = 1,
-                 virtual_loss: int = 1):
+                 virtual_loss: int = 1, reuse_tree: bool = False, capacity=None):
         if not hasattr(evaluator, "evaluate"):
             raise TypeError("SearchPlayer takes an evaluator (PolicyValueEvaluator, QEvaluator, UniformEvaluator)")
         if int(sims) < 1:
@@ -374,6 +447,9 @@ class SearchPlayer:
         check_round_arguments(sims, leaves, virtual_loss)
         self.evaluator, self.sims, self.c_puct, self.prior_temperature = evaluator, int(sims), float(c_puct), float(prior_temperature)
         self.leaves, self.virtual_loss = int(leaves), int(virtual_loss)
+        self.reuse_tree = bool(reuse_tree)
+        self.capacity = check_reuse_arguments(sims, reuse_tree, capacity)
+        self.on_carried = None
         self._search = None
 
     def search_for(self, env_handle, num_games: int, device) -> TreeSearch:
@@ -381,15 +457,29 @@ class SearchPlayer:
         size = math.isqrt(nv - 2)
         s = self._search
         if s is None or (s.hex_size, s.num_games, s.device) != (size, num_games, torch.device(device)):
-            s = self._search = TreeSearch(size, num_games, self.sims, self.c_puct, self.prior_temperature, device=device,
+            s = self._search = TreeSearch(size, num_games, self.capacity, self.c_puct, self.prior_temperature, device=device,
                                           leaves=self.leaves, virtual_loss=self.virtual_loss)
         return s
 
     def search_scores(self, env_handle, obs, active) -> torch.Tensor:
         s = self.search_for(env_handle, obs.k, obs.x.device)
-        s.reset()
+        if not self.reuse_tree:
+            s.reset()
         s.simulate(env_handle, self.evaluator, self.sims, active=active)
         return s.root(obs)
+
+    def begin_match(self) -> None:
+        """Before ply 0 of a match: with ``reuse_tree`` every tree becomes one unexpanded root (otherwise nothing)."""
+        if self.reuse_tree and self._search is not None:
+            self._search.reset()
+
+    def observe_moves(self, moves) -> None:
+        """After a ply: ``moves`` int32 [G] on the device, the vertex played in each game (-1: the game rests).  With
+        ``reuse_tree`` the trees are re-rooted at these moves (otherwise nothing)."""
+        if self.reuse_tree and self._search is not None:
+            carried = self._search.advance(moves, max_carry=self.capacity - self.sims)
+            if self.on_carried is not None:
+                self.on_carried(carried)
 
     def status(self) -> None:
         if self._search is not None:

@@ -5,7 +5,8 @@
 ``SearchSampleBuffer``   the sample ring on the device: per sample the board snapshot (what ``hexgnn_states_observe`` takes), the
                          visit distribution over the board cells, the root's mean value, the game result z for the side to move.
 ``SearchSelfPlay``       one lock-step match with the search on both sides on ``DeviceArena``'s pieces.  Per ply: observe -> a
-                         fresh tree and ``sims`` simulations with Dirichlet noise on the root priors -> ``hexgnn_search_record``
+                         fresh tree (``reuse_tree=True``: the played move's subtree) and ``sims`` simulations with Dirichlet
+                         noise on the root priors -> ``hexgnn_search_record``
                          (one sample per undecided game into the ring, one move choice per game) -> ``hexgnn_arena_ply`` with
                          those choices as ``forced`` -> offsets.  ``hexgnn_samples_finish`` labels the match's samples.
 ``PolicyValueUpdate``    forward, ``ops.PolicyValueLossFn`` (``hexgnn_pv_loss``: the reference's ``val_factor * MSE * B +
@@ -14,8 +15,8 @@
 The rules are stated in include/hexgnn.h (the section behind hexgnn_search_*) and restated on the host in
 tests/selfplay_oracle.py.  Scope: ``swap_allowed=False`` networks only; a move is drawn in proportion to the visit counts or is
 the most visited one (no other temperature exponent, no temperature decay); one match at a time fills the ring's tail, and
-batches are drawn between matches; updates are issued eagerly.  Not part of this: a captured update, tree reuse between plies,
-transposition merging.  There is no CPU fallback.
+batches are drawn between matches; updates are issued eagerly.  Tree reuse between plies (``reuse_tree=True``) is off by
+default.  Not part of this: a captured update, transposition merging.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ from . import _lib, ops
 from .arena import PICK_GREEDY, ArenaResult, DeviceArena
 from .data import Batch
 from .observation import ObsTarget
-from .search import TreeSearch, check_round_arguments
+from .search import TreeSearch, check_reuse_arguments, check_round_arguments
 
 
 class SearchSampleBuffer:
@@ -168,11 +169,15 @@ class SearchSelfPlay:
     Dirichlet(alpha) noise mixed into the root priors with weight eps after the simulation that expands the root (None: no
     noise).  ``proportional_plies``: the plies of a match (0 ..) whose move is drawn in proportion to the visit counts; from
     there on the most visited move is played (None: every ply is drawn).  ``leaves`` / ``virtual_loss``: as ``TreeSearch`` takes
-    them (``sims`` is then what is asked for, collisions included; ``sims > leaves``)."""
+    them (``sims`` is then what is asked for, collisions included; ``sims > leaves``).  ``reuse_tree=True`` keeps the played
+    move's subtree between plies (the reference's Reuse_Tree): the trees hold ``capacity`` simulations (default ``4 * sims``),
+    are reset once per match and re-rooted after every ply (``TreeSearch.advance``, ``max_carry = capacity - sims``); every ply
+    adds ``sims`` new simulations, and a sample's visit distribution N / T includes the carried visits, as in the reference.
+    ``on_carried``: an optional callable that receives each ``advance``'s ``carried`` tensor."""
 
     def __init__(self, hex_size: int, num_games: int, evaluator, sims: int, buffer: SearchSampleBuffer, c_puct: float = 1.5,
                  root_noise=(0.25, 0.2), proportional_plies=None, prior_temperature: float = 1.0, device=None, leaves: int = 1,
-                 virtual_loss: int = 1):
+                 virtual_loss: int = 1, reuse_tree: bool = False, capacity=None):
         if not hasattr(evaluator, "evaluate"):
             raise TypeError("SearchSelfPlay takes an evaluator (PolicyValueEvaluator, QEvaluator, UniformEvaluator)")
         if int(sims) < 2:
@@ -187,8 +192,11 @@ class SearchSelfPlay:
         self.proportional_plies = proportional_plies
         self.arena = DeviceArena(hex_size, num_games, device=device if device is not None else buffer.device, graph=False)
         dev = self.device = self.arena.device
-        self.search = TreeSearch(hex_size, num_games, sims, c_puct, prior_temperature, device=dev, leaves=leaves,
+        self.reuse_tree = bool(reuse_tree)
+        self.capacity = check_reuse_arguments(sims, reuse_tree, capacity)
+        self.search = TreeSearch(hex_size, num_games, self.capacity, c_puct, prior_temperature, device=dev, leaves=leaves,
                                  virtual_loss=virtual_loss)
+        self.on_carried = None
         self._zeros = torch.zeros(num_games * self.arena.mgr._nv, dtype=torch.float32, device=dev)
         self._u = torch.zeros(num_games, dtype=torch.float32, device=dev)
 
@@ -204,13 +212,16 @@ class SearchSelfPlay:
         ar._prepare(maker, None)
         buf.discard_pending()
         plies, live = 0, k
+        if self.reuse_tree:
+            s.reset()                                         # once per match; from here the played moves' subtrees are kept
         try:
             while live > 0:
                 if plies >= ar.max_plies:
                     raise RuntimeError("%d games still undecided after %d plies of Hex-%d" % (live, plies, self.hex_size))
                 obs.observe_env(h)
                 active = ((ar.game[:, 0] < 0) & (ar.game[:, 3] == 0)).to(torch.int32)
-                s.reset()
+                if not self.reuse_tree:
+                    s.reset()
                 s.simulate(h, self.evaluator, self.sims, active=active, root_noise=self.root_noise, generator=generator)
                 proportional = self.proportional_plies is None or plies < int(self.proportional_plies)
                 if proportional:
@@ -224,6 +235,10 @@ class SearchSelfPlay:
                                               ops._stream()), "hexgnn_arena_ply")
                 _lib.check(L.hexgnn_env_offsets(k, ar.result.data_ptr(), obs.node_off.data_ptr(), obs.edge_off.data_ptr(),
                                                 ops._stream()), "hexgnn_env_offsets")
+                if self.reuse_tree:                           # a resting game's -1 makes its tree fresh
+                    carried = s.advance(ar.log[plies], max_carry=self.capacity - self.sims)
+                    if self.on_carried is not None:
+                        self.on_carried(carried)
                 maker = not maker
                 plies += 1
                 live = int(ar.live.item())

@@ -1088,6 +1088,43 @@ size_t hexgnn_search_round_workspace_bytes(int num_games, int hex_size, int max_
 int hexgnn_search_round_descend(const hexgnn_env* root, hexgnn_env* leaf, const hexgnn_search_round_call* call, hexgnn_stream_t stream);
 int hexgnn_search_round_backup(const hexgnn_search_round_call* call, hexgnn_stream_t stream);
 
+/* ---- Tree search: keep the played move's subtree between plies (entry point added to ABI 8, nothing existing changes).
+ *      The tree reuse of the reference's CrazyAra engine (cpp_hex/CrazyAra/manager/treemanager.cpp, agents/mctsagent.cpp, the
+ *      Reuse_Tree option of main/options.cpp): after a move the tree is re-rooted at that move's child, once for the own move
+ *      and once for the opponent's reply, so the next search starts from the simulations already spent on its position.
+ *   hexgnn_search_advance, per game g.  Let e be the root edge with vertex(e) == moves[g], looked up among the root's ne edges,
+ *     and c = child(0, e).  The game gets a FRESH tree -- exactly what hexgnn_search_reset makes of it: Ns = edges-of-node = 0 on
+ *     all C slots, the counters (1, 0) -- and carried[g] = 0 when the root is unexpanded, moves[g] < 0, no root edge carries that
+ *     vertex, the edge has no child, or Ns(c) - 1 > max_carry.  None of these is an error; status is not touched.
+ *     Otherwise the subtree of c becomes the tree: the kept nodes are c and everything reachable from it through child; they
+ *     move to the slots 0, 1, 2, .. IN ASCENDING ORDER OF THEIR OLD SLOTS (the slot order stays the expansion order); Ns,
+ *     edges-of-node and the first edges-of-node words of P, W, N and vertex move with each node bit for bit, child as well with
+ *     every entry >= 0 rewritten to the new slot; the slots from `kept` up to the old count of slots in use get Ns =
+ *     edges-of-node = 0; the counters become (kept, Ns(c) - 1) and carried[g] = Ns(c) (>= 1: an expanded leaf has Ns = 1).
+ *     Only live words are specified -- slots below the count in use, edges below edges-of-node --, the rest is as unspecified
+ *     as hexgnn_search_reset leaves it.
+ *     Every kept node other than c was added by a simulation that also incremented Ns(c), so kept <= Ns(c): "node slots in use
+ *     <= simulations applied + 1" holds on, the tree still never fills and the SKIPPED rule (applied >= max_sims) is unchanged.
+ *     With max_carry = max_sims - s the next s simulations are guaranteed to fit.
+ *   Call it between searches only, never between a descent and its backup: path and leaf of an earlier descent are stale
+ *     afterwards and must not be backed up.  The in-flight counts of a round workspace are zero outside a round; they are
+ *     neither read nor written.  remap [G][C], C = max_sims + 1, is int32 scratch the caller owns (contents unspecified before
+ *     and after; no part of the workspace, whose section offsets stay as they are).
+ * A latency kernel like its siblings: one 64-lane workgroup per game, one launch on `stream`, nothing read back, plain vector
+ * loads and stores.  Checked on the host before the launch, in this order: a NULL descriptor or a struct_bytes of another size;
+ * the checks of hexgnn_search_* above on `call` (up to and including workspace_bytes; num_games == 0: HEXGNN_OK without a
+ * launch); moves, remap or carried NULL; max_carry outside 0 .. max_sims.  All HEXGNN_EINVAL. */
+typedef struct hexgnn_search_advance_call {
+    size_t struct_bytes;     /* sizeof(hexgnn_search_advance_call), else HEXGNN_EINVAL */
+    hexgnn_search_call call; /* as above, call.struct_bytes = sizeof(hexgnn_search_call); reads num_games, hex_size, max_sims,
+                                workspace, workspace_bytes, status (checked, never written) */
+    const int* moves;        /* [G] the vertex id (board cell + 2) played in game g, or a negative value */
+    int max_carry;           /* 0 .. max_sims: a subtree of more applied simulations is dropped */
+    int* remap;              /* [G][max_sims + 1] scratch */
+    int* carried;            /* [G] out: Ns of the new root, 0 for a fresh tree */
+} hexgnn_search_advance_call;
+int hexgnn_search_advance(const hexgnn_search_advance_call* call, hexgnn_stream_t stream);
+
 /* ---- Search self-play: training samples and the policy/value loss (entry points added to ABI 8, nothing existing changes).
  *      The AlphaZero pipeline of the reference's CrazyAra engine on top of the search above: Dirichlet noise on the root priors
  *      and a move drawn in proportion to the visit counts (cpp_hex/CrazyAra/rl/selfplay.cpp, main/options.cpp:49-53,71-76), one
@@ -1096,7 +1133,8 @@ int hexgnn_search_round_backup(const hexgnn_search_round_call* call, hexgnn_stre
  *      (rl_loop/dataset_loader.py:74) and the loss val_loss_factor MSE B + policy_loss_factor sum(-target log_policy)
  *      (rl_loop/trainer_agent_pytorch.py:245-275,326-337).  Scope: no swap rule; the move is the most visited one or a draw
  *      proportional to the counts (no other temperature exponent, no temperature decay); one match at a time fills the ring's
- *      tail.  Not part of this: a captured update, tree reuse, transposition merging.
+ *      tail.  Not part of this: a captured update, transposition merging (tree reuse: hexgnn_search_advance above; the samples' T and
+ *      N / T then include the carried visits, as in the reference).
  *   hexgnn_search_root_noise  acts on every game with active[g] != 0 (active NULL: all) whose root is expanded, ne its edges:
  *     S = the sum of noise[g][0 .. ne) in the order of HEXGNN_PICK_SOFTMAX (inclusive scans over chunks of 64 consecutive
  *     entries plus the running carry), then P(e_j) = (1 - eps) P(e_j) + eps (noise[g][j] / S) in fp32, every operation (the

@@ -12,6 +12,11 @@ rounds; the rate counts the simulations asked for, and ``applied`` is the share 
 Every point is warmed up once and then timed by the synchronised host clock over ``--repeats`` calls: the loop reads sizes back
 and is host-driven, so device events alone would miss what bounds it.
 Part 2: ``DeviceArena(graph=False)`` games per second of a ``SearchPlayer`` (as maker) against the built-in random player.
+``--reuse``: tree reuse between plies.  Part 1 adds, behind every point, one ``TreeSearch.advance`` by the most visited move on
+the tree that point built (the workspace restored before every call, each call timed alone by the synchronised host clock, the
+median of ``--advance-repeats`` calls), to stand beside the us per round.  Part 2 plays every player a second time as
+``SearchPlayer(reuse_tree=True)`` at equal new simulations per move and prints the mean of carried / sims over the advances of
+the timed matches (all games of every ply played, both the own and the opponent's moves; a resting game counts as 0).
 """
 import argparse
 import os
@@ -58,6 +63,8 @@ def main():
     ap.add_argument("--leaves", default="1", help="leaves per game per round, a list (1: the one-leaf search)")
     ap.add_argument("--virtual-loss", type=int, default=1)
     ap.add_argument("--models", default="0,1,2", help="which of the three models to time")
+    ap.add_argument("--reuse", action="store_true", help="time TreeSearch.advance and a SearchPlayer(reuse_tree=True)")
+    ap.add_argument("--advance-repeats", type=int, default=9)
     args = ap.parse_args()
     torch.manual_seed(0)
     models = [("GNN-S 10 x 35", 7, q_net(10, 35, 0), QEvaluator), ("GNN-L 15 x 110", 11, q_net(15, 110, 1), QEvaluator),
@@ -88,13 +95,32 @@ def main():
                     print("%-18s Hex-%-2d G %3d sims %3d leaves %2d  %9.0f sims/s  %8.1f us/round  applied %.2f  forward %7.1f us  "
                           "(round / forward %.1f)" % (name, size, G, S, K, G * S / sec, 1e6 * sec / rounds, applied, 1e6 * fwd,
                                                       sec / rounds / fwd), flush=True)
+                    if args.reuse:
+                        best = search.root(mgr.observe(), boards=True)[3]
+                        saved, took = search.workspace.clone(), []
+                        for _ in range(args.advance_repeats + 1):
+                            search.workspace.copy_(saved)
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            carried = search.advance(best)
+                            torch.cuda.synchronize()
+                            took.append(time.perf_counter() - t0)
+                        kept = search.tree()["cnt"][:, 0]
+                        print("%-18s Hex-%-2d G %3d sims %3d leaves %2d  advance %7.1f us (median of %d, first call %.1f us)  carried "
+                              "%.1f, kept %.1f of %d nodes  (advance / round %.2f)" % (
+                                  name, size, G, S, K, 1e6 * sorted(took[1:])[len(took[1:]) // 2], len(took) - 1, 1e6 * took[0],
+                                  float(carried.float().mean()), float(kept.mean()), S + 1,
+                                  sorted(took[1:])[len(took[1:]) // 2] / (sec / rounds)), flush=True)
     if args.arena_games > 0:
         G, S = args.arena_games, args.arena_sims
         print("DeviceArena(size, %d, graph=False): SearchPlayer(%d sims) as maker against \"random\", both first movers" % (G, S))
-        for name, size, model, make, K in [m + (K,) for m in models for K in leaves if K == 1 or K < S]:
+        for name, size, model, make, K, reuse in [m + (K, r) for m in models for K in leaves if K == 1 or K < S
+                                                  for r in ((False, True) if args.reuse else (False,))]:
             arena = DeviceArena(size, G, graph=False)
-            player = SearchPlayer(make(model), S, leaves=K, virtual_loss=args.virtual_loss)
+            player = SearchPlayer(make(model), S, leaves=K, virtual_loss=args.virtual_loss, reuse_tree=reuse)
+            shares = []
             arena.play(player, "random", first="m")          # first use
+            player.on_carried = lambda c: shares.append(c.float().mean())
             torch.cuda.synchronize()
             t0, won, plies = time.perf_counter(), 0, 0
             for first in ("m", "b"):
@@ -103,8 +129,9 @@ def main():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             player.status()
-            print("%-18s Hex-%-2d leaves %2d  %6.2f games/s  %6.1f plies/s  won %d of %d" % (name, size, K, 2 * G / dt, plies / dt, won,
-                                                                                        2 * G), flush=True)
+            tail = "  reuse: carried / sims %.2f over %d advances" % (float(torch.stack(shares).mean()) / S, len(shares)) if reuse else ""
+            print("%-18s Hex-%-2d leaves %2d  %6.2f games/s  %6.1f plies/s  won %d of %d%s" % (name, size, K, 2 * G / dt, plies / dt, won,
+                                                                                          2 * G, tail), flush=True)
 
 
 if __name__ == "__main__":

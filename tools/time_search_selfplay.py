@@ -8,6 +8,8 @@ Per board size and game count G: one ``SearchSelfPlay.play`` match (samples per 
 ``PolicyValueUpdate.step`` calls on batches of G samples drawn from that match (updates per second, ``sample`` included), and one
 plain no-grad forward of the model on G start positions as the yardstick.  Everything is warmed up once and timed by the
 synchronised host clock: the loop reads sizes back and is host-driven, so device events alone would miss what bounds it.
+``--reuse``: ``SearchSelfPlay(reuse_tree=True)`` at equal new simulations per move; the line gains the mean of carried / sims
+over the advances of the timed matches (all games of every ply, a resting game counts as 0).
 """
 import argparse
 import os
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--updates", type=int, default=10)
     ap.add_argument("--leaves", type=int, default=1, help="leaves per game per round (1: the one-leaf search; else < --sims)")
     ap.add_argument("--virtual-loss", type=int, default=1)
+    ap.add_argument("--reuse", action="store_true", help="keep the played move's subtree between plies")
     args = ap.parse_args()
     torch.manual_seed(0)
     gen = torch.Generator(device="cuda")
@@ -59,8 +62,11 @@ def main():
                 fwd = (time.perf_counter() - t0) / 20
             buf = SearchSampleBuffer(G * size * size, size, "cuda")
             sp = SearchSelfPlay(size, G, PolicyValueEvaluator(model), args.sims, buf, leaves=args.leaves,
-                                virtual_loss=args.virtual_loss)
+                                virtual_loss=args.virtual_loss, reuse_tree=args.reuse)
+            shares = []
             sp.play(generator=gen)                          # first use
+            if args.reuse:
+                sp.on_carried = lambda c: shares.append(c.float().mean())
             torch.cuda.synchronize()
             t0, samples, plies = time.perf_counter(), 0, 0
             for r in range(args.repeats):
@@ -76,9 +82,10 @@ def main():
                 upd.step(*buf.sample(G, generator=gen))
             torch.cuda.synchronize()
             step = (time.perf_counter() - t0) / args.updates
+            tail = "  reuse: carried / sims %.2f" % (float(torch.stack(shares).mean()) / args.sims) if shares else ""
             print("Hex-%-2d G %3d  self-play %8.1f samples/s (%d samples, %d plies, %.2f s)  update of %3d graphs %6.1f /s "
-                  "(%.2f ms)  forward %7.1f us" % (size, G, samples / play, samples, plies, play, G, 1 / step, 1e3 * step,
-                                                   1e6 * fwd), flush=True)
+                  "(%.2f ms)  forward %7.1f us%s" % (size, G, samples / play, samples, plies, play, G, 1 / step, 1e3 * step,
+                                                     1e6 * fwd, tail), flush=True)
 
 
 if __name__ == "__main__":

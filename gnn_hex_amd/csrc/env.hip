@@ -708,6 +708,7 @@ struct DescendArgs {
     int* rec;                    // [G][HEXGNN_SEARCH_REC]
     int* result;                 // [G][5]
     int* status;
+    int round_leaves, vl;        // of a round (path [G][K][C], rec [G][K][HEXGNN_SEARCH_REC], result [G * K][5]); one leaf: 1, 0
 };
 
 // Where a descent stands: its kind, the steps walked, a terminal's value, the side to move and the move count there.
@@ -810,28 +811,41 @@ __device__ __forceinline__ void search_store_leaf(GameT<WT>& g, const EnvDev& ro
     }
 }
 
+// A descent up to the position it ends on, the one copy behind both descent kernels: the root game into LDS, the root's
+// response tables into the rows rm / rb of the leaf env's game, the walk.  No walk, and SKIPPED, for a game that rests (leaf =
+// root, no tree change) and once `applied` simulations -- the tree's and, in a round, the earlier descents' -- have reached
+// max_sims (status bit 1).  All arguments but lane are uniform over the workgroup, so every lane takes the barriers of load_game
+// and of the walk's pick.  ROUND, root_waits: search_walk's; the one-leaf form reads no word of a round's sections.
+template <int WT, bool ROUND>
+__device__ __forceinline__ Descent search_descent(GameT<WT>& g, const EnvDev& root, const DescendArgs& a, int env, int lane, char* lds,
+                                                  bool rests, int applied, bool root_waits, short* rm, short* rb, int* path) {
+    const SearchTree& t = a.t;
+    load_game(g, root, env, lds);
+    const short* root_rm = root.resp_maker + (size_t)env * root.nv;
+    const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
+    for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
+    Descent d = {kSearchLeaf, 0, 0, root.maker_turn[env], root.total_moves[env]};
+    if (rests) {
+        d.kind = kSearchSkipped;
+    } else if (applied >= a.max_sims) {
+        d.kind = kSearchSkipped;
+        if (lane == 0) atomicOr(a.status, 1);
+    } else {
+        search_walk<WT, ROUND>(g, t, root.nv, env, lane, a.c_puct, a.vl, root_waits, t.score + (size_t)env * t.A, path, rm, rb, d);
+    }
+    return d;
+}
+
 template <int WT>
 __global__ __launch_bounds__(64) void search_descend_kernel(EnvDev root, DescendArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int env = blockIdx.x, lane = threadIdx.x;
     const SearchTree& t = a.t;
     GameT<WT> g;
-    load_game(g, root, env, lds);
     short* rm = a.leaf.resp_maker + (size_t)env * root.nv;
     short* rb = a.leaf.resp_breaker + (size_t)env * root.nv;
-    const short* root_rm = root.resp_maker + (size_t)env * root.nv;
-    const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
-    for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
-    Descent d = {kSearchLeaf, 0, 0, root.maker_turn[env], root.total_moves[env]};
-    if (a.active && !a.active[env]) {
-        d.kind = kSearchSkipped;                              // a resting game: no tree change, leaf = root
-    } else if (t.cnt[2 * env + 1] >= a.max_sims) {
-        d.kind = kSearchSkipped;
-        if (lane == 0) atomicOr(a.status, 1);
-    } else {
-        search_walk<WT, false>(g, t, root.nv, env, lane, a.c_puct, 0, false, t.score + (size_t)env * t.A,
-                               a.path + (size_t)env * t.C, rm, rb, d);
-    }
+    const Descent d = search_descent<WT, false>(g, root, a, env, lane, lds, a.active && !a.active[env], t.cnt[2 * env + 1], false,
+                                                rm, rb, a.path + (size_t)env * t.C);
     search_store_leaf(g, root, a.leaf, env, env, lane, lds, d, rm, rb, t.moves + (size_t)env * t.A, a.result,
                       a.rec + HEXGNN_SEARCH_REC * env);
 }
@@ -839,20 +853,11 @@ __global__ __launch_bounds__(64) void search_descend_kernel(EnvDev root, Descend
 // A round of K = t.K descents per game (include/hexgnn.h: hexgnn_search_round_descend), one after the other by the game's
 // workgroup: descent k reloads the root game into LDS, walks under the in-flight counts of the descents before it, adds itself
 // to them and stores its leaf into game env * K + k of the leaf env.  The tree proper is only read.
-struct RoundArgs {
-    DescendArgs d;               // path [G][K][C], rec [G][K][HEXGNN_SEARCH_REC], result [G * K][5]
-    int round_leaves, vl;
-};
-
 template <int WT>
-__global__ __launch_bounds__(64) void search_round_descend_kernel(EnvDev root, RoundArgs ra) {
+__global__ __launch_bounds__(64) void search_round_descend_kernel(EnvDev root, DescendArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int env = blockIdx.x, lane = threadIdx.x;
-    const DescendArgs& a = ra.d;
     const SearchTree& t = a.t;
-    const short* root_rm = root.resp_maker + (size_t)env * root.nv;
-    const short* root_rb = root.resp_breaker + (size_t)env * root.nv;
-    const int root_mt = root.maker_turn[env], root_moves = root.total_moves[env];
     const bool rests = a.active && !a.active[env];
     const int applied = t.cnt[2 * env + 1];
     int simulations = 0;                                      // LEAF and TERMINAL descents of this round so far
@@ -863,20 +868,11 @@ __global__ __launch_bounds__(64) void search_round_descend_kernel(EnvDev root, R
         // Descent k - 1 added itself to the in-flight counts from some lanes and read the game in LDS from all of them; every
         // lane of descent k reads those counts and overwrites that LDS: a workgroup barrier in between, not a wave's program order.
         if (k) __syncthreads();
-        load_game(g, root, env, lds);
         short* rm = a.leaf.resp_maker + (size_t)slot * root.nv;
         short* rb = a.leaf.resp_breaker + (size_t)slot * root.nv;
-        for (int i = lane; i < root.nv; i += 64) { rm[i] = root_rm[i]; rb[i] = root_rb[i]; }
         int* path = a.path + (size_t)slot * t.C;
-        Descent d = {kSearchLeaf, 0, 0, root_mt, root_moves};
-        if (rests || k >= ra.round_leaves) {
-            d.kind = kSearchSkipped;
-        } else if (applied + simulations >= a.max_sims) {
-            d.kind = kSearchSkipped;
-            if (lane == 0) atomicOr(a.status, 1);
-        } else {
-            search_walk<WT, true>(g, t, root.nv, env, lane, a.c_puct, ra.vl, root_waits, t.score + (size_t)env * t.A, path, rm, rb, d);
-        }
+        const Descent d = search_descent<WT, true>(g, root, a, env, lane, lds, rests || k >= a.round_leaves, applied + simulations,
+                                                   root_waits, rm, rb, path);
         if (d.kind == kSearchLeaf || d.kind == kSearchTerminal) ++simulations;
         if (d.kind == kSearchLeaf && d.len == 0) root_waits = true;
         if (d.kind != kSearchSkipped) {                       // LEAF, TERMINAL and COLLISION alike: I(e) += 1 along the path
@@ -1243,28 +1239,10 @@ int hexgnn_env_setup(hexgnn_env* h, const hexgnn_setup_call* c, hexgnn_stream_t 
     return check_launch();
 }
 
-int hexgnn_search_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_call* c, hexgnn_stream_t stream_) {
-    bool done;
-    const int rc = search_common_checks(c, &done);
-    if (rc != HEXGNN_OK || done) return rc;
-    if (!root_ || !leaf_ || root_ == leaf_) return HEXGNN_EINVAL;
-    const EnvDev& root = reinterpret_cast<const Env*>(root_)->d;
-    const EnvDev& leaf = reinterpret_cast<const Env*>(leaf_)->d;
-    if (root.size != c->hex_size || leaf.size != c->hex_size || root.num_envs != c->num_games || leaf.num_envs != c->num_games)
-        return HEXGNN_EINVAL;
-    if (!(c->c_puct >= 0.f && c->c_puct < INFINITY)) return HEXGNN_EINVAL;
-    if (!c->path || !c->leaf || !c->result) return HEXGNN_EINVAL;
-    DescendArgs a;
-    a.t = search_tree(c->num_games, root.nv, c->max_sims, c->workspace);
-    a.leaf = leaf; a.active = c->active; a.c_puct = c->c_puct; a.max_sims = c->max_sims;
-    a.path = c->path; a.rec = c->leaf; a.result = c->result; a.status = c->status;
-    dispatch_words(root.W, [&](auto wt) { launch_envs<&search_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a); });
-    return check_launch();
-}
-
-int hexgnn_search_round_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_round_call* r, hexgnn_stream_t stream_) {
-    if (!r || r->struct_bytes != sizeof(hexgnn_search_round_call)) return HEXGNN_EINVAL;
-    const hexgnn_search_call* c = &r->call;
+// Both descents: the checks in the order include/hexgnn.h documents, the kernel arguments, the launch.  r: the descriptor of a
+// round (its size checked), null: the one-leaf call.
+static int search_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_call* c, const hexgnn_search_round_call* r,
+                          hexgnn_stream_t stream_) {
     bool done;
     int rc = search_common_checks(c, &done);
     if (rc != HEXGNN_OK || done) return rc;
@@ -1272,18 +1250,31 @@ int hexgnn_search_round_descend(const hexgnn_env* root_, hexgnn_env* leaf_, cons
     const EnvDev& root = reinterpret_cast<const Env*>(root_)->d;
     const EnvDev& leaf = reinterpret_cast<const Env*>(leaf_)->d;
     if (root.size != c->hex_size || leaf.size != c->hex_size || root.num_envs != c->num_games ||
-        (long long)leaf.num_envs != (long long)c->num_games * r->leaves)
+        (long long)leaf.num_envs != (long long)c->num_games * (r ? r->leaves : 1))
         return HEXGNN_EINVAL;
     if (!(c->c_puct >= 0.f && c->c_puct < INFINITY)) return HEXGNN_EINVAL;
-    rc = search_round_checks(r, true, false);
+    if (r) rc = search_round_checks(r, true, false);
+    else if (!c->path || !c->leaf || !c->result) rc = HEXGNN_EINVAL;
     if (rc != HEXGNN_OK) return rc;
-    RoundArgs a;
-    a.d.t = search_tree(c->num_games, root.nv, c->max_sims, c->workspace, r->leaves);
-    a.d.leaf = leaf; a.d.active = c->active; a.d.c_puct = c->c_puct; a.d.max_sims = c->max_sims;
-    a.d.path = c->path; a.d.rec = c->leaf; a.d.result = c->result; a.d.status = c->status;
-    a.round_leaves = r->round_leaves; a.vl = r->virtual_loss;
-    dispatch_words(root.W, [&](auto wt) { launch_envs<&search_round_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a); });
+    DescendArgs a;
+    a.t = search_tree(c, r ? r->leaves : 0);
+    a.leaf = leaf; a.active = c->active; a.c_puct = c->c_puct; a.max_sims = c->max_sims;
+    a.path = c->path; a.rec = c->leaf; a.result = c->result; a.status = c->status;
+    a.round_leaves = r ? r->round_leaves : 1; a.vl = r ? r->virtual_loss : 0;
+    dispatch_words(root.W, [&](auto wt) {
+        if (r) launch_envs<&search_round_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a);
+        else launch_envs<&search_descend_kernel<decltype(wt)::value>>(root, (hipStream_t)stream_, a);
+    });
     return check_launch();
+}
+
+int hexgnn_search_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_call* c, hexgnn_stream_t stream_) {
+    return search_descend(root_, leaf_, c, nullptr, stream_);
+}
+
+int hexgnn_search_round_descend(const hexgnn_env* root_, hexgnn_env* leaf_, const hexgnn_search_round_call* r, hexgnn_stream_t stream_) {
+    if (!r || r->struct_bytes != sizeof(hexgnn_search_round_call)) return HEXGNN_EINVAL;
+    return search_descend(root_, leaf_, &r->call, r, stream_);
 }
 
 int hexgnn_frames_add(int64_t* frames, int64_t delta, hexgnn_stream_t stream_) {

@@ -1,21 +1,28 @@
 // The tree-only kernels of the batched PUCT search (include/hexgnn.h: hexgnn_search_*; the layout: search_tree.h): reset, the
 // expansion + backup of one simulation (and of a round of several per game), the root read-out, and the re-rooting of a tree at
-// the move played (tree reuse between plies).  The descents, which need
-// the game, are search_descend_kernel and search_round_descend_kernel of env.hip.  One 64-lane workgroup per game, edge loops strided over the lanes, the tree in global memory; latency kernels like
-// hexgnn_arena_ply, nothing here is bound by anything but the launch.  A game's kernels touch that game's slices only, and every
-// index read from memory (path entries, edge counts, offsets) is checked against the layout before it is used.
+// the move played (tree reuse between plies).  The descents, which need the game, are search_descend_kernel and
+// search_round_descend_kernel of env.hip.  One 64-lane workgroup per game, edge loops strided over the lanes, the tree in global
+// memory; latency kernels like hexgnn_arena_ply, nothing here is bound by anything but the launch.  A game's kernels touch that
+// game's slices only, and every index read from memory (path entries, edge counts, offsets) is checked against the layout
+// before it is used.
 // This file needs hipcc's correctly rounded fp32 division (its default; no fast-math flag here).
 #include "hexgnn_reduce.h"
 #include "search_tree.h"
 
 namespace hexgnn {
 
+// Game g's tree becomes one unexpanded root, the one copy behind search_reset_kernel and the fresh trees of
+// search_advance_kernel.  The in-flight counts of a round are no part of it: they belong to the reset kernel alone.
+__device__ __forceinline__ void search_fresh_tree(const SearchTree& t, int g, int lane) {
+    for (int n = lane; n < t.C; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
+    if (lane == 0) { t.cnt[2 * g] = 1; t.cnt[2 * g + 1] = 0; }
+}
+
 // clear_inflight: the workspace reaches behind the in-flight counts of a round (search_tree.h), which are cleared too
 __global__ __launch_bounds__(64) void search_reset_kernel(SearchTree t, int clear_inflight) {
     const int g = blockIdx.x, lane = threadIdx.x;
-    for (int n = lane; n < t.C; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
+    search_fresh_tree(t, g, lane);
     if (clear_inflight) for (int e = lane; e < t.C * t.A; e += 64) t.inflight[t.edge(g, 0) + e] = 0;
-    if (lane == 0) { t.cnt[2 * g] = 1; t.cnt[2 * g + 1] = 0; }
 }
 
 struct BackupArgs {
@@ -231,9 +238,9 @@ __global__ __launch_bounds__(64) void search_advance_kernel(AdvanceArgs a) {
             if (nsc < 1 || nsc - 1 > a.max_carry) c = -1;
         }
     }
-    if (c < 0) {                                              // a fresh tree, word for word search_reset_kernel's
-        for (int n = lane; n < t.C; n += 64) { t.ns[t.node(g, n)] = 0; t.ne[t.node(g, n)] = 0; }
-        if (lane == 0) { t.cnt[2 * g] = 1; t.cnt[2 * g + 1] = 0; a.carried[g] = 0; }
+    if (c < 0) {                                              // a fresh tree, as search_reset_kernel makes it
+        search_fresh_tree(t, g, lane);
+        if (lane == 0) a.carried[g] = 0;
         return;
     }
     // pass 1, fact (a): remap[n] = the new slot of a kept node, -1 for a dropped one
@@ -292,26 +299,32 @@ int hexgnn_search_reset(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
     bool done;
     const int rc = search_common_checks(c, &done);
     if (rc != HEXGNN_OK || done) return rc;
-    const SearchTree t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    const SearchTree t = search_tree(c);
     search_reset_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(t, c->workspace_bytes >= t.inflight_end);
     return check_launch();
 }
 
-int hexgnn_search_backup(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
+// Both backups: the checks in the order include/hexgnn.h documents, the kernel arguments, the launch.  r: the descriptor of a
+// round (its size checked), null: the one-leaf call.
+static int search_backup(const hexgnn_search_call* c, const hexgnn_search_round_call* r, hexgnn_stream_t stream_) {
     bool done;
-    const int rc = search_common_checks(c, &done);
+    int rc = search_common_checks(c, &done);
     if (rc != HEXGNN_OK || done) return rc;
     if (!(c->temperature > 0.f && c->temperature < INFINITY)) return HEXGNN_EINVAL;
     if (c->skip != 0 && c->skip != 2) return HEXGNN_EINVAL;
-    if (!c->path || !c->leaf) return HEXGNN_EINVAL;
-    if (!c->logits || !c->offsets) return HEXGNN_EINVAL;
+    if (r) rc = search_round_checks(r, false, true);
+    else if (!c->path || !c->leaf || !c->logits || !c->offsets) rc = HEXGNN_EINVAL;
+    if (rc != HEXGNN_OK) return rc;
     BackupArgs a;
-    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    a.t = search_tree(c, r ? r->leaves : 0);
     a.path = c->path; a.rec = c->leaf; a.logits = c->logits; a.offsets = c->offsets; a.value = c->value;
     a.skip = c->skip; a.temperature = c->temperature; a.status = c->status;
-    search_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
+    if (r) search_round_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
+    else search_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
     return check_launch();
 }
+
+int hexgnn_search_backup(const hexgnn_search_call* c, hexgnn_stream_t stream_) { return search_backup(c, nullptr, stream_); }
 
 size_t hexgnn_search_round_workspace_bytes(int num_games, int hex_size, int max_sims, int leaves) {
     if (hexgnn_search_workspace_bytes(num_games, hex_size, max_sims) == 0 || leaves < 1 || leaves > HEXGNN_SEARCH_MAX_LEAVES) return 0;
@@ -320,20 +333,7 @@ size_t hexgnn_search_round_workspace_bytes(int num_games, int hex_size, int max_
 
 int hexgnn_search_round_backup(const hexgnn_search_round_call* r, hexgnn_stream_t stream_) {
     if (!r || r->struct_bytes != sizeof(hexgnn_search_round_call)) return HEXGNN_EINVAL;
-    const hexgnn_search_call* c = &r->call;
-    bool done;
-    int rc = search_common_checks(c, &done);
-    if (rc != HEXGNN_OK || done) return rc;
-    if (!(c->temperature > 0.f && c->temperature < INFINITY)) return HEXGNN_EINVAL;
-    if (c->skip != 0 && c->skip != 2) return HEXGNN_EINVAL;
-    rc = search_round_checks(r, false, true);
-    if (rc != HEXGNN_OK) return rc;
-    BackupArgs a;
-    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace, r->leaves);
-    a.path = c->path; a.rec = c->leaf; a.logits = c->logits; a.offsets = c->offsets; a.value = c->value;
-    a.skip = c->skip; a.temperature = c->temperature; a.status = c->status;
-    search_round_backup_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
-    return check_launch();
+    return search_backup(&r->call, r, stream_);
 }
 
 int hexgnn_search_root(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
@@ -342,7 +342,7 @@ int hexgnn_search_root(const hexgnn_search_call* c, hexgnn_stream_t stream_) {
     if (rc != HEXGNN_OK || done) return rc;
     if (!c->gptr || !c->scores) return HEXGNN_EINVAL;
     RootArgs a;
-    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    a.t = search_tree(c);
     a.cells = c->hex_size * c->hex_size; a.fill = c->fill;
     a.gptr = c->gptr; a.scores = c->scores; a.counts = c->counts; a.q = c->q; a.best = c->best;
     search_root_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
@@ -358,7 +358,7 @@ int hexgnn_search_advance(const hexgnn_search_advance_call* v, hexgnn_stream_t s
     if (!v->moves || !v->remap || !v->carried) return HEXGNN_EINVAL;
     if (v->max_carry < 0 || v->max_carry > c->max_sims) return HEXGNN_EINVAL;
     AdvanceArgs a;
-    a.t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    a.t = search_tree(c);
     a.moves = v->moves; a.max_carry = v->max_carry; a.remap = v->remap; a.carried = v->carried;
     search_advance_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(a);
     return check_launch();

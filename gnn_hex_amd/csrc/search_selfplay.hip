@@ -226,7 +226,7 @@ int hexgnn_search_root_noise(const hexgnn_search_call* c, float eps, const float
     const int rc = search_common_checks(c, &done);
     if (rc != HEXGNN_OK || done) return rc;
     if (!(eps >= 0.f && eps <= 1.f) || !noise) return HEXGNN_EINVAL;
-    const SearchTree t = search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace);
+    const SearchTree t = search_tree(c);
     search_root_noise_kernel<<<c->num_games, 64, 0, (hipStream_t)stream_>>>(t, c->active, eps, noise, c->status);
     return check_launch();
 }
@@ -247,7 +247,7 @@ int hexgnn_search_record(const hexgnn_env* root_, const hexgnn_search_call* c, c
         !r->sizes || !r->meta || (r->pick_mode == 1 && !r->u))
         return HEXGNN_EINVAL;
     RecordArgs a;
-    a.t = search_tree(c->num_games, root.nv, c->max_sims, c->workspace);
+    a.t = search_tree(c);
     a.active = c->active; a.capacity = r->capacity; a.ply = r->ply; a.pick_mode = r->pick_mode;
     a.head = reinterpret_cast<const long long*>(r->head); a.u = r->u; a.pick = r->pick;
     a.policy = r->policy; a.root_q = r->root_q; a.z = r->z; a.adj = r->adj; a.alive = r->alive; a.side = r->side;

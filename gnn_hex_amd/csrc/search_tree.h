@@ -68,6 +68,11 @@ inline SearchTree search_tree(int G, int nv, int max_sims, void* workspace, int 
     return t;
 }
 
+// The tree of a call: its workspace in the layout of its sizes; leaves > 0: with the sections of a round of that many leaves.
+inline SearchTree search_tree(const hexgnn_search_call* c, int leaves = 0) {
+    return search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, c->workspace, leaves);
+}
+
 // The checks every hexgnn_search_* entry point makes first, in the order include/hexgnn.h documents.  *done: nothing to launch.
 inline int search_common_checks(const hexgnn_search_call* c, bool* done) {
     *done = false;
@@ -76,7 +81,7 @@ inline int search_common_checks(const hexgnn_search_call* c, bool* done) {
     if (c->hex_size > 25 || c->hex_size * c->hex_size + 2 > kSearchMaxNv) return HEXGNN_EUNSUPPORTED;
     if (c->num_games == 0) { *done = true; return HEXGNN_OK; }
     if (!c->workspace || !c->status) return HEXGNN_EINVAL;
-    if (c->workspace_bytes < search_tree(c->num_games, c->hex_size * c->hex_size + 2, c->max_sims, nullptr).bytes) return HEXGNN_EINVAL;
+    if (c->workspace_bytes < search_tree(c).bytes) return HEXGNN_EINVAL;
     return HEXGNN_OK;
 }
 
@@ -89,8 +94,7 @@ inline int search_round_checks(const hexgnn_search_round_call* c, bool need_resu
     if (!s.path || !s.leaf) return HEXGNN_EINVAL;
     if (need_result && !s.result) return HEXGNN_EINVAL;
     if (need_logits && (!s.logits || !s.offsets)) return HEXGNN_EINVAL;
-    if (s.workspace_bytes < search_tree(s.num_games, s.hex_size * s.hex_size + 2, s.max_sims, nullptr, c->leaves).round_bytes)
-        return HEXGNN_EINVAL;
+    if (s.workspace_bytes < search_tree(&s, c->leaves).round_bytes) return HEXGNN_EINVAL;
     return HEXGNN_OK;
 }
 

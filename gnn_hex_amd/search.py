@@ -9,12 +9,14 @@ The rule is restated in include/hexgnn.h and on the host in tests/search_oracle.
 transpositions are not merged; no swap rule.  Tree reuse between plies is ``TreeSearch.advance`` (``hexgnn_search_advance``: the
 played move's subtree becomes the tree) and ``SearchPlayer(reuse_tree=True)``; off by default.  ``TreeSearch(leaves=K)`` makes a
 ROUND of K descents per game under a virtual loss (``hexgnn_search_round_descend`` / ``_backup``; the rule: include/hexgnn.h,
-tests/search_round_oracle.py): K times fewer rounds, K times larger evaluator batches; ``leaves=1`` is the one-leaf loop, call
-for call.  Dirichlet noise on the
-root priors is ``TreeSearch.add_root_noise`` / ``simulate(root_noise=...)`` (``hexgnn_search_root_noise``); the self-play loop
-that uses it, the sample ring and the policy/value update are gnn_hex_amd/search_selfplay.py.
+tests/search_round_oracle.py): K times fewer rounds, K times larger evaluator batches; ``leaves=1`` is a round of one descent
+and issues the one-leaf calls.  Dirichlet noise on the root priors is ``TreeSearch.add_root_noise`` /
+``simulate(root_noise=...)`` (``hexgnn_search_root_noise``); the self-play loop that uses it, the sample ring and the
+policy/value update are gnn_hex_amd/search_selfplay.py.
 
 ``TreeSearch``             the trees, the leaf env and the simulation loop.
+``SearchPlies``            what a searching player does per match and per ply (reset, simulate, tree reuse): the one copy behind
+                           ``SearchPlayer`` and ``search_selfplay.SearchSelfPlay``.
 ``PolicyValueEvaluator``   leaves through a ``SAGE_torch_script`` policy / value network (the HexAra network).
 ``QEvaluator``             leaves through a ``get_pre_defined`` Q-network or a ``MonteCarloPlayer``: scores as logits, the maximum
                            score as value; one forward per side, so two per simulation.
@@ -55,6 +57,20 @@ def tree_layout(num_games: int, hex_size: int, max_sims: int, leaves=None):
     return out, tree, off
 
 
+def tensor_arg(name: str, t, dtype, shape=None, device=None, optional: bool = False, message=None):
+    """The one check of a tensor argument of a kernel call, and its address: a contiguous ``dtype`` tensor of ``shape`` (an int:
+    that many elements, a tuple: exactly that shape, None: any) on ``device`` (None: anywhere), else ``ValueError`` (with
+    ``message`` in place of the description made from the arguments).  ``optional``: None is allowed and returned."""
+    if t is None and optional:
+        return None
+    dims = () if shape is None else shape if isinstance(shape, tuple) else (shape,)
+    if not (torch.is_tensor(t) and t.dtype == dtype and t.is_contiguous() and (device is None or t.device == device)
+            and (shape is None or (tuple(t.shape) == shape if isinstance(shape, tuple) else t.numel() == shape))):
+        raise ValueError(message or "%s: a contiguous %s%s tensor%s" % (
+            name, str(dtype)[6:], " [%s]" % ", ".join(map(str, dims)) if dims else "", "" if device is None else " on %s" % (device,)))
+    return t.data_ptr()
+
+
 class TreeSearch:
     """``num_games`` search trees of at most ``max_sims`` simulations each over Hex ``hex_size`` positions.  Owns the leaf env,
     the tree workspace, the path / leaf record / status tensors and a capacity-sized leaf observation.  ``c_puct`` and
@@ -70,10 +86,7 @@ class TreeSearch:
         if not (c_puct >= 0 and math.isfinite(c_puct)) or not (temperature > 0 and math.isfinite(temperature)):
             raise ValueError("c_puct is finite and >= 0, temperature finite and > 0")
         self.hex_size, self.num_games, self.max_sims = int(hex_size), int(num_games), int(max_sims)
-        if int(leaves) != leaves or not 1 <= int(leaves) <= _lib.SEARCH_MAX_LEAVES:
-            raise ValueError("leaves is an integer in 1 .. %d" % _lib.SEARCH_MAX_LEAVES)
-        if int(virtual_loss) != virtual_loss or not 1 <= int(virtual_loss) <= _lib.SEARCH_MAX_VIRTUAL_LOSS:
-            raise ValueError("virtual_loss is an integer in 1 .. %d" % _lib.SEARCH_MAX_VIRTUAL_LOSS)
+        check_round_arguments(None, leaves, virtual_loss)
         self.c_puct, self.temperature = float(c_puct), float(temperature)
         K = self.leaves = int(leaves)
         self.virtual_loss = int(virtual_loss)
@@ -105,7 +118,7 @@ class TreeSearch:
         self._remap = self._carried = None                     # advance()'s scratch and output, allocated on first use
         self.reset()
 
-    # -- the four kernel calls --------------------------------------------------------------------------
+    # -- the kernel calls ------------------------------------------------------------------------------------
     def _call(self, **kw):
         return _lib.SearchCall(struct_bytes=C.sizeof(_lib.SearchCall), num_games=self.num_games, hex_size=self.hex_size,
                                max_sims=self.max_sims, c_puct=self.c_puct, temperature=self.temperature,
@@ -117,6 +130,24 @@ class TreeSearch:
         return _lib.SearchRoundCall(struct_bytes=C.sizeof(_lib.SearchRoundCall), call=self._call(**kw), leaves=self.leaves,
                                     round_leaves=self.leaves if round_leaves is None else int(round_leaves),
                                     virtual_loss=self.virtual_loss)
+
+    def _issue(self, what: str, *handles, round_leaves=None, **kw) -> None:
+        """``hexgnn_search_<what>(*handles, _call(**kw))`` or, with ``leaves > 1``, ``hexgnn_search_round_<what>`` with
+        ``_round_call(round_leaves, **kw)``: the one place that tells the two forms of descend and backup apart."""
+        if self.leaves > 1:
+            name, call = "hexgnn_search_round_" + what, self._round_call(round_leaves, **kw)
+        else:
+            name, call = "hexgnn_search_" + what, self._call(**kw)
+        _lib.check(getattr(_lib.lib(), name)(*handles, C.byref(call), ops._stream()), name)
+
+    def _section(self, name: str) -> torch.Tensor:
+        """A device view of the section ``name`` of the workspace (``tree_layout``: ``ns``, ``cnt``, ...); nothing is copied."""
+        off, dt, shape = self._layout()[name]
+        view = self.workspace[off:off + int(np.prod(shape)) * np.dtype(dt).itemsize]
+        return view.view(getattr(torch, np.dtype(dt).name)).view(shape)
+
+    def _layout(self):
+        return tree_layout(self.num_games, self.hex_size, self.max_sims, self.leaves if self.leaves > 1 else None)[0]
 
     def reset(self) -> None:
         """Every tree becomes one unexpanded root."""
@@ -132,16 +163,14 @@ class TreeSearch:
         Returns ``carried`` int32 [G] on the device (overwritten by the next call): the visit count Ns of each new root, 0 for
         a fresh tree.  Nothing is read back."""
         G = self.num_games
-        if not torch.is_tensor(moves) or moves.dtype != torch.int32 or not moves.is_contiguous() or moves.numel() != G \
-                or moves.device != self.device:
-            raise ValueError("moves: a contiguous int32 [%d] tensor on %s" % (G, self.device))
+        moves = tensor_arg("moves", moves, torch.int32, G, self.device)
         max_carry = self.max_sims if max_carry is None else max_carry
         if int(max_carry) != max_carry or not 0 <= int(max_carry) <= self.max_sims:
             raise ValueError("max_carry is an integer in 0 .. max_sims = %d" % self.max_sims)
         if self._remap is None:
             self._remap = torch.empty((G, self.max_sims + 1), dtype=torch.int32, device=self.device)
             self._carried = torch.zeros(G, dtype=torch.int32, device=self.device)
-        call = _lib.SearchAdvanceCall(struct_bytes=C.sizeof(_lib.SearchAdvanceCall), call=self._call(), moves=moves.data_ptr(),
+        call = _lib.SearchAdvanceCall(struct_bytes=C.sizeof(_lib.SearchAdvanceCall), call=self._call(), moves=moves,
                                       max_carry=int(max_carry), remap=self._remap.data_ptr(), carried=self._carried.data_ptr())
         _lib.check(_lib.lib().hexgnn_search_advance(C.byref(call), ops._stream()), "hexgnn_search_advance")
         self._advanced = True
@@ -149,43 +178,25 @@ class TreeSearch:
 
     def root_expanded(self) -> torch.Tensor:
         """bool [G] on the device: the games whose root is expanded (``ns[:, 0] > 0``); nothing is read back."""
-        G, Cn = self.num_games, self.max_sims + 1
-        return self.workspace[:4 * G * Cn].view(torch.int32).view(G, Cn)[:, 0] > 0
+        return self._section("ns")[:, 0] > 0
 
     def descend(self, root_handle, active=None, round_leaves=None) -> None:
         """One descent per game (``leaves`` > 1: one round of ``round_leaves`` <= ``leaves`` descents per game, None: all of
         them) from the positions of ``root_handle`` (read only); ``active``: int32 [G] on the device, 0 = the game rests.
         Fills ``path``, ``leaf``, ``result`` and the leaf env."""
-        if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != self.num_games
-                                   or active.device != self.device):
-            raise ValueError("active: a contiguous int32 [%d] tensor on %s" % (self.num_games, self.device))
-        if self.leaves > 1:
-            call = self._round_call(round_leaves, active=active.data_ptr() if active is not None else None)
-            _lib.check(_lib.lib().hexgnn_search_round_descend(root_handle, self.leaf_handle, C.byref(call), ops._stream()),
-                       "hexgnn_search_round_descend")
-            return
-        if round_leaves not in (None, 1):
+        active = tensor_arg("active", active, torch.int32, self.num_games, self.device, optional=True)
+        if self.leaves == 1 and round_leaves not in (None, 1):
             raise ValueError("round_leaves belongs to a search with leaves > 1")
-        call = self._call(active=active.data_ptr() if active is not None else None)
-        _lib.check(_lib.lib().hexgnn_search_descend(root_handle, self.leaf_handle, C.byref(call), ops._stream()),
-                   "hexgnn_search_descend")
+        self._issue("descend", root_handle, self.leaf_handle, round_leaves=round_leaves, active=active)
 
     def backup(self, logits, offsets, skip: int, value=None) -> None:
         """Expand and back up: ``logits`` float32 placed by the int32 ``offsets [num_leaves + 1]`` and ``skip`` (0 / 2),
         ``value`` float32 [num_leaves] or None (the maximum logit clamped to [-1, 1])."""
-        if logits.dtype != torch.float32 or not logits.is_contiguous() or offsets.dtype != torch.int32 \
-                or not offsets.is_contiguous() or offsets.numel() != self.num_leaves + 1:
-            raise ValueError("logits: contiguous float32; offsets: contiguous int32 [%d]" % (self.num_leaves + 1))
-        if value is not None and (value.dtype != torch.float32 or not value.is_contiguous() or value.numel() != self.num_leaves):
-            raise ValueError("value: a contiguous float32 [%d] tensor" % self.num_leaves)
-        if self.leaves > 1:
-            call = self._round_call(None, skip=int(skip), logits=logits.data_ptr(), offsets=offsets.data_ptr(),
-                                    value=value.data_ptr() if value is not None else None)
-            _lib.check(_lib.lib().hexgnn_search_round_backup(C.byref(call), ops._stream()), "hexgnn_search_round_backup")
-            return
-        call = self._call(skip=int(skip), logits=logits.data_ptr(), offsets=offsets.data_ptr(),
-                          value=value.data_ptr() if value is not None else None)
-        _lib.check(_lib.lib().hexgnn_search_backup(C.byref(call), ops._stream()), "hexgnn_search_backup")
+        both = "logits: contiguous float32; offsets: contiguous int32 [%d]" % (self.num_leaves + 1)
+        logits = tensor_arg("logits", logits, torch.float32, message=both)
+        offsets = tensor_arg("offsets", offsets, torch.int32, self.num_leaves + 1, message=both)
+        value = tensor_arg("value", value, torch.float32, self.num_leaves, optional=True)
+        self._issue("backup", skip=int(skip), logits=logits, offsets=offsets, value=value)
 
     def root(self, obs, boards: bool = False, fill: float = 0.0):
         """The read-out in the layout of the root observation ``obs`` (an ``ObsTarget`` or ``ObsList`` of the root env):
@@ -235,54 +246,38 @@ class TreeSearch:
     def apply_root_noise(self, eps: float, noise, active=None) -> None:
         """``hexgnn_search_root_noise`` with the caller's ``noise`` (contiguous float32 [G, hex_size ** 2] on the device)."""
         G, A = self.num_games, self.hex_size ** 2
-        if noise.dtype != torch.float32 or not noise.is_contiguous() or tuple(noise.shape) != (G, A) or noise.device != self.device:
-            raise ValueError("noise: a contiguous float32 [%d, %d] tensor on %s" % (G, A, self.device))
-        if active is not None and (active.dtype != torch.int32 or not active.is_contiguous() or active.numel() != G
-                                   or active.device != self.device):
-            raise ValueError("active: a contiguous int32 [%d] tensor on %s" % (G, self.device))
-        call = self._call(active=active.data_ptr() if active is not None else None)
-        _lib.check(_lib.lib().hexgnn_search_root_noise(C.byref(call), float(eps), noise.data_ptr(), ops._stream()),
+        noise = tensor_arg("noise", noise, torch.float32, (G, A), self.device)
+        call = self._call(active=tensor_arg("active", active, torch.int32, G, self.device, optional=True))
+        _lib.check(_lib.lib().hexgnn_search_root_noise(C.byref(call), float(eps), noise, ops._stream()),
                    "hexgnn_search_root_noise")
 
     def simulate(self, root_handle, evaluator, sims: int, active=None, trace=None, root_noise=None, generator=None) -> None:
-        """``sims`` simulations per game: descend -> ``evaluator.evaluate(self)`` -> backup.  ``trace``: a list that receives per
-        simulation a dict of host copies: ``path``, ``leaf``, ``logits``, ``offsets``, ``skip``, ``value`` (None: the maximum
-        logit rule).  ``root_noise = (eps, alpha)``: ``add_root_noise`` (draws from ``generator``) once, behind the first
-        simulation of the call -- on a fresh tree the one that expands the root.  After ``advance`` a root may be expanded
-        already: such a game's priors are noised before the first simulation instead, the others behind it, once per game.
-        With ``leaves = K > 1`` these are ``ceil(sims / K)`` ROUNDS of ``min(K, sims left)`` descents per game, ``trace``
-        receives one dict per round (plus ``round_leaves``), and the noise comes behind the first round.  A descent that ends
-        on a leaf an earlier descent of its round already waits for is a COLLISION and applies nothing, so the simulations
-        applied (``applied()``) are then FEWER than ``sims``: on a fresh tree the whole first round but its first descent."""
-        noise_behind = None
-        if root_noise is not None:
-            noise_behind = self._root_noise_plan(root_noise, active, generator)
-        if self.leaves > 1:
-            K, left, first = self.leaves, int(sims), True
-            while left > 0:
-                n = min(K, left)
-                self.descend(root_handle, active, round_leaves=n)
-                logits, offsets, skip, value = evaluator.evaluate(self)
-                if trace is not None:
-                    trace.append(dict(path=self.path.cpu().numpy(), leaf=self.leaf.cpu().numpy(), logits=logits.cpu().numpy(),
-                                      offsets=offsets.cpu().numpy(), skip=skip, round_leaves=n,
-                                      value=value.cpu().numpy() if value is not None else None))
-                self.backup(logits, offsets, skip, value)
-                if first and noise_behind is not None:
-                    noise_behind()
-                first = False
-                left -= n
-            return
-        for i in range(int(sims)):
-            self.descend(root_handle, active)
+        """``sims`` simulations per game in ``ceil(sims / K)`` ROUNDS of ``min(K, sims left)`` descents per game, K = ``leaves``:
+        descend -> ``evaluator.evaluate(self)`` -> backup; with ``leaves = 1`` a round is one simulation.  ``trace``: a list that
+        receives per round a dict of host copies: ``path``, ``leaf``, ``logits``, ``offsets``, ``skip``, ``value`` (None: the
+        maximum logit rule) and, with ``leaves > 1`` only, ``round_leaves``.  ``root_noise = (eps, alpha)``: ``add_root_noise``
+        (draws from ``generator``) once, behind the first round of the call -- on a fresh tree the one that expands the root.
+        After ``advance`` a root may be expanded already: such a game's priors are noised before the first round instead, the
+        others behind it, once per game.  With ``leaves > 1`` a descent that ends on a leaf an earlier descent of its round
+        already waits for is a COLLISION and applies nothing, so the simulations applied (``applied()``) are then FEWER than
+        ``sims``: on a fresh tree the whole first round but its first descent."""
+        noise_behind = self._root_noise_plan(root_noise, active, generator) if root_noise is not None else None
+        K, left = self.leaves, int(sims)
+        while left > 0:
+            n = min(K, left)
+            self.descend(root_handle, active, round_leaves=n)
             logits, offsets, skip, value = evaluator.evaluate(self)
             if trace is not None:
-                trace.append(dict(path=self.path.cpu().numpy(), leaf=self.leaf.cpu().numpy(), logits=logits.cpu().numpy(),
-                                  offsets=offsets.cpu().numpy(), skip=skip,
-                                  value=value.cpu().numpy() if value is not None else None))
+                rec = dict(path=self.path.cpu().numpy(), leaf=self.leaf.cpu().numpy(), logits=logits.cpu().numpy(),
+                           offsets=offsets.cpu().numpy(), skip=skip, value=value.cpu().numpy() if value is not None else None)
+                if K > 1:
+                    rec["round_leaves"] = n
+                trace.append(rec)
             self.backup(logits, offsets, skip, value)
-            if i == 0 and noise_behind is not None:
+            if noise_behind is not None:                       # once, behind the first round
                 noise_behind()
+                noise_behind = None
+            left -= n
 
     def _root_noise_plan(self, root_noise, active, generator):
         """The root noise of one ``simulate`` call: what to run behind its first simulation (round).  Trees that ``reset()``
@@ -302,9 +297,7 @@ class TreeSearch:
     def applied(self) -> torch.Tensor:
         """The simulations applied to every tree since ``reset``: int32 [G] on the device (LEAF and TERMINAL descents that
         were not dropped; with ``leaves > 1`` collisions make it smaller than what ``simulate`` was asked for)."""
-        lay, _, _ = tree_layout(self.num_games, self.hex_size, self.max_sims)
-        off = lay["cnt"][0]
-        return self.workspace[off:off + 8 * self.num_games].view(torch.int32).view(self.num_games, 2)[:, 1].clone()
+        return self._section("cnt")[:, 1].clone()
 
     def status(self) -> None:
         """Raise if a call since the last check met a limit (reads the device word: synchronises).  The kinds of a descent in
@@ -320,9 +313,8 @@ class TreeSearch:
     def tree(self):
         """Host copies of the tree's arrays by name (``tree_layout``): for tests and inspection."""
         raw = self.workspace.cpu().numpy()
-        lay, _, _ = tree_layout(self.num_games, self.hex_size, self.max_sims, self.leaves if self.leaves > 1 else None)
         return {name: raw[off:off + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape).copy()
-                for name, (off, dt, shape) in lay.items()}
+                for name, (off, dt, shape) in self._layout().items()}
 
 
 class UniformEvaluator:
@@ -399,13 +391,13 @@ class PolicyValueEvaluator:
 
 def check_round_arguments(sims, leaves, virtual_loss) -> None:
     """``leaves`` / ``virtual_loss`` of a player that searches ``sims`` simulations per move on a fresh tree: the ranges of
-    ``TreeSearch`` and, with ``leaves > 1``, ``sims > leaves`` -- the first round of a fresh tree only expands the root (one
-    LEAF, the rest collisions), and a root without a visit has no move to offer."""
+    ``TreeSearch`` (which checks them here, with ``sims=None``) and, with ``leaves > 1``, ``sims > leaves`` -- the first round
+    of a fresh tree only expands the root (one LEAF, the rest collisions), and a root without a visit has no move to offer."""
     if int(leaves) != leaves or not 1 <= int(leaves) <= _lib.SEARCH_MAX_LEAVES:
         raise ValueError("leaves is an integer in 1 .. %d" % _lib.SEARCH_MAX_LEAVES)
     if int(virtual_loss) != virtual_loss or not 1 <= int(virtual_loss) <= _lib.SEARCH_MAX_VIRTUAL_LOSS:
         raise ValueError("virtual_loss is an integer in 1 .. %d" % _lib.SEARCH_MAX_VIRTUAL_LOSS)
-    if int(leaves) > 1 and int(sims) <= int(leaves):
+    if sims is not None and int(leaves) > 1 and int(sims) <= int(leaves):
         raise ValueError("sims > leaves: the first round of a fresh tree only expands the root")
 
 
@@ -424,19 +416,46 @@ def check_reuse_arguments(sims, reuse_tree, capacity) -> int:
     return int(capacity)
 
 
-class SearchPlayer:
+class SearchPlies:
+    """What a player that searches ``sims`` simulations per move does per match and per ply, the one copy behind ``SearchPlayer``
+    and ``search_selfplay.SearchSelfPlay``.  Without ``reuse_tree``: a fresh tree before every search.  With it the trees hold
+    ``capacity`` simulations (``check_reuse_arguments``), are reset once per match and re-rooted at the moves played after every
+    ply (``TreeSearch.advance`` with ``max_carry = capacity - sims``, so the next search always fits), and ``on_carried`` -- an
+    optional callable, set at any time -- receives each ``advance``'s ``carried`` tensor."""
+
+    def __init__(self, sims: int, reuse_tree: bool = False, capacity=None):
+        self.sims, self.reuse_tree = int(sims), bool(reuse_tree)
+        self.capacity = check_reuse_arguments(sims, reuse_tree, capacity)
+        self.on_carried = None
+
+    def _match_begins(self, search) -> None:
+        if self.reuse_tree and search is not None:             # (None: a player before its first search)
+            search.reset()
+
+    def _search_ply(self, search: TreeSearch, root_handle, evaluator, active, root_noise=None, generator=None) -> None:
+        if not self.reuse_tree:
+            search.reset()
+        search.simulate(root_handle, evaluator, self.sims, active=active, root_noise=root_noise, generator=generator)
+
+    def _ply_played(self, search, moves) -> None:
+        if self.reuse_tree and search is not None:
+            carried = search.advance(moves, max_carry=self.capacity - self.sims)
+            if self.on_carried is not None:
+                self.on_carried(carried)
+
+
+class SearchPlayer(SearchPlies):
     """A player that searches ``sims`` simulations per move with a fresh tree per ply (``leaves`` / ``virtual_loss``: as
     ``TreeSearch`` takes them; the simulations asked for, collisions included).  ``DeviceArena.play`` (``graph=False``)
     hands it the root env, the root observation and the mask of undecided games; it answers with the root visit counts in the
     observation's row layout, from which ``hexgnn_arena_ply`` picks: the most visited move by first maximum at temperature 0,
     else a draw from softmax(count / T) -- NOT the count ** (1 / T) of AlphaZero's move selection.
 
-    ``reuse_tree=True`` keeps the played move's subtree between plies (the reference's Reuse_Tree): the trees hold ``capacity``
-    simulations (default ``4 * sims``, at least ``sims``), ``search_scores`` runs ``sims`` NEW simulations on whatever tree is
-    there, ``begin_match()`` resets the trees and ``observe_moves(moves)`` -- called by the arena after every ply, the
-    player's own and the opponent's -- re-roots them at the moves played (``TreeSearch.advance`` with ``max_carry = capacity -
-    sims``, so the new simulations always fit; a subtree above that, a move the tree does not hold and a resting game's -1 give
-    a fresh tree).  ``on_carried``: an optional callable that receives each ``advance``'s ``carried`` tensor."""
+    ``reuse_tree=True`` keeps the played move's subtree between plies (the reference's Reuse_Tree; ``SearchPlies``): the trees
+    hold ``capacity`` simulations (default ``4 * sims``, at least ``sims``), ``search_scores`` runs ``sims`` NEW simulations on
+    whatever tree is there, ``begin_match()`` resets the trees and ``observe_moves(moves)`` -- called by the arena after every
+    ply, the player's own and the opponent's -- re-roots them at the moves played; a subtree above ``capacity - sims``, a move
+    the tree does not hold and a resting game's -1 give a fresh tree."""
 
     def __init__(self, evaluator, sims: int, c_puct: float = 1.5, prior_temperature: float = 1.0, leaves: int = 1,
                  virtual_loss: int = 1, reuse_tree: bool = False, capacity=None):
@@ -445,11 +464,9 @@ class SearchPlayer:
         if int(sims) < 1:
             raise ValueError("sims must be positive")
         check_round_arguments(sims, leaves, virtual_loss)
-        self.evaluator, self.sims, self.c_puct, self.prior_temperature = evaluator, int(sims), float(c_puct), float(prior_temperature)
+        SearchPlies.__init__(self, sims, reuse_tree, capacity)
+        self.evaluator, self.c_puct, self.prior_temperature = evaluator, float(c_puct), float(prior_temperature)
         self.leaves, self.virtual_loss = int(leaves), int(virtual_loss)
-        self.reuse_tree = bool(reuse_tree)
-        self.capacity = check_reuse_arguments(sims, reuse_tree, capacity)
-        self.on_carried = None
         self._search = None
 
     def search_for(self, env_handle, num_games: int, device) -> TreeSearch:
@@ -463,23 +480,17 @@ class SearchPlayer:
 
     def search_scores(self, env_handle, obs, active) -> torch.Tensor:
         s = self.search_for(env_handle, obs.k, obs.x.device)
-        if not self.reuse_tree:
-            s.reset()
-        s.simulate(env_handle, self.evaluator, self.sims, active=active)
+        self._search_ply(s, env_handle, self.evaluator, active)
         return s.root(obs)
 
     def begin_match(self) -> None:
         """Before ply 0 of a match: with ``reuse_tree`` every tree becomes one unexpanded root (otherwise nothing)."""
-        if self.reuse_tree and self._search is not None:
-            self._search.reset()
+        self._match_begins(self._search)
 
     def observe_moves(self, moves) -> None:
         """After a ply: ``moves`` int32 [G] on the device, the vertex played in each game (-1: the game rests).  With
         ``reuse_tree`` the trees are re-rooted at these moves (otherwise nothing)."""
-        if self.reuse_tree and self._search is not None:
-            carried = self._search.advance(moves, max_carry=self.capacity - self.sims)
-            if self.on_carried is not None:
-                self.on_carried(carried)
+        self._ply_played(self._search, moves)
 
     def status(self) -> None:
         if self._search is not None:

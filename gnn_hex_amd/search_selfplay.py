@@ -6,9 +6,9 @@
                          visit distribution over the board cells, the root's mean value, the game result z for the side to move.
 ``SearchSelfPlay``       one lock-step match with the search on both sides on ``DeviceArena``'s pieces.  Per ply: observe -> a
                          fresh tree (``reuse_tree=True``: the played move's subtree) and ``sims`` simulations with Dirichlet
-                         noise on the root priors -> ``hexgnn_search_record``
-                         (one sample per undecided game into the ring, one move choice per game) -> ``hexgnn_arena_ply`` with
-                         those choices as ``forced`` -> offsets.  ``hexgnn_samples_finish`` labels the match's samples.
+                         noise on the root priors -> ``hexgnn_search_record`` (one sample per undecided game into the ring,
+                         one move choice per game) -> ``hexgnn_arena_ply`` with those choices as ``forced`` -> offsets.
+                         ``hexgnn_samples_finish`` labels the match's samples.
 ``PolicyValueUpdate``    forward, ``ops.PolicyValueLossFn`` (``hexgnn_pv_loss``: the reference's ``val_factor * MSE * B +
                          pol_factor * sum(-target * log_policy)`` with both gradients in one call), backward, optimizer step.
 
@@ -29,7 +29,7 @@ from . import _lib, ops
 from .arena import PICK_GREEDY, ArenaResult, DeviceArena
 from .data import Batch
 from .observation import ObsTarget
-from .search import TreeSearch, check_reuse_arguments, check_round_arguments
+from .search import SearchPlies, TreeSearch, check_round_arguments, tensor_arg
 
 
 class SearchSampleBuffer:
@@ -83,15 +83,12 @@ class SearchSampleBuffer:
         """``hexgnn_search_record``: one sample per recorded game behind ``head``, one move choice per game into ``pick``
         (int32 [G]); ``u``: float32 [G] uniforms for ``pick_mode`` 1."""
         G = search.num_games
-        if pick.dtype != torch.int32 or pick.numel() != G or not pick.is_contiguous():
-            raise ValueError("pick: a contiguous int32 [%d] tensor" % G)
-        if u is not None and (u.dtype != torch.float32 or u.numel() != G or not u.is_contiguous()):
-            raise ValueError("u: a contiguous float32 [%d] tensor" % G)
-        if active is not None and (active.dtype != torch.int32 or active.numel() != G or not active.is_contiguous()):
-            raise ValueError("active: a contiguous int32 [%d] tensor" % G)
+        tensor_arg("pick", pick, torch.int32, G)               # (no device named: the callers pass their arena's tensors)
+        tensor_arg("u", u, torch.float32, G, optional=True)
+        active = tensor_arg("active", active, torch.int32, G, optional=True)
         if search.hex_size != self.hex_size:
             raise ValueError("the search plays Hex-%d, the ring holds Hex-%d" % (search.hex_size, self.hex_size))
-        call = search._call(active=active.data_ptr() if active is not None else None)
+        call = search._call(active=active)
         rec = self.record_call(ply, pick_mode, u, pick)
         _lib.check(_lib.lib().hexgnn_search_record(root_handle, C.byref(call), C.byref(rec), ops._stream()),
                    "hexgnn_search_record")
@@ -163,17 +160,16 @@ class SearchSampleBuffer:
         return b, index
 
 
-class SearchSelfPlay:
+class SearchSelfPlay(SearchPlies):
     """Lock-step self-play of ``num_games`` games of Hex ``hex_size`` with a ``sims``-simulation search on both sides, every
     searched position recorded into ``buffer``.  ``evaluator``: as ``SearchPlayer`` takes it.  ``root_noise = (eps, alpha)``:
     Dirichlet(alpha) noise mixed into the root priors with weight eps after the simulation that expands the root (None: no
     noise).  ``proportional_plies``: the plies of a match (0 ..) whose move is drawn in proportion to the visit counts; from
     there on the most visited move is played (None: every ply is drawn).  ``leaves`` / ``virtual_loss``: as ``TreeSearch`` takes
     them (``sims`` is then what is asked for, collisions included; ``sims > leaves``).  ``reuse_tree=True`` keeps the played
-    move's subtree between plies (the reference's Reuse_Tree): the trees hold ``capacity`` simulations (default ``4 * sims``),
-    are reset once per match and re-rooted after every ply (``TreeSearch.advance``, ``max_carry = capacity - sims``); every ply
-    adds ``sims`` new simulations, and a sample's visit distribution N / T includes the carried visits, as in the reference.
-    ``on_carried``: an optional callable that receives each ``advance``'s ``carried`` tensor."""
+    move's subtree between plies (the reference's Reuse_Tree; ``search.SearchPlies``, shared with ``SearchPlayer``): the trees
+    hold ``capacity`` simulations (default ``4 * sims``), are reset once per match and re-rooted after every ply; every ply adds
+    ``sims`` new simulations, and a sample's visit distribution N / T includes the carried visits, as in the reference."""
 
     def __init__(self, hex_size: int, num_games: int, evaluator, sims: int, buffer: SearchSampleBuffer, c_puct: float = 1.5,
                  root_noise=(0.25, 0.2), proportional_plies=None, prior_temperature: float = 1.0, device=None, leaves: int = 1,
@@ -187,16 +183,14 @@ class SearchSelfPlay:
             raise ValueError("the buffer holds Hex-%d and needs capacity >= num_games * hex_size ** 2" % buffer.hex_size)
         if root_noise is not None and (not 0.0 <= float(root_noise[0]) <= 1.0 or not float(root_noise[1]) > 0):
             raise ValueError("root_noise = (eps in [0, 1], alpha > 0) or None")
-        self.hex_size, self.num_games, self.sims = int(hex_size), int(num_games), int(sims)
+        SearchPlies.__init__(self, sims, reuse_tree, capacity)
+        self.hex_size, self.num_games = int(hex_size), int(num_games)
         self.evaluator, self.buffer, self.root_noise = evaluator, buffer, root_noise
         self.proportional_plies = proportional_plies
         self.arena = DeviceArena(hex_size, num_games, device=device if device is not None else buffer.device, graph=False)
         dev = self.device = self.arena.device
-        self.reuse_tree = bool(reuse_tree)
-        self.capacity = check_reuse_arguments(sims, reuse_tree, capacity)
         self.search = TreeSearch(hex_size, num_games, self.capacity, c_puct, prior_temperature, device=dev, leaves=leaves,
                                  virtual_loss=virtual_loss)
-        self.on_carried = None
         self._zeros = torch.zeros(num_games * self.arena.mgr._nv, dtype=torch.float32, device=dev)
         self._u = torch.zeros(num_games, dtype=torch.float32, device=dev)
 
@@ -212,17 +206,14 @@ class SearchSelfPlay:
         ar._prepare(maker, None)
         buf.discard_pending()
         plies, live = 0, k
-        if self.reuse_tree:
-            s.reset()                                         # once per match; from here the played moves' subtrees are kept
+        self._match_begins(s)                                 # tree reuse: once per match; from here the subtrees are kept
         try:
             while live > 0:
                 if plies >= ar.max_plies:
                     raise RuntimeError("%d games still undecided after %d plies of Hex-%d" % (live, plies, self.hex_size))
                 obs.observe_env(h)
                 active = ((ar.game[:, 0] < 0) & (ar.game[:, 3] == 0)).to(torch.int32)
-                if not self.reuse_tree:
-                    s.reset()
-                s.simulate(h, self.evaluator, self.sims, active=active, root_noise=self.root_noise, generator=generator)
+                self._search_ply(s, h, self.evaluator, active, root_noise=self.root_noise, generator=generator)
                 proportional = self.proportional_plies is None or plies < int(self.proportional_plies)
                 if proportional:
                     torch.rand(k, generator=generator, out=self._u)
@@ -235,10 +226,7 @@ class SearchSelfPlay:
                                               ops._stream()), "hexgnn_arena_ply")
                 _lib.check(L.hexgnn_env_offsets(k, ar.result.data_ptr(), obs.node_off.data_ptr(), obs.edge_off.data_ptr(),
                                                 ops._stream()), "hexgnn_env_offsets")
-                if self.reuse_tree:                           # a resting game's -1 makes its tree fresh
-                    carried = s.advance(ar.log[plies], max_carry=self.capacity - self.sims)
-                    if self.on_carried is not None:
-                        self.on_carried(carried)
+                self._ply_played(s, ar.log[plies])
                 maker = not maker
                 plies += 1
                 live = int(ar.live.item())
